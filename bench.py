@@ -24,6 +24,15 @@ at <= 1e-4 by the parity tests) on this very workload, per parameter group (rota
 to each pose's own translation), and -- `pose_deviation.vs_oracle`, inside the cpu_baseline leg -- against the CPU ORACLE on the
 first 32 detections of the workload through all five iterations, for every benched storage type.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, the N timed steps,
+the outputs of the last timed step when --dump-outputs DIR is given, and the JSON line.  Everything else below -- the single-stream
+schedule, the collective alone, `roofline`, `other_dtypes`, `pose_deviation` and `cpu_baseline` -- is measured only with --full (--layers
+implies it); their fields are null otherwise, and --no-cpu-baseline / --no-other-dtypes / --no-profile drop parts of it.
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned (rank 0): the refined poses of all candidates
+(`poses.npy`) and, where the path returns them, every stage / iteration's result tensors (`<stage>_iteration<k>_<field>.npy`), float32,
+at most 64 MB together (larger outputs: a fixed, seeded sample of rows).  The inputs depend on the arguments alone, so two builds can be
+compared output for output.
+
 One JSON line on stdout (rank 0).  `roofline` is for the dominant kernel FAMILY of the backbone (all instantiations of one
 kernel template together; the dominant single instantiation and the next two are reported beside it), timed live with HIP events recorded on
 the launch stream after every launch (cosy_effnet_b3_set_profiling) in a second pass over the same steps right after the
@@ -320,6 +329,33 @@ def make_scene(syn, torch, tc, pd, labels, seed, D, n_frames, h, w, n_obj, with_
     return frames, K, tc.PandasTensorCollection(infos=infos, bboxes=torch.from_numpy(boxes).cuda())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, poses, preds, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what one step returned, as DIR/<name>.npy in float32 -- `poses` (the refined poses of all candidates) and, when the path
+    returns them, every stage / iteration's collection field by field (`refiner/iteration=4` -> refiner_iteration4_<field>).  The given initial
+    poses of config 2 (`external_coarse`) are an input and are not written.  Above `limit` bytes in all, every array keeps the same fraction of
+    its rows, chosen by a fixed seed (sorted)."""
+    arrays = {'poses': poses}
+    for key, coll in (preds or {}).items():
+        if key == 'external_coarse':
+            continue
+        stage, it = key.split('/')
+        for field, t in coll.tensors.items():
+            arrays[f"{stage}_{it.replace('=', '')}_{field}"] = t
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        frac = limit / total
+        for k, a in arrays.items():
+            keep = int(len(a) * frac)
+            arrays[k] = a[np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -336,14 +372,23 @@ def main():
     ap.add_argument('--streams', type=int, default=None,
                     help='HIP streams the chunks of a stage run on concurrently (CoarseRefinePosePredictor n_streams; default 2); with N > 1 and no '
                          '--bsz-objects the candidates of a rank are cut into N equal chunks')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-dtypes', action='store_true', help='skip the bf16 / fp32 repeats of the timed loop and the deviation pass')
-    ap.add_argument('--no-profile', action='store_true', help='skip the per-kernel HIP-event pass (no roofline object)')
-    ap.add_argument('--layers', action='store_true', help='print the per-launch table to stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline (single-stream schedule, collective alone, per-kernel pass / roofline, '
+                         'bf16 / fp32 repeats and pose deviations, CPU baseline and oracle comparison); off by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the oracle comparison')
+    ap.add_argument('--no-other-dtypes', action='store_true', help='with --full: skip the bf16 / fp32 repeats of the timed loop and the deviation pass')
+    ap.add_argument('--no-profile', action='store_true', help='with --full: skip the per-kernel HIP-event pass (no roofline object)')
+    ap.add_argument('--layers', action='store_true', help='print the per-launch table to stderr (implies --full: the table comes from its per-kernel pass)')
     ap.add_argument('--renderer', default='pregenerated', choices=['pregenerated', 'hip'],
                     help="renderer.render source: pre-generated device images (default: the reference's renderer is outside the "
                          "path) or the on-device HIP rasteriser (SURVEY 8f-1) rendering every crop in every iteration")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.layers:
+        args.full = True
 
     import torch
     import torch.distributed as dist
@@ -425,20 +470,24 @@ def main():
     iters_total = total * (n_coarse + n_refine)
     gather_us = []
     use_dist = dist.is_available() and dist.is_initialized()     # world > 1, or a forced 1-rank RCCL group (COSY_FORCE_DIST=1)
+    last_outputs = {}       # --dump-outputs: the per-iteration collections the last step returned
 
     def step(local_only=False):
+        preds = None
         if cfg_i == 1:
             frames, K, det = scenes[0]
-            final, _ = predictor.get_predictions(frames, K, detections=det, n_coarse_iterations=n_coarse, n_refiner_iterations=n_refine)
+            final, preds = predictor.get_predictions(frames, K, detections=det, n_coarse_iterations=n_coarse, n_refiner_iterations=n_refine)
             poses = final.poses
             if use_dist and not local_only:
                 poses = all_gather_rows(poses, counts=per_rank)   # ONE collective: refined poses of all ranks, rank order
         elif cfg_i == 2:
             frames, K, init = scenes[0]
-            final, _ = get_predictions_sharded(predictor, frames, K, data_TCO_init=init, n_coarse_iterations=0, n_refiner_iterations=n_refine)
+            final, preds = get_predictions_sharded(predictor, frames, K, data_TCO_init=init, n_coarse_iterations=0, n_refiner_iterations=n_refine)
             poses = final.poses
         else:
             poses, _ = get_predictions_sharded_scenes(predictor, scenes, n_coarse, n_refine, **plan_kw)
+        if args.dump_outputs:
+            last_outputs['preds'] = preds
         return poses
 
     def sync():
@@ -461,7 +510,7 @@ def main():
         out = step()
     assert torch.isfinite(out).all(), 'non-finite refined poses'
     assert out.shape == (total, 4, 4)
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     gather_us.clear()
     if gc_late:
         gc.collect()
@@ -474,7 +523,7 @@ def main():
     marks[0].record()
     for i in range(args.steps):
         th = time.perf_counter()
-        step()
+        last_poses = step()
         marks[i + 1].record()
         host_ms.append((time.perf_counter() - th) * 1e3)   # host enqueue time of the step (the GPU runs behind)
     sync()
@@ -486,9 +535,12 @@ def main():
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_poses, last_outputs.get('preds'))
+    last_outputs.clear()
     # the same K steps as ONE stream of full-size launches (the schedule of rounds 1-3's lines), reported beside the headline
     single = None
-    if args.streams > 1 and not args.no_other_dtypes:
+    if args.full and args.streams > 1 and not args.no_other_dtypes:
         predictor.n_streams, predictor.bsz_objects = 1, min(max(per_rank), full_bsz)
         step()
         k1 = max(2, min(args.steps, 8))
@@ -501,7 +553,7 @@ def main():
         single = dict(value=round(iters_total * k1 / d1, 1), ms_per_step=round(1e3 * d1 / k1, 3), steps=k1, bsz_objects=predictor.bsz_objects, streams=1)
         predictor.n_streams, predictor.bsz_objects = args.streams, args.bsz_objects
     # the collective alone, timed in its own pass (device events around the call; nothing is drained inside the timed region)
-    if use_dist and cfg_i == 1:
+    if args.full and use_dist and cfg_i == 1:
         local = step(local_only=True)
         for _ in range(5):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -636,7 +688,7 @@ def main():
 
     # ---- the same timed loop in the other storage types, and the benched type's pose deviation from the fp32 HIP path
     other, deviation = {}, None
-    if not args.no_other_dtypes and args.renderer == 'pregenerated':
+    if args.full and not args.no_other_dtypes and args.renderer == 'pregenerated':
         def run_first(models):
             for m in models:
                 m.renderer.i = 0          # same synthetic renders for every dtype
@@ -691,7 +743,7 @@ def main():
             'ms_per_step': round(1e3 * dt / args.steps, 3), 'higher_is_better': True, 'scaling': scaling, 'vs_baseline': None,
             'dtype': dtype, 'data': 'synthetic',
             'dtype_note': 'BASELINE configs[1] names bf16; bf16 storage misses north_star\'s 1e-4 pose bound, fp16 (same bytes, same MFMA '
-                          'rate) meets it: the headline is fp16, bf16 / fp32 are timed beside it in other_dtypes',
+                          'rate) meets it: the headline is fp16, bf16 / fp32 are timed beside it in other_dtypes (--full)',
             'config_deviation': ({'field': 'dtype', 'baseline': NAMED_DTYPE[cfg_i], 'benched': dtype,
                                   'reason': 'the named type misses north_star\'s 1e-4 pose bound (see other_dtypes.%s: conforms false); same bytes, same '
                                             'MFMA rate; do not compare `value` with a number quoted on the named type without reading other_dtypes' % NAMED_DTYPE[cfg_i]}
@@ -711,7 +763,7 @@ def main():
             'path_hbm_frac': round(value / world * mb * 1e6 / (HBM_PEAK_GBS * 1e9), 5) if mb else None,
             'cpu_baseline': None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if cfg_i == 1 and args.renderer == 'pregenerated':
                 try:      # the bench line's own comparison with the ORACLE (32-crop subset, all five iterations), every benched storage type
                     vo = oracle_deviation(torch, tc, pd, CoarseRefinePosePredictor, coarse, refiner, labels, renders, (H, W),

@@ -12,11 +12,11 @@ export TMPDIR=/tmp
 # 2. per-layer HIP-event table
 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --streams 1 --layers > $OUT/bench_layers.json 2> $OUT/layers_events.txt
 # 3. other configurations on one GPU
-python bench.py --config 2 --no-cpu-baseline > $OUT/bench_config2.json 2> /dev/null
-python bench.py --config 3 --no-cpu-baseline > $OUT/bench_config3_skewed.json 2> /dev/null
-python bench.py --config 3 --split balanced --no-cpu-baseline > $OUT/bench_config3_balanced.json 2> /dev/null
-python bench.py --crop 240x320 --no-cpu-baseline > $OUT/bench_240x320.json 2> /dev/null
-python bench.py --renderer hip --no-cpu-baseline > $OUT/bench_renderer_hip.json 2> /dev/null
+python bench.py --full --config 2 --no-cpu-baseline > $OUT/bench_config2.json 2> /dev/null
+python bench.py --full --config 3 --no-cpu-baseline > $OUT/bench_config3_skewed.json 2> /dev/null
+python bench.py --full --config 3 --split balanced --no-cpu-baseline > $OUT/bench_config3_balanced.json 2> /dev/null
+python bench.py --full --crop 240x320 --no-cpu-baseline > $OUT/bench_240x320.json 2> /dev/null
+python bench.py --full --renderer hip --no-cpu-baseline > $OUT/bench_renderer_hip.json 2> /dev/null
 # 3b. the default is two HIP streams per rank (CoarseRefinePosePredictor n_streams); the single-stream schedule and three streams on config 3 beside it
 python bench.py --streams 1 --no-cpu-baseline --no-other-dtypes --no-profile > $OUT/bench_streams1.json 2> /dev/null
 python bench.py --crop 240x320 --streams 1 --no-cpu-baseline --no-other-dtypes --no-profile > $OUT/bench_240x320_streams1.json 2> /dev/null
@@ -29,7 +29,7 @@ cp gpurun_out/prof_$TAG/stats/*kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/nul
 # 1. headline line, exactly the driver's command -- after the PMC passes, with this call's traffic file in place (bench.py reports
 #    roofline.traffic only from a file collected for the same kernel sources)
 cp $OUT/pmc_traffic.json profiles/${TAG%[a-z]}_pmc_traffic.json 2>/dev/null
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # 5. batch sweep: throughput and matrix-core utilisation of the GEMM kernels at 256..2048 crops per forward
 for B in 256 512 1024 2048; do
   python bench.py --steps 4 --warmup 2 --detections $B --bsz-objects $B --streams 1 --no-cpu-baseline --no-profile --no-other-dtypes > $OUT/sweep_B$B.json 2> /dev/null

@@ -371,3 +371,32 @@ def test_predictor_accepts_models_with_the_reference_forward_signature():
     assert Foreign.calls == 6 and not CoarseRefinePosePredictor._accepts(Foreign(), 'out')
     from cosypose_amd.pose import PosePredictor
     assert CoarseRefinePosePredictor._accepts(PosePredictor.__new__(PosePredictor), 'out')
+
+
+def test_bench_dump_outputs_writes_float32_arrays_within_the_cap(tmp_path):
+    """bench.py --dump-outputs: the step's poses and every stage / iteration field as <name>.npy in float32 (16-bit fields widened), the given
+    initial poses of config 2 left out; above the byte cap every array keeps the same seeded, sorted rows, so two runs write the same files."""
+    import bench
+    from cosypose_amd import tensor_collection as tc
+    n = 64
+    g = torch.Generator().manual_seed(0)
+    infos = pd.DataFrame(dict(label=['obj_1'] * n, batch_im_id=0, score=1.0))
+    preds = {'external_coarse': tc.PandasTensorCollection(infos, poses=torch.rand(n, 4, 4, generator=g)),
+             'refiner/iteration=1': tc.PandasTensorCollection(infos, poses=torch.rand(n, 4, 4, generator=g), K_crop=torch.rand(n, 3, 3, generator=g),
+                                                              boxes_crop=torch.rand(n, 4, generator=g).half())}
+    poses = torch.rand(n, 4, 4, generator=g)
+    bench.dump_outputs(tmp_path / 'all', poses, preds)
+    got = {p.stem: np.load(p) for p in (tmp_path / 'all').iterdir()}
+    assert sorted(got) == ['poses', 'refiner_iteration1_K_crop', 'refiner_iteration1_boxes_crop', 'refiner_iteration1_poses']
+    assert all(a.dtype == np.float32 and len(a) == n for a in got.values())
+    assert np.array_equal(got['poses'], poses.numpy())
+    assert np.array_equal(got['refiner_iteration1_boxes_crop'], preds['refiner/iteration=1'].boxes_crop.float().numpy())
+    cap = 4096
+    for d in ('a', 'b'):
+        bench.dump_outputs(tmp_path / d, poses, preds, limit=cap)
+    a = {p.stem: np.load(p) for p in (tmp_path / 'a').iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / 'b').iterdir()}
+    assert sum(v.nbytes for v in a.values()) <= cap and 0 < len(a['poses']) < n
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    rows = [i for i in range(n) if any(np.array_equal(poses.numpy()[i], r) for r in a['poses'])]
+    assert np.array_equal(a['poses'], poses.numpy()[rows])        # whole rows, in their order
