@@ -1236,7 +1236,8 @@ int cosy_crop_pack_to_ws(void* x_nhwc8, int dtype, const float* frames_nhwc4, co
 int cosy_bn_train_stats(const float* x, long M, int C, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                         float* running_var, void* workspace, cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    COSY_REQUIRE(x && mean && rstd && workspace && M > 0 && C > 0, "bn_train_stats: bad argument");
+    COSY_REQUIRE(x && mean && rstd && workspace && M > 0, "bn_train_stats: bad argument (M=%ld)", M);
+    COSY_REQUIRE(C > 0 && C % 4 == 0, "bn_train_stats: C=%d must be a positive multiple of 4 (16-byte channel quads)", C);
     const RedGeom g = red_geom(M, C);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(g.cgroups, g.nslab), dim3(256), 0, s, x, M, C, g.rows_per_slab, (double*)workspace);
     COSY_CHECK_HIP(hipGetLastError());
@@ -1296,6 +1297,8 @@ int cosy_dw_train_forward(const float* x, const float* wt, int B, int H, int W, 
                           cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(x && wt && out && C % 4 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_train_forward: bad argument");
+    // static "same" padding of stride 2 pads k - 2 in total: a 1-pixel side has no output (arch.conv_out), the C division below would say 1
+    COSY_REQUIRE(stride == 1 || (H >= 2 && W >= 2), "dw_train_forward: stride 2 needs H >= 2 and W >= 2 (H=%d, W=%d)", H, W);
     const int lo = stride == 1 ? (k - 1) / 2 : (k - 2) / 2;
     const int Ho = stride == 1 ? H : (H + (k - 2) - k) / 2 + 1, Wo = stride == 1 ? W : (W + (k - 2) - k) / 2 + 1;
     const long n4 = (long)B * Ho * Wo * (C / 4);
@@ -1318,6 +1321,7 @@ int cosy_dw_train_backward_data_add(const float* dy, const float* wt, const floa
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(dy && wt && dx && C % 4 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_train_backward_data: bad argument");
     COSY_REQUIRE(!add || stride == 1, "dw_train_backward_data: the fused skip gradient exists for stride 1 (blocks with a skip connection)%s", "");
+    COSY_REQUIRE(stride == 1 || (H >= 2 && W >= 2), "dw_train_backward_data: stride 2 needs H >= 2 and W >= 2 (H=%d, W=%d)", H, W);
     const int lo = stride == 1 ? (k - 1) / 2 : (k - 2) / 2;
     const int Ho = stride == 1 ? H : (H + (k - 2) - k) / 2 + 1, Wo = stride == 1 ? W : (W + (k - 2) - k) / 2 + 1;
     const long n4 = (long)B * H * W * (C / 4);
@@ -1341,6 +1345,7 @@ int cosy_dw_train_backward_weight_ex(const float* x, const float* dy, int B, int
     hipStream_t s = (hipStream_t)stream;
     float* dwt = dw;
     COSY_REQUIRE(x && dy && dwt && workspace && (k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_train_backward_weight: bad argument");
+    COSY_REQUIRE(stride == 1 || (H >= 2 && W >= 2), "dw_train_backward_weight: stride 2 needs H >= 2 and W >= 2 (H=%d, W=%d)", H, W);
     const int lo = stride == 1 ? (k - 1) / 2 : (k - 2) / 2;
     const int Ho = stride == 1 ? H : (H + (k - 2) - k) / 2 + 1, Wo = stride == 1 ? W : (W + (k - 2) - k) / 2 + 1;
     const long nunits = (long)B * Ho * cdiv(Wo, 4);     // unit = a run of 4 output pixels of one row (RUN in the kernel)
@@ -1470,7 +1475,8 @@ static int rows_chunks(int B, int HW, int C, int* rows_per_chunk) {
     return cdiv(HW, *rows_per_chunk);
 }
 int cosy_rows_mean(const float* a, int B, int HW, int C, float* out, void* workspace, cosy_stream_t stream) {
-    COSY_REQUIRE(a && out && workspace && B > 0 && HW > 0 && C > 0, "rows_mean: bad argument");
+    COSY_REQUIRE(a && out && workspace && B > 0 && HW > 0, "rows_mean: bad argument (B=%d, HW=%d)", B, HW);
+    COSY_REQUIRE(C > 0 && C % 4 == 0, "rows_mean: C=%d must be a positive multiple of 4 (16-byte channel quads)", C);
     int rpc;
     const int nchunk = rows_chunks(B, HW, C, &rpc);
     hipLaunchKernelGGL(rows_reduce_kernel<0>, dim3(cdiv(C, 64), B, nchunk), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, HW, C,
@@ -1482,7 +1488,8 @@ int cosy_rows_mean(const float* a, int B, int HW, int C, float* out, void* works
     return COSY_OK;
 }
 int cosy_rows_dot(const float* a, const float* a2, int B, int HW, int C, float* out, void* workspace, cosy_stream_t stream) {
-    COSY_REQUIRE(a && a2 && out && workspace && B > 0 && HW > 0 && C > 0, "rows_dot: bad argument");
+    COSY_REQUIRE(a && a2 && out && workspace && B > 0 && HW > 0, "rows_dot: bad argument (B=%d, HW=%d)", B, HW);
+    COSY_REQUIRE(C > 0 && C % 4 == 0, "rows_dot: C=%d must be a positive multiple of 4 (16-byte channel quads)", C);
     int rpc;
     const int nchunk = rows_chunks(B, HW, C, &rpc);
     hipLaunchKernelGGL(rows_reduce_kernel<1>, dim3(cdiv(C, 64), B, nchunk), dim3(256), 0, (hipStream_t)stream, a, a2, HW, C, rpc,

@@ -204,7 +204,8 @@ size_t cosy_crop_pack_workspace_bytes(int B, int H, int W);
 int cosy_crop_pack_to_ws(void* x_nhwc8, int dtype, const float* frames_nhwc4, const int* im_id, const float* boxes_crop,
                          const float* renders, int B, int N, int h, int w, int H, int W, void* workspace, cosy_stream_t stream);
 /* nn.BatchNorm2d in train mode (efficientnet.py:49-68; eps 1e-3, momentum 0.01): batch mean / 1/sqrt(biased var + eps)
- * per channel over the M rows; running_mean/var (optional) updated in place with the unbiased variance. */
+ * per channel over the M rows; running_mean/var (optional) updated in place with the unbiased variance.  C % 4 == 0
+ * (rows are read as 16-byte channel quads), else COSY_EINVAL. */
 int cosy_bn_train_stats(const float* x, long M, int C, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                         float* running_var, void* workspace, cosy_stream_t stream);
 /* out = act((x-mean)*rstd*gamma+beta) [* rowscale[row/HW]] [+ res];  act 0 none / 1 Swish; rowscale = drop_connect's
@@ -222,7 +223,9 @@ int cosy_bn_train_backward(const float* dout, const float* x, const float* mean,
 int cosy_bn_train_backward_gated(const float* dout, const float* cgate, const float* cadd, float cadd_scale, const float* x, const float* mean,
                                  const float* rstd, const float* gamma, const float* beta, long M, int C, int act, const float* rowscale, int HW,
                                  float* dgamma, float* dbeta, int accumulate, float* dx, float* sums, void* workspace, cosy_stream_t stream);
-/* depthwise convolution with the reference's static "same" padding; weights transposed to (k*k, C) */
+/* depthwise convolution with the reference's static "same" padding; weights transposed to (k*k, C); C % 4 == 0.
+ * Output size: H x W at stride 1, ((H - 2) / 2 + 1) x ((W - 2) / 2 + 1) at stride 2 (arch.conv_out).  Stride 2 needs H >= 2 and
+ * W >= 2 (a 1-pixel side has no output under that padding): COSY_EINVAL otherwise, for the forward and both gradients. */
 int cosy_dw_train_forward(const float* x, const float* wt, int B, int H, int W, int C, int k, int stride, float* out,
                           cosy_stream_t stream);
 int cosy_dw_train_backward_data(const float* dy, const float* wt, int B, int H, int W, int C, int k, int stride, float* dx,
@@ -232,7 +235,8 @@ int cosy_dw_train_backward_data_add(const float* dy, const float* wt, const floa
                                     cosy_stream_t stream);
 int cosy_dw_train_backward_weight(const float* x, const float* dy, int B, int H, int W, int C, int k, int stride, float* dwt,
                                   void* workspace, cosy_stream_t stream);
-/* module_layout = 1: the gradient is written as (C, k*k) = the module's _depthwise_conv.weight (C,1,k,k) instead of [tap][channel] */
+/* module_layout = 0 (and cosy_dw_train_backward_weight): the gradient as [tap][channel] (k*k, C), the layout of `wt`;
+ * module_layout = 1: as (C, k*k) = the module's _depthwise_conv.weight (C,1,k,k).  The two are transposes of each other bit for bit. */
 int cosy_dw_train_backward_weight_ex(const float* x, const float* dy, int B, int H, int W, int C, int k, int stride, float* dw, int module_layout,
                                      void* workspace, cosy_stream_t stream);
 /* 1x1 convolutions of the training step on the library's own fp32 MFMA GEMMs (no rocBLAS on the path):
@@ -258,7 +262,8 @@ int cosy_train_gemm_packed(const float* A, const float* pool, long long packed_o
 int cosy_wgrad_tall_supported(long M, int N, int K);
 int cosy_wgrad_tall(const float* dY, const float* X, long M, int N, int K, float* dW, void* workspace, cosy_stream_t stream);
 /* per-sample reductions / broadcasts over the HW pixels of a (B,HW,C) activation: mean (adaptive_avg_pool2d),
- * sum of a*a2 (gradient of the squeeze-excite gate), a*g[b,c] (+ add[b,c]*add_scale), v[b,c]*scale broadcast */
+ * sum of a*a2 (gradient of the squeeze-excite gate), a*g[b,c] (+ add[b,c]*add_scale), v[b,c]*scale broadcast.
+ * All of them need C % 4 == 0 (16-byte channel quads), else COSY_EINVAL. */
 int cosy_rows_mean(const float* a, int B, int HW, int C, float* out, void* workspace, cosy_stream_t stream);
 /* Squeeze-excite without the unscaled activation in memory (efficientnet.py:84-90 in train mode): the per-sample means / dot products take the
  * BatchNorm INPUT `raw` and recompute swish(bn(raw)) per element (the arithmetic of cosy_bn_train_apply), and cosy_bn_train_apply_gated writes
