@@ -11,7 +11,7 @@ COSY_F32, COSY_BF16, COSY_F16 = 0, 1, 2
 _lib = None
 
 _c = ctypes
-_P, _I, _F, _SZ, _L = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_long
+_P, _I, _F, _SZ, _L, _D = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_long, _c.c_double
 
 _SIGNATURES = {
     'cosy_version': ([], _I),
@@ -84,6 +84,12 @@ _SIGNATURES = {
     'cosy_stem_im2col': ([_P, _I, _I, _I, _P, _P], _I),
     'cosy_loss_refiner_disentangled_backward': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
     'cosy_grad_norm_clip': ([_P, _L, _F, _P, _P, _P], _I),
+    'cosy_symmetric_distance_reprojected': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    'cosy_ba_workspace_bytes': ([_I, _I, _I, _I], _SZ),
+    'cosy_ba_upload_ids': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    'cosy_ba_align': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    'cosy_ba_linearize': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_ba_solve': ([_P, _P, _I, _D, _P, _P, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -1,4 +1,4 @@
-"""Symmetric pose distances, same surface as the reference's cosypose/lib3d/symmetric_distances.py:8-57.
+"""Symmetric pose distances, same surface as the reference's cosypose/lib3d/symmetric_distances.py:8-57 and :94-121.
 
 The reference expands every (sample, symmetry) pair on the host (cosypose_cext.expand_ids_for_symmetry), gathers
 points and symmetries per pair, computes one distance per pair, copies the distances to the CPU and runs a C++
@@ -73,3 +73,28 @@ def symmetric_distance_batched(T1, T2, labels, mesh_db):
 def symmetric_distance_batched_fast(T1, T2, labels, mesh_db):
     """Same with the best symmetry chosen by the mean SQUARED distance over the padded table (reference :39-57)."""
     return _symmetric_distance(T1, T2, labels, mesh_db, 1)
+
+
+def symmetric_distance_reprojected(T1, T2, K, labels, mesh_db):
+    """min over the object's symmetries S of mean_p |project(K, T1 S, p) - project(K, T2, p)| in pixels, and that S (reference
+    :94-121; project_points without a z clamp).  One launch of cosy_symmetric_distance_reprojected."""
+    bsz = T1.shape[0]
+    assert T1.shape == (bsz, 4, 4)
+    assert T2.shape == (bsz, 4, 4)
+    assert K.shape == (bsz, 3, 3)
+    assert len(labels) == bsz
+    if bsz == 0:
+        return torch.empty(0, dtype=T1.dtype, device=T1.device), torch.empty(0, 4, 4, dtype=T1.dtype, device=T1.device)
+    require_device(T1, T2, K, mesh_db.points, mesh_db.symmetries)
+    dev = T1.device
+    T1c, T2c, Kc = T1.detach().float().contiguous(), T2.detach().float().contiguous(), K.detach().float().contiguous()
+    pts = mesh_db.points.detach().float().contiguous()
+    sym = mesh_db.symmetries.detach().float().contiguous()
+    obj = mesh_db.object_ids(labels, dev)
+    n_sym = _n_sym_table(mesh_db, dev)
+    min_dists = torch.empty(bsz, device=dev)
+    best = torch.empty(bsz, dtype=torch.int32, device=dev)
+    S12 = torch.empty(bsz, 4, 4, device=dev)
+    check(lib().cosy_symmetric_distance_reprojected(ptr(T1c), ptr(T2c), ptr(Kc), ptr(obj), ptr(pts), ptr(sym), ptr(n_sym), bsz, pts.shape[0],
+                                                    pts.shape[1], sym.shape[1], ptr(min_dists), ptr(best), ptr(S12), stream()))
+    return min_dists, S12

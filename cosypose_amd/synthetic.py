@@ -175,3 +175,111 @@ def make_render_meshes(seed, n_obj, n_lat=24, n_lon=32):
         colors_l.append(np.clip(base + 0.3 * dirs * rs.uniform(-1, 1, 3), 0, 1).astype(np.float32))
         faces_l.append(faces)
     return verts_l, faces_l, colors_l
+
+
+# ---- multi-view scenes for the bundle adjustment (cosypose_amd/bundle_adjustment.py) ----------------------------------------
+BA_N_SYM = (1, 2, 4, 3)     # real symmetries of the four synthetic meshes (rotations about z), identity-padded to S = 4
+
+
+def _rodrigues(rs, angle_std):
+    """rotation by N(0, angle_std) radians about a random axis"""
+    axis = rs.randn(3)
+    axis /= np.linalg.norm(axis)
+    a = rs.randn() * angle_std
+    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(a) * Kx + (1 - np.cos(a)) * (Kx @ Kx)
+
+
+def _rigid_noise(rs, angle_std, trans_std):
+    T = np.eye(4)
+    T[:3, :3] = _rodrigues(rs, angle_std)
+    T[:3, 3] = rs.randn(3) * trans_std
+    return T
+
+
+def make_ba_scene(seed, n_objects, n_views, n_points, exact_pairs=False, p_visible=0.75):
+    """A seeded multi-view scene, float64: objects standing on a table, cameras on a 0.9 m hemisphere looking at the origin
+    (600 px focal, 640x480), per-view candidates = true pose . a random symmetry of the mesh . noise (0.03 rad, 4 mm), all
+    ordered view pairs with relative poses noisy by 0.02 rad / 5 mm (or exact).  n_points == 8 gives the corners of each mesh's
+    bounding box.  -> dict of numpy arrays: the mesh tables (pts, sym, n_sym), the candidates' columns (cand_view_id, cand_obj_id,
+    cand_label_id, cand_score, cand_poses), the cameras' (cam_view_id, cam_K, cam_TWC: the truth) and the pairs' (pair_view1,
+    pair_view2, pair_TC1C2)."""
+    rs = np.random.RandomState(seed)
+    n_mesh, S = len(BA_N_SYM), max(BA_N_SYM)
+    ext = rs.uniform(0.03, 0.12, (n_mesh, 1, 3))
+    if n_points == 8:
+        corners = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], np.float64)
+        pts = corners[None] * ext
+    else:
+        pts = rs.uniform(-1, 1, (n_mesh, n_points, 3)) * ext
+    sym = np.tile(np.eye(4), (n_mesh, S, 1, 1))
+    for m in range(n_mesh):
+        for k in range(1, BA_N_SYM[m]):
+            a = 2 * np.pi * k / BA_N_SYM[m]
+            sym[m, k, :3, :3] = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+    obj_mesh = rs.randint(0, n_mesh, n_objects)
+    TWO = np.tile(np.eye(4), (n_objects, 1, 1))
+    for o in range(n_objects):
+        a = rs.uniform(0, 2 * np.pi)
+        TWO[o, :3, :3] = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+        TWO[o, :3, 3] = [rs.uniform(-0.25, 0.25), rs.uniform(-0.25, 0.25), ext[obj_mesh[o], 0, 2]]
+    TWC = np.tile(np.eye(4), (n_views, 1, 1))
+    for v in range(n_views):
+        az, el = rs.uniform(0, 2 * np.pi), rs.uniform(np.radians(25), np.radians(75))
+        c = 0.9 * np.array([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)])
+        z = -c / np.linalg.norm(c)                       # optical axis: towards the origin
+        x = np.cross(z, [0., 0., 1.]); x /= np.linalg.norm(x)
+        TWC[v, :3, :3] = np.stack([x, np.cross(z, x), z], axis=1)
+        TWC[v, :3, 3] = c
+    TCW = np.linalg.inv(TWC)
+    visible = rs.uniform(size=(n_objects, n_views)) < p_visible
+    for o in range(n_objects):                           # every object is seen at least once, every view sees something
+        if not visible[o].any():
+            visible[o, rs.randint(n_views)] = True
+    for v in range(n_views):
+        if not visible[:, v].any():
+            visible[rs.randint(n_objects), v] = True
+    view_ids, obj_ids = 10 + 3 * np.arange(n_views), 100 + np.arange(n_objects)
+    cv, co, cl, cp = [], [], [], []
+    for v in range(n_views):
+        for o in range(n_objects):
+            if visible[o, v]:
+                m = obj_mesh[o]
+                cv.append(view_ids[v]); co.append(obj_ids[o]); cl.append(m)
+                cp.append(TCW[v] @ TWO[o] @ sym[m, rs.randint(BA_N_SYM[m])] @ _rigid_noise(rs, 0.03, 0.004))
+    p1, p2, pt = [], [], []
+    for a in range(n_views):
+        for b in range(n_views):
+            if a != b:
+                T = TCW[a] @ TWC[b]
+                p1.append(view_ids[a]); p2.append(view_ids[b])
+                pt.append(T if exact_pairs else T @ _rigid_noise(rs, 0.02, 0.005))
+    K = np.tile(np.array([[600., 0, 320], [0, 600., 240], [0, 0, 1]]), (n_views, 1, 1))
+    return dict(pts=pts, sym=sym, n_sym=np.array(BA_N_SYM, np.int32), cand_view_id=np.array(cv, np.int64), cand_obj_id=np.array(co, np.int64),
+                cand_label_id=np.array(cl, np.int64), cand_score=rs.uniform(0.5, 1.0, len(cv)), cand_poses=np.array(cp),
+                cam_view_id=view_ids.astype(np.int64), cam_K=K, cam_TWC=TWC, pair_view1=np.array(p1, np.int64),
+                pair_view2=np.array(p2, np.int64), pair_TC1C2=np.array(pt).reshape(-1, 4, 4))
+
+
+def ba_scene_collections(scene, make_mesh_db, dtype=None, device=None, collection=None):
+    """(candidates, cameras, pairs_TC1C2, mesh_db) of a make_ba_scene dict (or the same columns loaded from a fixture) as
+    PandasTensorCollections.  `make_mesh_db(infos, labels, points, symmetries)` is the BatchedMeshes class to use, `collection` the
+    PandasTensorCollection class (default: this package's)."""
+    import pandas as pd
+    import torch
+    if collection is None:
+        from .tensor_collection import PandasTensorCollection as collection
+    PandasTensorCollection = collection
+    dtype = dtype or torch.float64
+
+    def t(a):
+        out = torch.as_tensor(np.asarray(a)).to(dtype)
+        return out.to(device) if device is not None else out
+    labels = np.array([f'obj_{i:06d}' for i in range(1, len(scene['n_sym']) + 1)])
+    infos = {l: dict(label=l, n_points=scene['pts'].shape[1], n_sym=int(scene['n_sym'][i])) for i, l in enumerate(labels)}
+    mesh_db = make_mesh_db(infos, labels, t(scene['pts']), t(scene['sym']))
+    cand = PandasTensorCollection(pd.DataFrame(dict(view_id=scene['cand_view_id'], obj_id=scene['cand_obj_id'],
+                                                    label=labels[scene['cand_label_id']], score=scene['cand_score'])), poses=t(scene['cand_poses']))
+    cams = PandasTensorCollection(pd.DataFrame(dict(view_id=scene['cam_view_id'])), K=t(scene['cam_K']))
+    pairs = PandasTensorCollection(pd.DataFrame(dict(view1=scene['pair_view1'], view2=scene['pair_view2'])), TC1C2=t(scene['pair_TC1C2']))
+    return cand, cams, pairs, mesh_db

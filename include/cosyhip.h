@@ -174,6 +174,13 @@ int cosy_expand_ids_for_symmetry(const int* n_sym_item, int B, int* ids_expand, 
 int cosy_symmetric_distance(const float* T1, const float* T2, const int* obj_id, const float* pts_table, const float* sym_table,
                             const int* n_sym, int B, int P, int S, int mode, float* min_dists, int* best_sym, float* S12,
                             cosy_stream_t stream);
+/* symmetric_distance_reprojected (cosypose/lib3d/symmetric_distances.py:94-121): per item, over the object's n_sym real symmetries S_k,
+ * the mean over its P points of the PIXEL distance between project(K, T1 S_k, p) and project(K, T2, p) (camera_geometry.py:4-15, no z
+ * clamp); strict <, first wins.  K (B,3,3); n_obj = rows of the tables (>= B when obj_id is NULL).  -> min_dists (B), best_sym (B) int32,
+ * S12 (B,4,4) = sym_table[obj, best].  An item whose object id is outside [0, n_obj) or whose n_sym is <= 0 gets NaN, -1 and a zero S12. */
+int cosy_symmetric_distance_reprojected(const float* T1, const float* T2, const float* K, const int* obj_id, const float* pts_table,
+                                        const float* sym_table, const int* n_sym, int B, int n_obj, int P, int S, float* min_dists,
+                                        int* best_sym, float* S12, cosy_stream_t stream);
 /* loss_CO_symmetric with l1 (cosypose/lib3d/cosypose_ops.py:34-46), forward value: per sample the minimum over the S
  * possible ground truths of mean |pred points - gt points| (first minimum wins, torch.min) -> loss (B), min_id (B)
  * int32 (optional), TCO_assign (B,4,4) (optional). */
@@ -358,6 +365,38 @@ int cosy_render_crop_pack(cosy_net_t* net, const cosy_mesh_t* mesh, const cosy_s
 int cosy_render_crop_pack_to(void* x_nhwc8, int dtype, const cosy_mesh_t* mesh, const cosy_shade_t* shade, const int* obj_id,
                              const float* TCO, const float* K_crop, const float* frames_nhwc4, const int* im_id, const float* boxes_crop,
                              int B, int N, int h, int w, int H, int W, void* scratch, cosy_stream_t stream);
+
+/* ---- scene-level bundle adjustment (cosypose/multiview/bundle_adjustment.py:164-222), ALL FLOAT64 ----
+ * States are 9-D poses (ortho6d rotation, translation; transform_ops.py:54-64): TWO_9d (n_obj,9) of the objects, TCW_9d (n_views,9) of the
+ * cameras.  Candidate c observes object cand_obj[c] in view cand_view[c] with pose cand_TCO[c] (n_cand,4,4); K (n_views,3,3).  Points and
+ * symmetries come from per-mesh tables pts_table (n_mesh,P,3), sym_table (n_mesh,S,4,4), n_sym (n_mesh) int32; cand_mesh[c] / obj_mesh[o]
+ * are the table rows of a candidate's label / an object's label.  The unknowns are ordered objects first: n = 9 (n_obj + n_views), and
+ * n_obj + n_views <= 128 (COSY_ESIZE beyond).  Residual r = (c P + point) 2 + (0: x, 1: y), the reference's order.
+ *
+ * cosy_ba_upload_ids: checks the HOST id arrays against their tables (COSY_EINVAL names the first id outside; nothing is copied or
+ *   launched) and copies them into `ids` (3 n_cand + n_obj int32 on the device), the id table every call below takes.
+ * cosy_ba_align (:164-173): TCO = TCW[view] TWO[obj]; best symmetry of each candidate against it by the reprojected distance above;
+ *   -> dists (n_cand), best_sym (n_cand) int32, TCO_cand_aligned (n_cand,4,4) = cand_TCO S.
+ * cosy_ba_linearize (:175-214 and the products of :218-219): errors e = y - yhat (n_res = 2 P n_cand), loss = mean(min(e^2, threshold))
+ *   (1 double; the clamp enters the loss only), A = J^T J (n,n), b = J^T e (n) with J the ANALYTIC Jacobian of yhat, accumulated as
+ *   per-candidate 18x18 blocks summed in candidate order (no atomics: bit-identical from run to run).  J_obj, J_view (n_res,9) each,
+ *   optional: the Jacobian rows with respect to the residual's own object / view (every other entry of the dense row is 0).
+ * cosy_ba_solve (:216-222): h = (A + lambda I)^-1 b by Cholesky, lambda > 0; n <= 1152.
+ * workspace: cosy_ba_workspace_bytes(n_cand, P, n_obj, n_views) bytes of device scratch (0 for sizes the calls reject) = the larger of
+ *   what cosy_ba_linearize needs (190 doubles per candidate) and what cosy_ba_solve needs (n*n doubles for the factor).  The two SHARE it
+ *   from offset 0: a solve overwrites the linearisation's scratch, which is dead by then (A and b are complete when cosy_ba_linearize's
+ *   launches have run; calls on one stream are ordered).  Do not share one workspace between streams. */
+size_t cosy_ba_workspace_bytes(int n_cand, int P, int n_obj, int n_views);
+int cosy_ba_upload_ids(const int* host_cand_obj, const int* host_cand_view, const int* host_cand_mesh, const int* host_obj_mesh, int n_cand,
+                       int n_obj, int n_views, int n_mesh, int* ids, cosy_stream_t stream);
+int cosy_ba_align(const double* TWO_9d, const double* TCW_9d, const double* cand_TCO, const double* K, const int* ids, const double* pts_table,
+                  const double* sym_table, const int* n_sym, int n_cand, int n_obj, int n_views, int n_mesh, int P, int S, double* dists,
+                  int* best_sym, double* TCO_cand_aligned, cosy_stream_t stream);
+int cosy_ba_linearize(const double* TWO_9d, const double* TCW_9d, const double* TCO_cand_aligned, const double* K, const int* ids,
+                      const double* pts_table, int n_cand, int n_obj, int n_views, int n_mesh, int P, double residuals_threshold,
+                      double* errors, double* loss, double* A, double* b, double* J_obj, double* J_view, void* workspace,
+                      cosy_stream_t stream);
+int cosy_ba_solve(const double* A, const double* b, int n, double lambda, double* h, void* workspace, cosy_stream_t stream);
 
 #ifdef __cplusplus
 }
