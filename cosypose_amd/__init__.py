@@ -19,6 +19,12 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('HipBatchRenderer', 'RenderMeshes'):
         from . import rasterizer
         return getattr(rasterizer, name)
+    if name == 'MultiviewScenePredictor':
+        from .multiview_predictor import MultiviewScenePredictor
+        return MultiviewScenePredictor
+    if name == 'multiview_candidate_matching':
+        from .multiview_matching import multiview_candidate_matching
+        return multiview_candidate_matching
     if name == 'h_pose':
         from .pose_forward_loss import h_pose
         return h_pose

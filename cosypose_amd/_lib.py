@@ -90,6 +90,11 @@ _SIGNATURES = {
     'cosy_ba_align': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
     'cosy_ba_linearize': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     'cosy_ba_solve': ([_P, _P, _I, _D, _P, _P, _P], _I),
+    'cosy_ransac_max_tmatches': ([], _I),
+    'cosy_ransac_hypotheses': ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
+    'cosy_ransac_score': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_ransac_best': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+                         _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

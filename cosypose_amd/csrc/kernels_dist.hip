@@ -9,29 +9,13 @@
 // of the P-term sums differs (~1e-7 relative).  Index results (best symmetry, assigned ground truth, nearest point)
 // follow the reference's tie rule: strict <, first index wins.
 #include "cosy_common.h"
+#include "dist_device.h"
 
 #pragma clang fp contract(off)
 
 namespace cosy {
 
 namespace {
-
-__device__ __forceinline__ void mat4_mul(const float* A, const float* Bm, float* C) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc += A[i * 4 + k] * Bm[k * 4 + j];
-            C[i * 4 + j] = acc;
-        }
-}
-// transform_pts (lib3d/transform_ops.py:7-21): R p + t
-__device__ __forceinline__ void xform_pt(const float* T, float x, float y, float z, float* q) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) q[i] = ((T[i * 4 + 0] * x + T[i * 4 + 1] * y) + T[i * 4 + 2] * z) + T[i * 4 + 3];
-}
 
 // sum over the 256 threads of a workgroup in a fixed order: lanes by xor-shuffle tree, then waves 0..3 in sequence.
 // `scratch` = 4 floats of LDS per reduced value.  Returns the total in every thread.

@@ -87,6 +87,16 @@ class BatchedMeshes(TensorCollection):
             self._tables[key] = tab
         return tab
 
+    def aabb(self):
+        """A BatchedMeshes of the same objects whose points are the 8 corners of each object's axis-aligned bounding box, built from
+        the point table where it lies (the reference's MeshDataBase.batched(aabb=True); corner order of mesh_ops.py:15-28).  This is
+        what the multi-view matching measures its distances over."""
+        lo, hi = self.points.min(dim=1).values, self.points.max(dim=1).values
+        pick = torch.tensor([[0, 1, 1], [1, 1, 1], [1, 0, 1], [0, 0, 1], [0, 1, 0], [1, 1, 0], [1, 0, 0], [0, 0, 0]], dtype=torch.bool,
+                            device=self.points.device)
+        corners = torch.where(pick[None], hi[:, None, :], lo[:, None, :]).contiguous()
+        return BatchedMeshes(self.infos, self.labels, corners, self.symmetries)
+
     def to(self, torch_attr):
         super().to(torch_attr)
         self._tables.clear()

@@ -398,6 +398,42 @@ int cosy_ba_linearize(const double* TWO_9d, const double* TCW_9d, const double* 
                       cosy_stream_t stream);
 int cosy_ba_solve(const double* A, const double* b, int n, double lambda, double* h, void* workspace, cosy_stream_t stream);
 
+/* ---- multi-view candidate matching, CosyPose stage 2 (cosypose/multiview/ransac.py:19-88, csrc/cosypose_cext.cpp:107-216), float32 ----
+ * The scene: cand_poses (n_cand,4,4) TCO of every candidate, cand_mesh (n_cand) int32 row of its label in pts_table (n_mesh,P,3) /
+ * sym_table (n_mesh,S,4,4, identity-padded) / n_sym (n_mesh) int32.  Tentative matches are stored once per ORDERED view pair, not per
+ * hypothesis: tmatches (n_tm,4) int32 = cand1, cand2, rank of cand1 among the pair's cand1s, rank of cand2 among its cand2s (both
+ * < the pair's number of matches); the matches of pair p are rows pair_off[p] .. pair_off[p+1].  max_tm = the longest such list;
+ * beyond cosy_ransac_max_tmatches() (4096) the calls return COSY_ESIZE.  All pointers are device pointers.  Ids outside their tables
+ * are skipped (no inlier / best_sym -1), never dereferenced; callers check them on the host.
+ *
+ * cosy_ransac_hypotheses: seeds (H,4) int32 = match1 (a, b), match2 (g, d).  Over the n_sym symmetries S of a's label: the
+ *   symmetric_distance_batched_fast distance (as cosy_symmetric_distance, mode 1) of a's label between TC1Og and
+ *   ((TC1Oa S) inv(TC2Ob)) TC2Od; the first strict minimum S* -> TC1C2 (H,4,4) = (TC1Oa S*) inv(TC2Ob), best_sym (H), gap (H) = runner-up
+ *   distance - minimum (inf with one symmetry); sym_dists (H,S), optional: every symmetry's distance (inf beyond n_sym).  S <= 64.
+ * cosy_ransac_score: hypothesis h belongs to view pair hyp_pair[h].  Distance of each of the pair's matches = the same distance between
+ *   TC1Oa and TC1C2[h] TC2Ob; inliers: distance <= dist_threshold; ordered by (distance, list position) and walked greedily so that every
+ *   cand1 and every cand2 is used once -> n_inliers (H) int32, dists_sum (H) added in that order.  Optional tables, both laid out as the
+ *   reference's expanded list (hypothesis h's matches from hyp_dist_off[h] on, (H) int64): dists_out receives the distances, dists_in
+ *   REPLACES them (the reference's find_ransac_inliers on given distances; the scene and TC1C2 are then not read and may be NULL / 0).
+ * cosy_ransac_best: the hypotheses of pair p are pair_hyps[pair_hyp_off[p] .. pair_hyp_off[p+1]), ascending.  Most inliers, then the
+ *   smaller dists_sum, then the lower id, among those with >= n_min_inliers -> best_hyp (n_pairs), -1 for none; with skip_hypothesis_0
+ *   hypothesis 0 is never reported (the reference tests `hypothesis_id > 0`).  The winner's walk is repeated and its matches written to
+ *   match_cand1/2[pair_off[p] ...], their number to n_matches (n_pairs).
+ * Fixed summation orders, no atomics: equal inputs give equal bits. */
+int cosy_ransac_max_tmatches(void);
+int cosy_ransac_hypotheses(const float* cand_poses, const int* cand_mesh, const float* pts_table, const float* sym_table, const int* n_sym,
+                           int n_cand, int n_mesh, int P, int S, const int* seeds, int H, float* TC1C2, int* best_sym, float* gap,
+                           float* sym_dists, cosy_stream_t stream);
+int cosy_ransac_score(const float* cand_poses, const int* cand_mesh, const float* pts_table, const float* sym_table, int n_cand, int n_mesh,
+                      int P, int S, const float* TC1C2, const int* hyp_pair, int H, const int* pair_off, const int* tmatches, int n_pairs,
+                      int max_tm, float dist_threshold, const long long* hyp_dist_off, const float* dists_in, float* dists_out,
+                      int* n_inliers, float* dists_sum, cosy_stream_t stream);
+int cosy_ransac_best(const float* cand_poses, const int* cand_mesh, const float* pts_table, const float* sym_table, int n_cand, int n_mesh,
+                     int P, int S, const float* TC1C2, int H, const int* n_inliers, const float* dists_sum, const int* pair_hyp_off,
+                     const int* pair_hyps, const int* pair_off, const int* tmatches, int n_pairs, int max_tm, float dist_threshold,
+                     int n_min_inliers, int skip_hypothesis_0, const long long* hyp_dist_off, const float* dists_in, int* best_hyp,
+                     int* n_matches, int* match_cand1, int* match_cand2, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
