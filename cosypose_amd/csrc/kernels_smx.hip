@@ -38,7 +38,7 @@ template <int CTRL> __device__ __forceinline__ float smx_dppf(float v) { return 
 
 struct SmxKArgs {
     const void* X; const void* Wp; const char* params; void* D; float* partial; const void* zeros;
-    int Cin, Cmid, nkb_total, ncg, cpw, dbg;
+    int B, Cin, Cmid, nkb_total, ncg, dbg;      // ncg: chunk groups (workgroups per sample / pair of samples)
     // the map as the kernel walks it: NSEG segments of two 8-pixel walk rows; walk pixel (r, c) = map pixel r * Wm + c, or c * Wm + r for a transposed walk (7x10 maps:
     // the 10 columns are the walk rows); cv = valid pixels of a walk row (8, or 7: the eighth is expanded from a clamped address, zeroed as a tap operand, left out of
     // the squeeze sums and not stored); HW = pixels of the map
@@ -46,31 +46,46 @@ struct SmxKArgs {
 };
 enum { SMX_HDR = 1024 };       // bytes of a chunk's parameter header [b0 * log2 e 48][s1 48][b1 48] fp32 (padded to one DMA instruction)
 constexpr int smx_pbytes(int ks) { return SMX_HDR + 3 * ks * 2 * 512; }   // + [tile 3][ky][operand 2][lane 64] 8-byte Toeplitz fragments
+// dynamic LDS of a workgroup: per sample the E operands [NSEG + 2][3][64] x 8 bytes and the squeeze partials [NSEG][48]; once the weight ring and two parameter buffers
+constexpr size_t smx_lds_bytes(int ks, int kbn, int hl, int nseg, int spw) {
+    return (size_t)spw * (nseg + 2) * 3 * 512 + (size_t)3 * kbn * hl * 1024 + (size_t)2 * smx_pbytes(ks) + (size_t)spw * nseg * 48 * sizeof(float);
+}
 
 // NSEG = 4: the 8x8 maps, wave w = segment w, three work units per wave and chunk (its segment x the chunk's three 16-channel tiles).
 // NSEG = 5 (round 6: the 7x10 / 10x7 maps of 240x320 / 320x240 crops): still FOUR waves -- a fifth wave would share a SIMD with another wave of its workgroup and
 // double that SIMD's share of every barrier-separated phase (measured: 95 us per block against 56 us on the 8x8 maps) -- wave w < 3 also owns the unit (segment 4, tile w):
 // 4 + 4 + 4 + 3 units.  Unit u < 3 = (segment wave, tile u); unit 3 = (segment 4, tile wave).
-template <typename T, int KS, int KBN, int NSEG>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) void mbconv_small_mx_kernel(SmxKArgs a) {
+// SPW = samples per workgroup.  1: the organisation above.  2 (8x8 maps): 8 waves = 2 consecutive samples x 4 segments; wave w serves sample w >> 2, segment w & 3.
+// The weight ring Wl and the parameter / Toeplitz double buffer Pl -- the same for every sample, and most of the LDS -- are shared and filled once per chunk by all
+// 8 waves; each sample has its own Eh and red.  ~75 KB of LDS still lets two workgroups share a CU: 16 waves per CU, 4 per SIMD, which needs <= 128 VGPRs.  A sample's
+// values do not depend on SPW, its partner or its place in the batch: the same MFMA chains, sums and converts in the same order.  The last pair of an odd batch has
+// one sample: the missing sample's waves take part in every barrier, DMA issue and lane permutation, read the last sample's (valid) addresses and store nothing.
+template <typename T, int KS, int KBN, int NSEG, int SPW>
+__global__ __launch_bounds__(256 * SPW) __attribute__((amdgpu_waves_per_eu(SPW == 2 ? 4 : 2, SPW == 2 ? 4 : 3))) void mbconv_small_mx_kernel(SmxKArgs a) {
+    static_assert(SPW == 1 || (SPW == 2 && NSEG == 4), "two samples per workgroup: the 8x8 maps only");
     using raw_t = typename DT<T>::raw_t;
     constexpr int EPL = DT<T>::EPL, KB = DT<T>::KB;
     constexpr int NI = 3, CC = 48, LO = (KS - 1) / 2, PBYTES = smx_pbytes(KS), PJ = PBYTES / 1024;
     constexpr int HL = __is_same(T, bf16_t) ? 2 : 1, NF = KBN * HL;      // weight fragments per 16-channel tile: [k-block][hi | lo]
     constexpr int NU = NSEG == 5 ? 4 : 3;                                // work units per wave (the fourth: waves 0-2 only)
+    constexpr int EHB = (NSEG + 2) * NI * 512, NWV = 4 * SPW;            // bytes of one sample's E operands; waves of the workgroup
     typedef T t4 __attribute__((ext_vector_type(4)));
     typedef f16_t tt4 __attribute__((ext_vector_type(4)));          // operands of the tap MFMAs: fp16 in both 16-bit modes (a register / LDS format between two MFMAs, not storage)
     typedef T out_t __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Eh = smem;                               // [NSEG + 2 segments][NI][64 lanes] 8 bytes
-    char* Wl = Eh + (NSEG + 2) * NI * 512;
-    char* Pl = Wl + NI * NF * 1024;
-    float* red = (float*)(Pl + 2 * PBYTES);        // [NSEG segments][48]
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x / a.ncg, cg = blockIdx.x - b * a.ncg;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = SPW == 1 ? wv : (wv & 3), sp = SPW == 1 ? 0 : (wv >> 2);      // segment wave, sample of the workgroup
+    char* Eh = smem + (size_t)sp * EHB;            // per sample: [NSEG + 2 segments][NI][64 lanes] 8 bytes
+    char* Wl = smem + SPW * EHB;                   // shared by the workgroup's samples
+    char* Pl = Wl + NI * NF * 1024;                // (shared)
+    float* red = (float*)(Pl + 2 * PBYTES) + sp * NSEG * CC;        // per sample: [NSEG segments][48]
+    const int grp = blockIdx.x / a.ncg, cg = blockIdx.x - grp * a.ncg;
+    const int bs = grp * SPW + sp;                 // this wave's sample
+    const bool valid = SPW == 1 || bs < a.B;       // (wave-uniform) false: the missing partner of an odd batch's last sample
+    const int b = SPW == 1 ? bs : min(bs, a.B - 1);
     const int nchunks = a.Cmid / CC;
-    const int ch0 = cg * a.cpw, ch1 = min(nchunks, ch0 + a.cpw);
+    const int ch0 = cg * nchunks / a.ncg, ch1 = (cg + 1) * nchunks / a.ncg;      // this workgroup's run of chunks (even split)
     const int prow = lane & 15, kg = lane >> 4;
     const int cb = lane >> 2, jq = lane & 3;       // small-MFMA roles: channel of the tile, quad (row jq >> 1 of the segment, half jq & 1)
     const bool has4 = NSEG == 5 && wave < 3;       // this wave owns (segment 4, tile wave) as well
@@ -78,13 +93,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     auto utile = [&](int u) -> int { return u < 3 ? u : wave; };
 
     auto issue_w = [&](int ch) {
-        for (int blk = wave; blk < NI * NF; blk += 4) {
+        for (int blk = wv; blk < NI * NF; blk += NWV) {
             const int ni = blk / NF, f = blk - ni * NF;
             const T* src = (const T*)a.Wp + (((size_t)(ch * NI + ni) * a.nkb_total + f / HL) * HL + f % HL) * 64 * EPL + lane * EPL;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(Wl + (size_t)blk * 1024), 16, 0, 0);
         }
-        for (int j = wave; j < PJ; j += 4) {
+        for (int j = wv; j < PJ; j += NWV) {
             const char* src = a.params + (size_t)ch * PBYTES + (size_t)j * 1024 + lane * 16;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(Pl + (size_t)(ch & 1) * PBYTES + (size_t)j * 1024), 16, 0, 0);
@@ -104,7 +119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
             xf[q][kb] = *(const raw_t*)(k < a.Cin ? (const void*)(X + k) : a.zeros);
         }
     }
-    for (int i = tid; i < (NSEG + 2) * NI * 512 / 16; i += 256) *(f32x4*)(Eh + (size_t)i * 16) = f32x4{0.f, 0.f, 0.f, 0.f};   // segments -1 and NSEG are never written
+    for (int i = tid; i < SPW * EHB / 16; i += 256 * SPW) *(f32x4*)(smem + (size_t)i * 16) = f32x4{0.f, 0.f, 0.f, 0.f};   // segments -1 and NSEG are never written
     const int bp_in = (cb + 16 * jq) * 4, bp_out = (4 * prow + kg) * 4;
     t4 ident;
 #pragma unroll
@@ -163,16 +178,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
             for (int u = 0; u < NU; ++u)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) Sw[u][q] = smx_i32x2{smx_dpp<0x4E>(S[u][q][0]), smx_dpp<0x4E>(S[u][q][1])};             // rows of the segment swapped (quad_perm [2,3,0,1])
-            // every LDS read of the phase is issued up front (the Toeplitz fragments: 2 KS x 3 register pairs): a read's round trip is several hundred
-            // cycles while the next chunk's DMA is writing into the LDS, and 2 waves per SIMD do not hide one per tap row
-            tt4 A0[KS][NI], A1[KS][NI];
+            // SPW = 1: every LDS read of the phase is issued up front (the Toeplitz fragments: 2 KS x 3 register pairs): a read's round trip is several hundred
+            // cycles while the next chunk's DMA is writing into the LDS, and 2 waves per SIMD do not hide one per tap row.
+            // SPW = 2: four waves per SIMD hide it, and 2 KS x 3 pairs up front (60 VGPRs at k = 5) do not fit the 128 registers four waves leave each:
+            // the fragments are read tap row by tap row
+            constexpr bool UPFRONT = SPW == 1;
+            auto toep = [&](int ky, int ni, int m) -> tt4 { return *(const tt4*)(P + SMX_HDR + (size_t)((ni * KS + ky) * 2 + m) * 512 + lane * 8); };
+            tt4 A0[UPFRONT ? KS : 1][NI], A1[UPFRONT ? KS : 1][NI];
+            if constexpr (UPFRONT) {
 #pragma unroll
-            for (int ky = 0; ky < KS; ++ky)
+                for (int ky = 0; ky < KS; ++ky)
 #pragma unroll
-                for (int ni = 0; ni < NI; ++ni) {
-                    A0[ky][ni] = *(const tt4*)(P + SMX_HDR + (size_t)((ni * KS + ky) * 2 + 0) * 512 + lane * 8);
-                    A1[ky][ni] = *(const tt4*)(P + SMX_HDR + (size_t)((ni * KS + ky) * 2 + 1) * 512 + lane * 8);
-                }
+                    for (int ni = 0; ni < NI; ++ni) { A0[ky][ni] = toep(ky, ni, 0); A1[ky][ni] = toep(ky, ni, 1); }
+            }
             // unit 3's tile is this wave's index: its fragments selected once (wave-uniform)
             tt4 A0x[NU == 4 ? KS : 1], A1x[NU == 4 ? KS : 1];
             if constexpr (NU == 4) {
@@ -193,6 +211,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
             for (int ky = 0; ky < KS; ++ky) {                              // tap row outer: the units' accumulation chains advance together
                 const int d = ky - LO;                                      // input row = output row + d
                 smx_i32x2 op[NU], w2[NU];
+                tt4 a0r[NI], a1r[NI];                                       // this tap row's fragments
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni) {
+                    if constexpr (UPFRONT) { a0r[ni] = A0[ky][ni]; a1r[ni] = A1[ky][ni]; }
+                    else { a0r[ni] = toep(ky, ni, 0); a1r[ni] = toep(ky, ni, 1); }
+                }
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     if (d == -2) op[u] = S[u][0];
@@ -207,11 +231,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
                 }
 #pragma unroll
                 for (int u = 0; u < NU; ++u)
-                    if (u < 3) accx[u] = smx_mma4(A0[ky][u < 3 ? u : 0], __builtin_bit_cast(tt4, op[u]), accx[u]);
+                    if (u < 3) accx[u] = smx_mma4(a0r[u < 3 ? u : 0], __builtin_bit_cast(tt4, op[u]), accx[u]);
                     else if (has4) accx[u] = smx_mma4(A0x[NU == 4 ? ky : 0], __builtin_bit_cast(tt4, op[u]), accx[u]);
 #pragma unroll
                 for (int u = 0; u < NU; ++u)
-                    if (u < 3) accx[u] = smx_mma4(A1[ky][u < 3 ? u : 0], __builtin_bit_cast(tt4, w2[u]), accx[u]);
+                    if (u < 3) accx[u] = smx_mma4(a1r[u < 3 ? u : 0], __builtin_bit_cast(tt4, w2[u]), accx[u]);
                     else if (has4) accx[u] = smx_mma4(A1x[NU == 4 ? ky : 0], __builtin_bit_cast(tt4, w2[u]), accx[u]);
             }
             smx_i32x2 hh[NU];
@@ -242,17 +266,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
         }
         // Global stores count in vmcnt and retire in order with the loads: the wait for the next chunk's DMA comes BEFORE this chunk's stores
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!COSY_DBG(a.dbg & 1) && (prow & 7) < a.cv) {
+        if (!COSY_DBG(a.dbg & 1) && (prow & 7) < a.cv && valid) {
 #pragma unroll
             for (int u = 0; u < NU; ++u)
                 if (u < 3 || has4)
-                    *(out_t*)((T*)a.D + (((size_t)b * (a.Cmid >> 4) + ch * NI + utile(u)) * a.HW + walk_pix(useg(u), prow & 7)) * 16 + kg * 4) = yv[u];
+                    *(out_t*)((T*)a.D + (((size_t)bs * (a.Cmid >> 4) + ch * NI + utile(u)) * a.HW + walk_pix(useg(u), prow & 7)) * 16 + kg * 4) = yv[u];
         }
         __syncthreads();   // red complete; everybody's DMA(ch+1) landed; all Eh / parameter reads of this chunk are done
-        if (tid < CC && !COSY_DBG(a.dbg & 1)) {
-            float sm = ((red[tid] + red[CC + tid]) + red[2 * CC + tid]) + red[3 * CC + tid];
-            if constexpr (NSEG == 5) sm += red[4 * CC + tid];
-            a.partial[(size_t)b * a.Cmid + ch * CC + tid] = sm;
+        const int lt = SPW == 1 ? tid : (tid & 255);      // thread of the sample's four waves
+        if (lt < CC && valid && !COSY_DBG(a.dbg & 1)) {
+            float sm = ((red[lt] + red[CC + lt]) + red[2 * CC + lt]) + red[3 * CC + lt];
+            if constexpr (NSEG == 5) sm += red[4 * CC + lt];
+            a.partial[(size_t)bs * a.Cmid + ch * CC + lt] = sm;
         }
     }
 }
@@ -296,40 +321,59 @@ void small_mx_pack_params(const float* b0l2e, const float* dww, const float* s1,
                         }
     }
 }
-void small_mx_kernel_name(int Cin, int k, int dtype, char* buf, size_t n) {
-    snprintf(buf, n, "mbconv_small_mx_kernel<%s, %d, %d>", dtype == COSY_BF16 ? "__bf16" : "_Float16", k, cdiv(Cin, 32));
+// Samples per workgroup of the instantiation a launch runs: a property of the shape, never of the batch.  2 on the 8x8 maps in fp16 (the bf16 form's doubled weight
+// ring would not leave two such workgroups a CU; k = 5 with 12 k-blocks -- no block of the network -- does not fit 128 registers)
+static int smx_spw(int k, int kbn, int dtype, int HW) {
+    if (HW != 64 || dtype == COSY_BF16 || (k == 5 && kbn == 12)) return 1;
+    return tune_int("COSY_SMALL_SPW", 2) == 1 ? 1 : 2;      // (read per launch: the tune build alternates the two forms inside one process)
+}
+// as rocprofv3 prints it: <T, KS, KBN, NSEG, SPW>
+void small_mx_kernel_name(int Cin, int k, int dtype, int H, int W, char* buf, size_t n) {
+    const int kbn = cdiv(Cin, 32);
+    snprintf(buf, n, "mbconv_small_mx_kernel<%s, %d, %d, %d, %d>", dtype == COSY_BF16 ? "__bf16" : "_Float16", k, kbn, H * W == 64 ? 4 : 5, smx_spw(k, kbn, dtype, H * W));
 }
 
-template <typename T, int KS, int KBN, int NSEG>
-static int launch_smx_ks(const SmxKArgs& k, int B, hipStream_t s) {
+template <typename T, int KS, int KBN, int NSEG, int SPW>
+static int launch_smx_ks(SmxKArgs k, hipStream_t s) {
     constexpr int HL = __is_same(T, bf16_t) ? 2 : 1;      // bf16: hi + lo weight fragments
-    const size_t lds = (size_t)(NSEG + 2) * 3 * 512 + (size_t)3 * KBN * HL * 1024 + (size_t)2 * smx_pbytes(KS) + NSEG * 48 * sizeof(float);
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)mbconv_small_mx_kernel<T, KS, KBN, NSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // chunk groups: a launch lasts as long as a workgroup's chain of chunks while the workgroups fit the machine at once (two per CU: 512).  SPW = 1: groups of
+    // <= 15 chunks whatever the batch.  SPW = 2: as many groups as bring the launch to COSY_SMALL_WGS workgroups -- 4 groups of 7-8 (block 25: 12) chunks for a
+    // 256-crop launch, 8 of 3-4 (6) for the 128-crop launches of the two-stream schedule, a chunk per workgroup for a handful of samples.  D and the squeeze
+    // sums are per chunk: the result does not depend on the grouping
+    const int nchunks = k.Cmid / 48;
+    const int cpw_knob = tune_int("COSY_SMALL_CPW", 0), wgs = tune_int("COSY_SMALL_WGS", 512);
+    if (cpw_knob > 0) k.ncg = cdiv(nchunks, std::min(cpw_knob, nchunks));
+    else if (SPW == 1) k.ncg = cdiv(nchunks, 15);
+    else k.ncg = std::min(nchunks, std::max(1, cdiv(wgs, cdiv(k.B, SPW))));
+    constexpr size_t lds = smx_lds_bytes(KS, KBN, HL, NSEG, SPW);
+    static_assert(SPW == 1 || lds <= 80 * 1024, "two samples per workgroup pay only while two workgroups (16 waves) share a CU's 160 KB of LDS");
+    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)mbconv_small_mx_kernel<T, KS, KBN, NSEG, SPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     COSY_CHECK_HIP(attr_rc);
-    hipLaunchKernelGGL((mbconv_small_mx_kernel<T, KS, KBN, NSEG>), dim3((unsigned)(B * k.ncg)), dim3(256), lds, s, k);
+    hipLaunchKernelGGL((mbconv_small_mx_kernel<T, KS, KBN, NSEG, SPW>), dim3((unsigned)(cdiv(k.B, SPW) * k.ncg)), dim3(256 * SPW), lds, s, k);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }
 template <typename T, int KS, int KBN>
-static int launch_smx_k(const SmxKArgs& k, int B, hipStream_t s) {
-    return k.HW == 64 ? launch_smx_ks<T, KS, KBN, 4>(k, B, s) : launch_smx_ks<T, KS, KBN, 5>(k, B, s);
+static int launch_smx_k(const SmxKArgs& k, int dtype, hipStream_t s) {
+    if (k.HW != 64) return launch_smx_ks<T, KS, KBN, 5, 1>(k, s);
+    if constexpr (__is_same(T, f16_t) && !(KS == 5 && KBN == 12)) {
+        if (smx_spw(KS, KBN, dtype, 64) == 2) return launch_smx_ks<T, KS, KBN, 4, 2>(k, s);
+    }
+    return launch_smx_ks<T, KS, KBN, 4, 1>(k, s);
 }
 template <typename T>
-static int launch_smx_t(const FuseArgs& a, hipStream_t s) {
+static int launch_smx_t(const FuseArgs& a, int dtype, hipStream_t s) {
     SmxKArgs k;
     k.X = a.X; k.Wp = a.Wp; k.params = (const char*)a.wparams; k.D = a.D; k.partial = a.partial; k.zeros = a.zeros;
-    k.Cin = a.Cin; k.Cmid = a.Cmid; k.nkb_total = (cdiv(a.Cin, 32) + 1) & ~1;
+    k.B = a.B; k.Cin = a.Cin; k.Cmid = a.Cmid; k.nkb_total = (cdiv(a.Cin, 32) + 1) & ~1;
     k.HW = a.H * a.W; k.Wm = a.W; k.tr = small_mx_transposed(a.H, a.W); k.cv = a.H * a.W == 64 ? 8 : 7;
-    const int nchunks = a.Cmid / 48;
-    static const int cpw_target = tune_int("COSY_SMALL_CPW", 15);
-    k.cpw = nchunks <= cpw_target ? nchunks : cdiv(nchunks, cdiv(nchunks, cpw_target));
-    k.ncg = cdiv(nchunks, k.cpw);
+    k.ncg = 0;      // (launch_smx_ks)
     k.dbg = tune_int("COSY_SMALL_DBG", 0);
     const int kbn = cdiv(a.Cin, 32);
-    if (a.k == 3 && kbn == 8) return launch_smx_k<T, 3, 8>(k, a.B, s);
-    if (a.k == 3 && kbn == 12) return launch_smx_k<T, 3, 12>(k, a.B, s);
-    if (a.k == 5 && kbn == 8) return launch_smx_k<T, 5, 8>(k, a.B, s);
-    if (a.k == 5 && kbn == 12) return launch_smx_k<T, 5, 12>(k, a.B, s);
+    if (a.k == 3 && kbn == 8) return launch_smx_k<T, 3, 8>(k, dtype, s);
+    if (a.k == 3 && kbn == 12) return launch_smx_k<T, 3, 12>(k, dtype, s);
+    if (a.k == 5 && kbn == 8) return launch_smx_k<T, 5, 8>(k, dtype, s);
+    if (a.k == 5 && kbn == 12) return launch_smx_k<T, 5, 12>(k, dtype, s);
     set_error("mbconv_small_mx: unsupported k=%d k-blocks=%d", a.k, kbn);
     return COSY_EINVAL;
 }
@@ -338,7 +382,7 @@ int launch_mbconv_small_mx(const FuseArgs& a, int dtype, hipStream_t s) {
     if (a.B == 0) return COSY_OK;
     COSY_REQUIRE(small_mx_supported(a.Cin, a.Cmid, a.k, a.s, dtype, a.H, a.W), "mbconv_small_mx: unsupported shape Cin=%d Cmid=%d %dx%d k=%d s=%d", a.Cin, a.Cmid, a.H, a.W, a.k, a.s);
     COSY_REQUIRE(a.wparams != nullptr, "mbconv_small_mx: packed parameters missing (small_mx_pack_params)%s", "");
-    return dtype == COSY_BF16 ? launch_smx_t<bf16_t>(a, s) : launch_smx_t<f16_t>(a, s);
+    return dtype == COSY_BF16 ? launch_smx_t<bf16_t>(a, dtype, s) : launch_smx_t<f16_t>(a, dtype, s);
 }
 
 }  // namespace cosy
