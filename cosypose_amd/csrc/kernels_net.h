@@ -2,9 +2,22 @@
 #pragma once
 #include "cosy_common.h"
 
+#include <string.h>
+
 namespace cosy {
 
 struct SeArgs;
+
+const char* dt_name(int dtype);      // the storage type as it appears in a kernel's template arguments (profiler names)
+
+// host-side float -> fp16 / bf16 bits of the weight packers: fp16 saturates at +-65504, bf16 rounds to nearest even
+static inline uint16_t f32_to_f16_host(float f) { _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f)); uint16_t u; memcpy(&u, &h, 2); return u; }
+static inline uint16_t f32_to_bf16_host(float f) {
+    uint32_t u; memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
 
 // tile configuration of the pointwise-conv GEMM: WV waves as (WV/WN) x WN, each 64 rows x 16*NI columns:
 // BN = 16*NI*WN, BM = 64*(WV/WN)
@@ -158,10 +171,11 @@ int launch_stem(const void* x_nhwc8, const void* w_packed, const float* scale, c
                 int B, int H, int W, int Ho, int Wo, int dtype, hipStream_t s);
 int launch_pool_fc(const void* head /*(B,HW,1536)*/, const float* fc_w /*(9,1536)*/, const float* fc_b, float* feat_or_null,
                    float* feat_scratch, float* pose, int B, int HW, int dtype, hipStream_t s);
-// colH > 0: the activation's pixels are stored column-major (x * colH + y, colH = the map's height); the probes index them row-major
-int launch_nhwc_to_nchw(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* out, hipStream_t s, int chunked = 0, int colH = 0, int perm_lw = 0, int perm_lp = 0);
-int launch_taps(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* taps /*(B,9,16)*/, int tap_index,
-                hipStream_t s, int colH = 0, int chunked = 0, int perm_lw = 0, int perm_lp = 0);   // chunked: [sample][ceil(C/16)][HW][16] (+ PwArgs::out_perm_*)
+// How an activation (B, HW, C) is stored.  chunked: [sample][ceil(C/16)][HW][16] instead of NHWC rows; colH > 0: the pixels of a sample are column-major
+// (x * colH + y, colH = the map's height; the probes index them row-major); perm_lw / perm_lp: the row permutation of PwArgs::out_perm_* (chunked only)
+struct ActLayout { int chunked = 0, colH = 0, perm_lw = 0, perm_lp = 0; };
+int launch_nhwc_to_nchw(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* out, hipStream_t s, const ActLayout& l);
+int launch_taps(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* taps /*(B,9,16)*/, int tap_index, hipStream_t s, const ActLayout& l);
 // out (B, H*W, C) row-major pixels <- in (B, W*H, C) column-major pixels: the exit of a resolution stage that is stored transposed
 int launch_pixels_to_rowmajor(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s);
 

@@ -83,17 +83,10 @@ bool pw_gate_on_weights(int HW, int dtype) { return HW % 64 == 0 && dtype != COS
 // multiplies the same activation fragment with both (fp32 accumulation), so what meets the activations is hi + lo = w to 16 significant bits.  bf16's 8-bit
 // weights were what kept the type BASELINE configs[1] names outside north_star's 1e-4 pose bound (1.7e-4; with the pairs 3e-5, below fp16's: profiles/r06_bf16.txt).
 int pw_hl(int dtype) { return dtype == COSY_BF16 ? 2 : 1; }
-static inline uint16_t f32_to_f16_host(float f) { _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f)); uint16_t u; memcpy(&u, &h, 2); return u; }
 static int pw_nkb_total(int K, int dtype) { int n = cdiv(K, pw_kb(dtype)); return (n + 1) & ~1; }
 size_t pw_packed_elems(int K, int N, PwCfg c, int dtype, int hl) {      // hl: fragment blocks per k-block; < 0 = the type's own (pw_hl), 1 = single values (the stem kernels)
     const int epl = dtype == COSY_F32 ? 4 : 8;
     return (size_t)cdiv(N, pw_bn(c)) * c.NI * c.WN * pw_nkb_total(K, dtype) * (hl < 0 ? pw_hl(dtype) : hl) * 64 * epl;
-}
-static inline uint16_t f32_to_bf16_host(float f) {
-    uint32_t u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
 }
 static inline float bf16_bits_to_f32(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
 void pw_pack_weights(const float* w, int K, int N, PwCfg c, int dtype, void* dst, int hl_) {
@@ -703,18 +696,18 @@ static int launch_pw_t(const PwArgs& a, PwCfg c, int dtype, hipStream_t s) {
     return a.gate ? launch_pw_dma<T, true>(k, c, grid, s) : launch_pw_dma<T, false>(k, c, grid, s);
 }
 
-static const char* tname(int dtype) { return dtype == COSY_F32 ? "float" : dtype == COSY_BF16 ? "__bf16" : "_Float16"; }
+const char* dt_name(int dtype) { return dtype == COSY_F32 ? "float" : dtype == COSY_BF16 ? "__bf16" : "_Float16"; }
 // the kernel symbol (as rocprofv3 demangles it) that launch_pw_gemm will run for these arguments
 void pw_kernel_name(const PwArgs& a, PwCfg c, int dtype, char* buf, size_t n) {
     const int nkb = cdiv(a.K, pw_kb(dtype));
     const int mi = pw_mi_for(a.gate != nullptr, a.HW, nkb, a.N, dtype == COSY_F32 ? 4 : 2);
-    if (c.WV == 16) snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, %d, %s, 4, 16, %d>", tname(dtype), c.NI, c.WN, dtype == COSY_BF16 ? 2 : 3, a.gate ? "true" : "false", c.KG);
-    else if (c.WV == 8) snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, 3, %s, 4, 8>", tname(dtype), c.NI, c.WN, a.gate ? "true" : "false");
-    else snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, %d, %s, %d>", tname(dtype), c.NI, c.WN, pw_ring_stages(a.K, c, dtype), a.gate ? "true" : "false", mi);
+    if (c.WV == 16) snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, %d, %s, 4, 16, %d>", dt_name(dtype), c.NI, c.WN, dtype == COSY_BF16 ? 2 : 3, a.gate ? "true" : "false", c.KG);
+    else if (c.WV == 8) snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, 3, %s, 4, 8>", dt_name(dtype), c.NI, c.WN, a.gate ? "true" : "false");
+    else snprintf(buf, n, "pw_gemm_dma_kernel<%s, %d, %d, %d, %s, %d>", dt_name(dtype), c.NI, c.WN, pw_ring_stages(a.K, c, dtype), a.gate ? "true" : "false", mi);
 }
 void small_kernel_name(int Cin, int k, int s, int dtype, int H, int W, char* buf, size_t n) {
     const int mbr = cdiv(H * W, 16), mpw = cdiv(mbr, (mbr <= 4 ? 256 : 512) / 64);
-    snprintf(buf, n, "mbconv_small_kernel<%s, %d, %d, %d, %d, %d>", tname(dtype), k, s, s == 1 ? (H == 7 && W == 10 ? 5 : 4) : 2, cdiv(Cin, 32), mpw);
+    snprintf(buf, n, "mbconv_small_kernel<%s, %d, %d, %d, %d, %d>", dt_name(dtype), k, s, s == 1 ? (H == 7 && W == 10 ? 5 : 4) : 2, cdiv(Cin, 32), mpw);
 }
 
 int launch_pw_gemm(const PwArgs& a, PwCfg cfg, int dtype, hipStream_t s) {

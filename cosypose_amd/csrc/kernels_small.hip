@@ -255,10 +255,10 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* __restrict__
     const size_t src = chunked ? ((size_t)b * ((C + 15) >> 4) + (c >> 4)) * HW * 16 + perm_pixel(p, lw, lp) * 16 + (c & 15) : ((size_t)b * HW + p) * C + c;
     out[(size_t)b * HW * C + i] = (float)act[src];
 }
-int launch_nhwc_to_nchw(const void* act, int B, int HW, int C, int dtype, float* out, hipStream_t s, int chunked, int colH, int perm_lw, int perm_lp) {
+int launch_nhwc_to_nchw(const void* act, int B, int HW, int C, int dtype, float* out, hipStream_t s, const ActLayout& l) {
     if (B == 0) return COSY_OK;
     dim3 grid(cdiv((long)HW * C, 256), B);
-    COSY_DISPATCH_STMT(dtype, hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, s, (const T*)act, HW, C, out, chunked, colH, perm_lw, perm_lp));
+    COSY_DISPATCH_STMT(dtype, hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, s, (const T*)act, HW, C, out, l.chunked, l.colH, l.perm_lw, l.perm_lp));
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }
@@ -292,9 +292,9 @@ __global__ __launch_bounds__(256) void taps_kernel(const T* __restrict__ act, in
         t[2 + tid] = at(p, c);
     }
 }
-int launch_taps(const void* act, int B, int HW, int C, int dtype, float* taps, int tap_index, hipStream_t s, int colH, int chunked, int perm_lw, int perm_lp) {
+int launch_taps(const void* act, int B, int HW, int C, int dtype, float* taps, int tap_index, hipStream_t s, const ActLayout& l) {
     if (B == 0) return COSY_OK;
-    COSY_DISPATCH_STMT(dtype, hipLaunchKernelGGL(taps_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)act, HW, C, taps, tap_index, colH, chunked, perm_lw, perm_lp));
+    COSY_DISPATCH_STMT(dtype, hipLaunchKernelGGL(taps_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)act, HW, C, taps, tap_index, l.colH, l.chunked, l.perm_lw, l.perm_lp));
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }

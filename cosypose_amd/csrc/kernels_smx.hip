@@ -285,12 +285,6 @@ __global__ __launch_bounds__(256 * SPW) __attribute__((amdgpu_waves_per_eu(SPW =
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static inline uint16_t smx_f16_bits(float f) { _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f)); return __builtin_bit_cast(uint16_t, h); }
-static inline uint16_t smx_bf16_bits(float f) {
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 bool small_mx_transposed(int H, int W) { return H == 7 && W == 10; }      // the map's columns are the walk rows
 static int smx_enabled() { static const int v = tune_int("COSY_SMALL_MX", 1); return v; }
 bool small_mx_supported(int Cin, int Cmid, int k, int s, int dtype, int H, int W) {
@@ -317,7 +311,7 @@ void small_mx_pack_params(const float* b0l2e, const float* dww, const float* s1,
                         for (int q = 0; q < 4; ++q) {
                             const int i = lane & 3, cc = ch * 48 + ni * 16 + (lane >> 2), kx = off[m][q] - i + lo;
                             const float w = (kx >= 0 && kx < k) ? dww[(size_t)(transposed ? kx * k + ky : ky * k + kx) * Cmid + cc] : 0.f;      // transposed walk: tap row = the map's kx
-                            fr[((((size_t)ni * k + ky) * 2 + m) * 64 + lane) * 4 + q] = smx_f16_bits(w);      // fp16 in both 16-bit modes (the tap MFMAs' operand type)
+                            fr[((((size_t)ni * k + ky) * 2 + m) * 64 + lane) * 4 + q] = f32_to_f16_host(w);      // fp16 in both 16-bit modes (the tap MFMAs' operand type)
                         }
     }
 }

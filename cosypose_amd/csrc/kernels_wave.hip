@@ -1113,12 +1113,6 @@ static WavePlan wave_plan(int Cin, int Cmid, int H, int W, int k, int s, int dty
 // Taps on the matrix pipe (WavePlan::mx): [chunk][s0 16][b0 16][s1 16][b1 16] fp32 (no log2 e: the expanded values are rounded to the storage
 // type as they are), then 2 k fragments [ky][operand 0 | 1][lane 64][4] of the storage type: the Toeplitz rows of tap row ky for the lane's
 // output pixel i = lane & 3 and channel lane >> 2 -- operand 0 against the pixels 4j .. 4j+3 of the lane quad, operand 1 against 4j-2, 4j-1, 4j+4, 4j+5.
-static inline uint16_t wave_f16_bits(float f) { _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f)); return __builtin_bit_cast(uint16_t, h); }
-static inline uint16_t wave_bf16_bits(float f) {       // round to nearest even (finite weights)
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 static size_t wave_chunk_floats(const WavePlan& p, int k) { return p.mx ? (size_t)64 + 2 * k * 128 : (size_t)(4 + k * k) * 16; }
 size_t wave_params_floats(int Cin, int Cmid, int k, int s, int dtype, int H, int W) {
     return (size_t)(Cmid / 16) * wave_chunk_floats(wave_plan(Cin, Cmid, H, W, k, s, dtype), k);
@@ -1142,7 +1136,7 @@ void wave_pack_params(const float* s0, const float* b0, const float* dww, const 
                             const int i = lane & 3, cc = ch * 16 + (lane >> 2), kx = off[m][q] - i + lo;
                             float w = 0.f;
                             if (kx >= 0 && kx < k) w = dww[(size_t)(p.transposed ? kx * k + ky : ky * k + kx) * Cmid + cc];
-                            a[(((size_t)ky * 2 + m) * 64 + lane) * 4 + q] = wave_f16_bits(w);      // fp16 in both 16-bit modes (the tap MFMAs' operand type)
+                            a[(((size_t)ky * 2 + m) * 64 + lane) * 4 + q] = f32_to_f16_host(w);      // fp16 in both 16-bit modes (the tap MFMAs' operand type)
                         }
         }
         return;
