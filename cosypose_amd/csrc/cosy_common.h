@@ -26,6 +26,11 @@ void set_error(const char* fmt, ...);
         }                                       \
     } while (0)
 
+// a required pointer argument: the message names it ("crop_geometry: null TCO")
+#define COSY_REQUIRE_PTR(fn, p) COSY_REQUIRE((p) != nullptr, fn ": null " #p)
+// blockIdx.y carries the batch in a few kernels: the hardware limit of gridDim.y
+constexpr int COSY_MAX_GRID_Y = 65535;
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Tuning / phase knock-out knobs exist only in the -DCOSY_TUNE build (lib/libcosyhip_tune.so: experiments, timing only --

@@ -757,12 +757,21 @@ int cosy_effnet_b3_set_input_nchw(cosy_net_t* n, const float* x, int B, cosy_str
     return launch_pack_nchw(n->X, n->dtype, x, B, n->H, n->W, (hipStream_t)stream);
 }
 
+// (N,3,h,w) -> (N,h,w,4): N rides in gridDim.y
+static int frames_args(const char* fn, const void* images, const void* out, int N, int h, int w) {
+    COSY_REQUIRE(N >= 0 && N <= COSY_MAX_GRID_Y, "%s: N=%d outside [0, %d]", fn, N, COSY_MAX_GRID_Y);
+    if (N == 0) return COSY_OK;
+    COSY_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= 0x7fffffffL / 3, "%s: bad frame size h=%d w=%d", fn, h, w);
+    COSY_REQUIRE(images, "%s: null images", fn);
+    COSY_REQUIRE(out, "%s: null out", fn);
+    return COSY_OK;
+}
 int cosy_frames_u8_to_nhwc4(const unsigned char* images, float* out, int N, int h, int w, cosy_stream_t stream) {
-    COSY_REQUIRE(images && out, "frames_u8_to_nhwc4: null argument");
+    if (int rc = frames_args("frames_u8_to_nhwc4", images, out, N, h, w)) return rc;
     return launch_frames_u8_to_nhwc4(images, out, N, h, w, (hipStream_t)stream);
 }
 int cosy_frames_to_nhwc4(const float* images, float* out, int N, int h, int w, cosy_stream_t stream) {
-    COSY_REQUIRE(images && out, "frames_to_nhwc4: null argument");
+    if (int rc = frames_args("frames_to_nhwc4", images, out, N, h, w)) return rc;
     return launch_frames_to_nhwc4(images, out, N, h, w, (hipStream_t)stream);
 }
 
@@ -801,41 +810,61 @@ int cosy_effnet_b3_features_nchw(cosy_net_t* n, int B, float* out, cosy_stream_t
 int cosy_crop_geometry(const float* pts_table, const int* obj_id, const float* K, const int* im_id, const float* TCO, int B, int P,
                        float z_min, int im_h, int im_w, int out_h, int out_w, float lamb, float* boxes_rend, float* boxes_crop,
                        float* K_crop, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0, "crop_geometry: B=%d is negative", B);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(pts_table && obj_id && K && TCO && boxes_rend && boxes_crop && K_crop, "crop_geometry: null argument");
-    COSY_REQUIRE(B >= 0 && P >= 1, "crop_geometry: bad sizes B=%d P=%d", B, P);
+    COSY_REQUIRE(P >= 1, "crop_geometry: P=%d, at least one point per object is needed", P);
+    COSY_REQUIRE(im_h >= 1 && im_w >= 1 && out_h >= 1 && out_w >= 1, "crop_geometry: bad sizes im_h=%d im_w=%d out_h=%d out_w=%d", im_h, im_w,
+                 out_h, out_w);
+    COSY_REQUIRE_PTR("crop_geometry", pts_table); COSY_REQUIRE_PTR("crop_geometry", obj_id); COSY_REQUIRE_PTR("crop_geometry", K);
+    COSY_REQUIRE_PTR("crop_geometry", TCO); COSY_REQUIRE_PTR("crop_geometry", boxes_rend); COSY_REQUIRE_PTR("crop_geometry", boxes_crop);
+    COSY_REQUIRE_PTR("crop_geometry", K_crop);
     return launch_crop_geometry(pts_table, obj_id, K, im_id, TCO, B, P, z_min, im_h, im_w, out_h, out_w, lamb, boxes_rend,
                                 boxes_crop, K_crop, (hipStream_t)stream);
 }
 
 int cosy_roi_align(const float* images, const int* im_id, const float* boxes, int B, int N, int C, int h, int w, int out_h,
                    int out_w, int sampling_ratio, float* out, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0 && B <= COSY_MAX_GRID_Y, "roi_align: B=%d outside [0, %d]", B, COSY_MAX_GRID_Y);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(images && boxes && out, "roi_align: null argument");
+    COSY_REQUIRE(N >= 1 && C >= 1 && h >= 1 && w >= 1, "roi_align: bad image size N=%d C=%d h=%d w=%d", N, C, h, w);
+    COSY_REQUIRE(out_h >= 1 && out_w >= 1 && (long)out_h * out_w <= 0x7fffffffL, "roi_align: bad output size out_h=%d out_w=%d", out_h, out_w);
+    COSY_REQUIRE(sampling_ratio > 0, "roi_align: sampling_ratio=%d must be > 0 (the reference uses 4)", sampling_ratio);
+    COSY_REQUIRE_PTR("roi_align", images); COSY_REQUIRE_PTR("roi_align", boxes); COSY_REQUIRE_PTR("roi_align", out);
     return launch_roi_align(images, im_id, boxes, B, N, C, h, w, out_h, out_w, sampling_ratio, out, (hipStream_t)stream);
 }
 
 int cosy_pose_update(const float* TCO_in, const float* K_crop, const float* pose9, int B, float* TCO_out, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0, "pose_update: B=%d is negative", B);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(TCO_in && K_crop && pose9 && TCO_out, "pose_update: null argument");
+    COSY_REQUIRE_PTR("pose_update", TCO_in); COSY_REQUIRE_PTR("pose_update", K_crop); COSY_REQUIRE_PTR("pose_update", pose9);
+    COSY_REQUIRE_PTR("pose_update", TCO_out);
     return launch_pose_update(TCO_in, K_crop, pose9, B, TCO_out, (hipStream_t)stream);
 }
 
 int cosy_tco_init_from_boxes(const float* boxes, const float* K, const int* im_id, int B, float z, float* TCO, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0, "tco_init_from_boxes: B=%d is negative", B);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(boxes && K && TCO, "tco_init_from_boxes: null argument");
+    COSY_REQUIRE_PTR("tco_init_from_boxes", boxes); COSY_REQUIRE_PTR("tco_init_from_boxes", K); COSY_REQUIRE_PTR("tco_init_from_boxes", TCO);
     return launch_tco_init_from_boxes(boxes, K, im_id, B, z, TCO, (hipStream_t)stream);
 }
 
 int cosy_tco_init_zup_autodepth(const float* boxes, const float* pts_table, const int* obj_id, const float* K, const int* im_id,
                                 int B, int P, float* TCO, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0, "tco_init_zup_autodepth: B=%d is negative", B);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(boxes && pts_table && obj_id && K && TCO, "tco_init_zup_autodepth: null argument");
+    // P = 0 would give max - min = -inf - inf over no point: a NaN depth, not an error anyone sees
+    COSY_REQUIRE(P >= 1, "tco_init_zup_autodepth: P=%d, at least one point per object is needed", P);
+    COSY_REQUIRE_PTR("tco_init_zup_autodepth", boxes); COSY_REQUIRE_PTR("tco_init_zup_autodepth", pts_table);
+    COSY_REQUIRE_PTR("tco_init_zup_autodepth", obj_id); COSY_REQUIRE_PTR("tco_init_zup_autodepth", K);
+    COSY_REQUIRE_PTR("tco_init_zup_autodepth", TCO);
     return launch_tco_init_zup(boxes, pts_table, obj_id, K, im_id, B, P, TCO, (hipStream_t)stream);
 }
 
 int cosy_scatter_argmin(const float* dists, const int* ids, int M, int n_seg, int* out, cosy_stream_t stream) {
-    COSY_REQUIRE(dists && ids && out, "scatter_argmin: null argument");
+    COSY_REQUIRE(M >= 0 && n_seg >= 0, "scatter_argmin: M=%d n_seg=%d must not be negative", M, n_seg);
+    if (n_seg == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("scatter_argmin", out);
+    if (M > 0) { COSY_REQUIRE_PTR("scatter_argmin", dists); COSY_REQUIRE_PTR("scatter_argmin", ids); }
     return launch_scatter_argmin(dists, ids, M, n_seg, out, (hipStream_t)stream);
 }
 

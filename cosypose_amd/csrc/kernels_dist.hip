@@ -29,6 +29,10 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
 }
 
+// torch.min / argmin treat NaN as the smallest value: the first NaN wins and later values never replace it.
+// (A plain `c < best` would skip a NaN that is not the first candidate.)
+__device__ __forceinline__ bool torch_min_takes(float c, float best) { return c < best || (c != c && best == best); }
+
 __global__ __launch_bounds__(256) void symmetric_distance_kernel(const float* __restrict__ T1, const float* __restrict__ T2,
                                                                  const int* __restrict__ obj, const float* __restrict__ pts,
                                                                  const float* __restrict__ sym, const int* __restrict__ n_sym,
@@ -63,7 +67,8 @@ __global__ __launch_bounds__(256) void symmetric_distance_kernel(const float* __
         sum_n = block_sum(sum_n, red);
         sum_sq = block_sum(sum_sq, red + 4);
         const float c = mode == 0 ? sum_n / (float)P : sum_sq / (float)P;
-        if (best < 0 || c < best_c) { best = s; best_c = c; best_d = sum_n / (float)P; }
+        // mode 0 is the reference's C++ scan (strict <: a NaN stays only where it comes first), mode 1 its torch argmin
+        if (best < 0 || (mode == 0 ? c < best_c : torch_min_takes(c, best_c))) { best = s; best_c = c; best_d = sum_n / (float)P; }
     }
     if (tid == 0) { min_dists[b] = best_d; best_sym[b] = best; }
     if (tid < 16 && best >= 0) S12[(size_t)b * 16 + tid] = sym[((size_t)o * S + best) * 16 + tid];
@@ -86,7 +91,7 @@ __device__ __forceinline__ void co_symmetric(const float* pred /*regs*/, const f
             acc += fabsf(q1[0] - q2[0]); acc += fabsf(q1[1] - q2[1]); acc += fabsf(q1[2] - q2[2]);
         }
         const float l = block_sum(acc, red) / (float)(3 * P);
-        if (arg < 0 || l < loss) { arg = s; loss = l; }
+        if (arg < 0 || torch_min_takes(l, loss)) { arg = s; loss = l; }
     }
 }
 
@@ -241,7 +246,10 @@ int cosy_symmetric_distance(const float* T1, const float* T2, const int* obj_id,
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(B >= 0 && P > 0 && S > 0 && (mode == 0 || mode == 1), "cosy_symmetric_distance: B=%d P=%d S=%d mode=%d", B, P, S, mode);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(T1 && T2 && pts_table && sym_table && min_dists && best_sym && S12, "cosy_symmetric_distance: null pointer");
+    COSY_REQUIRE_PTR("cosy_symmetric_distance", T1); COSY_REQUIRE_PTR("cosy_symmetric_distance", T2);
+    COSY_REQUIRE_PTR("cosy_symmetric_distance", pts_table); COSY_REQUIRE_PTR("cosy_symmetric_distance", sym_table);
+    COSY_REQUIRE_PTR("cosy_symmetric_distance", min_dists); COSY_REQUIRE_PTR("cosy_symmetric_distance", best_sym);
+    COSY_REQUIRE_PTR("cosy_symmetric_distance", S12);
     hipLaunchKernelGGL(symmetric_distance_kernel, dim3(B), dim3(256), 0, s, T1, T2, obj_id, pts_table, sym_table, n_sym, P, S, mode,
                        min_dists, best_sym, S12);
     COSY_CHECK_HIP(hipGetLastError());
@@ -253,7 +261,8 @@ int cosy_loss_co_symmetric(const float* TCO_possible_gt, const float* TCO_pred, 
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(B >= 0 && P > 0 && S > 0, "cosy_loss_co_symmetric: B=%d S=%d P=%d", B, S, P);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(TCO_possible_gt && TCO_pred && pts_table && loss, "cosy_loss_co_symmetric: null pointer");
+    COSY_REQUIRE_PTR("cosy_loss_co_symmetric", TCO_possible_gt); COSY_REQUIRE_PTR("cosy_loss_co_symmetric", TCO_pred);
+    COSY_REQUIRE_PTR("cosy_loss_co_symmetric", pts_table); COSY_REQUIRE_PTR("cosy_loss_co_symmetric", loss);
     hipLaunchKernelGGL(loss_co_symmetric_kernel, dim3(B), dim3(256), 0, s, TCO_possible_gt, TCO_pred, pts_table, obj_id, S, P, loss,
                        min_id, TCO_assign);
     COSY_CHECK_HIP(hipGetLastError());
@@ -266,7 +275,9 @@ int cosy_loss_refiner_disentangled(const float* TCO_possible_gt, const float* TC
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(B >= 0 && P > 0 && S > 0, "cosy_loss_refiner_disentangled: B=%d S=%d P=%d", B, S, P);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(TCO_possible_gt && TCO_input && refiner_outputs && K_crop && pts_table && loss, "cosy_loss_refiner_disentangled: null pointer");
+    COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", TCO_possible_gt); COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", TCO_input);
+    COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", refiner_outputs); COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", K_crop);
+    COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", pts_table); COSY_REQUIRE_PTR("cosy_loss_refiner_disentangled", loss);
     hipLaunchKernelGGL(loss_refiner_disentangled_kernel, dim3(B), dim3(256), 0, s, TCO_possible_gt, TCO_input, refiner_outputs, K_crop,
                        pts_table, obj_id, S, P, loss);
     COSY_CHECK_HIP(hipGetLastError());
@@ -277,8 +288,10 @@ int cosy_dists_add(const float* TXO_pred, const float* TXO_gt, const float* pts_
                    float* dists, cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(B >= 0 && P > 0, "cosy_dists_add: B=%d P=%d", B, P);
+    COSY_REQUIRE(B <= COSY_MAX_GRID_Y, "cosy_dists_add: B=%d exceeds %d (one grid row per item)", B, COSY_MAX_GRID_Y);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(TXO_pred && TXO_gt && pts_table && dists, "cosy_dists_add: null pointer");
+    COSY_REQUIRE_PTR("cosy_dists_add", TXO_pred); COSY_REQUIRE_PTR("cosy_dists_add", TXO_gt);
+    COSY_REQUIRE_PTR("cosy_dists_add", pts_table); COSY_REQUIRE_PTR("cosy_dists_add", dists);
     hipLaunchKernelGGL(dists_add_kernel, dim3(cdiv(P, 256), B), dim3(256), 0, s, TXO_pred, TXO_gt, pts_table, obj_id, P, symmetric ? 1 : 0,
                        dists);
     COSY_CHECK_HIP(hipGetLastError());
@@ -292,7 +305,8 @@ int cosy_expand_ids_for_symmetry(const int* n_sym_item, int B, int* ids_expand, 
         if (total) COSY_CHECK_HIP(hipMemsetAsync(total, 0, sizeof(int), s));
         return COSY_OK;
     }
-    COSY_REQUIRE(n_sym_item && ids_expand && sym_ids, "cosy_expand_ids_for_symmetry: null pointer");
+    COSY_REQUIRE_PTR("cosy_expand_ids_for_symmetry", n_sym_item); COSY_REQUIRE_PTR("cosy_expand_ids_for_symmetry", ids_expand);
+    COSY_REQUIRE_PTR("cosy_expand_ids_for_symmetry", sym_ids);
     hipLaunchKernelGGL(expand_ids_kernel, dim3(1), dim3(256), 0, s, n_sym_item, B, ids_expand, sym_ids, total);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;

@@ -170,6 +170,8 @@ int launch_roi_align(const float* images, const int* im_id, const float* boxes, 
     (void)N;
     if (B == 0) return COSY_OK;
     COSY_REQUIRE(sampling > 0, "roi_align: sampling_ratio must be > 0 (the reference uses 4)");
+    COSY_REQUIRE(B > 0 && B <= COSY_MAX_GRID_Y && C > 0 && out_h > 0 && out_w > 0, "roi_align: bad sizes B=%d C=%d out_h=%d out_w=%d", B, C, out_h,
+                 out_w);   // B is gridDim.y
     hipLaunchKernelGGL(roi_align_kernel, dim3(cdiv(out_h * out_w, 256), B), dim3(256), 0, s, images, im_id, boxes, C, h, w,
                        out_h, out_w, sampling, out);
     COSY_CHECK_HIP(hipGetLastError());
@@ -212,12 +214,14 @@ __global__ __launch_bounds__(256) void frames_u8_to_nhwc4_kernel(const unsigned 
 }
 int launch_frames_u8_to_nhwc4(const unsigned char* images, float* out, int N, int h, int w, hipStream_t s) {
     if (N == 0) return COSY_OK;
+    COSY_REQUIRE(N > 0 && N <= COSY_MAX_GRID_Y && h > 0 && w > 0, "frames_u8_to_nhwc4: bad sizes N=%d h=%d w=%d", N, h, w);   // N is gridDim.y
     hipLaunchKernelGGL(frames_u8_to_nhwc4_kernel, dim3(cdiv(h * w, 256), N), dim3(256), 0, s, images, out, h * w);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }
 int launch_frames_to_nhwc4(const float* images, float* out, int N, int h, int w, hipStream_t s) {
     if (N == 0) return COSY_OK;
+    COSY_REQUIRE(N > 0 && N <= COSY_MAX_GRID_Y && h > 0 && w > 0, "frames_to_nhwc4: bad sizes N=%d h=%d w=%d", N, h, w);   // N is gridDim.y
     hipLaunchKernelGGL(frames_to_nhwc4_kernel, dim3(cdiv(h * w, 256), N), dim3(256), 0, s, images, out, h * w);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
@@ -762,22 +766,30 @@ int launch_tco_init_zup(const float* boxes, const float* pts_table, const int* o
 // ----------------------------------------------------------------------------------------
 // scatter_argmin (cosypose_cext.cpp:218-245): segmented argmin, first index wins.
 // Single-launch, deterministic: one wave per segment scans the (short) id list.
+// NaN follows the reference's scan (the first member seeds the minimum, then strict <): a NaN is the result exactly when
+// it is the segment's FIRST member, and is never chosen otherwise.  So the wave reduces two things: the first member's
+// index, and the (value, index)-smallest member among the non-NaN ones.
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void scatter_argmin_kernel(const float* __restrict__ dists, const int* __restrict__ ids, int M,
                                                             int* __restrict__ out) {
     const int seg = blockIdx.x, lane = threadIdx.x;
-    float best = INFINITY; int bi = -1;
+    float best = INFINITY; int bi = -1, first = 0x7fffffff;
     for (int m = lane; m < M; m += 64) {
         if (ids[m] != seg) continue;
+        first = min(first, m);
         const float d = dists[m];
-        if (bi < 0 || d < best) { best = d; bi = m; }   // strict <: first index wins within a lane
+        if (d == d && (bi < 0 || d < best)) { best = d; bi = m; }   // strict <: first index wins within a lane
     }
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
         const bool take = oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi));
         if (take) { best = ob; bi = oi; }
+        first = min(first, __shfl_xor(first, o, 64));
     }
-    if (lane == 0) out[seg] = bi;
+    if (lane != 0) return;
+    if (first == 0x7fffffff) { out[seg] = -1; return; }   // no member
+    const float f = dists[first];
+    out[seg] = f != f ? first : bi;
 }
 
 int launch_scatter_argmin(const float* dists, const int* ids, int M, int n_seg, int* out, hipStream_t s) {

@@ -66,7 +66,8 @@ size_t cosy_effnet_b3_workspace_bytes(const cosy_net_t* net);
 int cosy_effnet_b3_set_input_nchw(cosy_net_t* net, const float* x, int B, cosy_stream_t stream);
 
 /* Frames (N,3,h,w) fp32 planar -> (N,h,w,4) fp32 interleaved (RGB + pad), the layout cosy_crop_pack samples from.
- * Done once per PosePredictor.forward call (the frames do not change across iterations); out holds N*h*w*4 floats. */
+ * Done once per PosePredictor.forward call (the frames do not change across iterations); out holds N*h*w*4 floats.
+ * 0 <= N <= 65535 (one grid row per frame), h, w >= 1; N = 0 is COSY_OK with null pointers; anything else COSY_EINVAL. */
 int cosy_frames_to_nhwc4(const float* images, float* out, int N, int h, int w, cosy_stream_t stream);
 /* the same from uint8 frames (N,3,h,w) as the datasets deliver them: out = value / 255.f (training/pose_forward_loss.py:24: images.float() / 255.) */
 int cosy_frames_u8_to_nhwc4(const unsigned char* images, float* out, int N, int h, int w, cosy_stream_t stream);
@@ -128,7 +129,14 @@ int cosy_effnet_b3_profile_read(cosy_net_t* net, cosy_prof_rec_t* recs, int cap,
  * (cosypose/lib3d/cropping.py:7-47, lamb=1.4, not clamped), get_K_crop_resize (camera_geometry.py:45-87).
  * pts_table (n_obj,P,3) = mesh_db points after sample_points(P, deterministic=True)
  * (cosypose/lib3d/mesh_ops.py:31-41); obj_id (B) int32 rows of pts_table; K is (N,3,3) indexed
- * by im_id (B) or (B,3,3) when im_id is NULL. */
+ * by im_id (B) or (B,3,3) when im_id is NULL.
+ *
+ * Argument limits of every entry of this section and the two below (checked on the host, before any launch; a violation
+ * returns COSY_EINVAL and cosy_last_error() names the argument): batch sizes B, M, n_seg >= 0, and B = 0 (n_seg = 0)
+ * returns COSY_OK at once, with null data pointers allowed; P >= 1, S >= 1; im_h, im_w, out_h, out_w, C >= 1 and
+ * sampling_ratio >= 1; every pointer not called optional must be non-null; cosy_roi_align and cosy_dists_add take
+ * B <= 65535 (one grid row per item; split larger batches).  The VALUES of obj_id / im_id / n_sym live on the device and
+ * are the caller's to keep inside their tables. */
 int cosy_crop_geometry(const float* pts_table, const int* obj_id, const float* K, const int* im_id, const float* TCO,
                        int B, int P, float z_min, int im_h, int im_w, int out_h, int out_w, float lamb,
                        float* boxes_rend, float* boxes_crop, float* K_crop, cosy_stream_t stream);
@@ -153,8 +161,9 @@ int cosy_tco_init_zup_autodepth(const float* boxes, const float* pts_table, cons
 
 /* ---- index / assignment ops adjacent to the loop (bit-exact) --------------------------------
  * scatter_argmin (cosypose/csrc/cosypose_cext.cpp:218-245): per segment id in [0,n_seg) the index of the
- * smallest distance, first index wins on ties; out[s] = -1 for an empty segment. dists (M) fp32,
- * ids (M) int32 on the device. */
+ * smallest distance, first index wins on ties; out[s] = -1 for an empty segment (the reference's loop reads a missing
+ * key of its map there, which yields 0 and lengthens its output). dists (M) fp32, ids (M) int32 on the device.
+ * NaN as in the reference's scan: a NaN distance is chosen exactly when it is the segment's first member. */
 int cosy_scatter_argmin(const float* dists, const int* ids, int M, int n_seg, int* out, cosy_stream_t stream);
 
 /* expand_ids_for_symmetry (cosypose/csrc/cosypose_cext.cpp:247-259): for item n (in order), for k < n_sym_item[n]:
@@ -169,7 +178,9 @@ int cosy_expand_ids_for_symmetry(const int* n_sym_item, int B, int* ids_expand, 
  * cosy_symmetric_distance: symmetric_distance_batched (mode 0) / symmetric_distance_batched_fast (mode 1),
  * cosypose/lib3d/symmetric_distances.py:19-57.  sym_table (n_obj,S,4,4) is the identity-padded symmetry table,
  * n_sym (n_obj) the real counts (mode 0 scans only those, like expand_ids_for_symmetry + scatter_argmin: strict <,
- * first wins; mode 1 scans all S rows and takes the first minimum of the mean SQUARED distance, like argmin).
+ * first wins; mode 1 scans all S rows and takes the first minimum of the mean SQUARED distance, like argmin -- a NaN
+ * cost counts as the smallest there, as in torch; in mode 0 it is kept only where it comes first, as in the C++ scan).
+ * n_sym == NULL: mode 0 scans all S rows too.
  * -> min_dists (B), best_sym (B) int32, S12 (B,4,4) = sym_table[obj, best]. */
 int cosy_symmetric_distance(const float* T1, const float* T2, const int* obj_id, const float* pts_table, const float* sym_table,
                             const int* n_sym, int B, int P, int S, int mode, float* min_dists, int* best_sym, float* S12,
@@ -182,7 +193,7 @@ int cosy_symmetric_distance_reprojected(const float* T1, const float* T2, const 
                                         const float* sym_table, const int* n_sym, int B, int n_obj, int P, int S, float* min_dists,
                                         int* best_sym, float* S12, cosy_stream_t stream);
 /* loss_CO_symmetric with l1 (cosypose/lib3d/cosypose_ops.py:34-46), forward value: per sample the minimum over the S
- * possible ground truths of mean |pred points - gt points| (first minimum wins, torch.min) -> loss (B), min_id (B)
+ * possible ground truths of mean |pred points - gt points| (first minimum wins, a NaN counts as the smallest: torch.min) -> loss (B), min_id (B)
  * int32 (optional), TCO_assign (B,4,4) (optional). */
 int cosy_loss_co_symmetric(const float* TCO_possible_gt, const float* TCO_pred, const float* pts_table, const int* obj_id, int B,
                            int S, int P, float* loss, int* min_id, float* TCO_assign, cosy_stream_t stream);
