@@ -14,6 +14,10 @@
 //      id): order-independent, hence deterministic
 //   3. resolve: one thread per pixel re-derives the barycentrics of the winning face, perspective-correct colour
 //      interpolation, Lambert term from the camera-space face normal, clamps, writes planar RGB (+ depth).
+// Near plane, where this differs from OpenGL: a triangle with ANY vertex at z <= 0.01 is dropped whole (the z-buffer pass tests the
+// three vertices, not the pixel), where OpenGL clips it at the plane and keeps the part beyond.  An object that straddles the near
+// plane loses its nearest triangles entirely; tests/test_raster_kernels.py exempts exactly those pixels from its float64 ray caster.
+// The z-buffer pass puts the batch in gridDim.y: the wrappers refuse B > 65535 (COSY_MAX_GRID_Y) before any launch.
 // fp32 with contraction off: oracle/cosy_oracle.c:cosy_oracle_rasterize is the same arithmetic in scalar loops and the
 // GPU tests require identical face ids / depths.
 #include "cosy_common.h"
@@ -168,10 +172,18 @@ int launch_render_zbuffer(const float* verts, const int* faces, const int* n_fac
     return COSY_OK;
 }
 int check_mesh_shade(const cosy_mesh_t* mesh, const cosy_shade_t* shade, MeshView* m, ShadeParams* sp) {
-    COSY_REQUIRE(mesh && shade, "render: null mesh / shade");
-    COSY_REQUIRE(mesh->verts && mesh->colors && mesh->faces && mesh->n_faces && mesh->V > 0 && mesh->F > 0, "render: incomplete mesh set");
-    COSY_REQUIRE(!shade->smooth || mesh->normals, "render: smooth shading needs vertex normals");
-    COSY_REQUIRE(!mesh->tex || (mesh->uvs && mesh->TH > 0 && mesh->TW > 0), "render: a texture needs uvs and its size");
+    COSY_REQUIRE_PTR("render", mesh);
+    COSY_REQUIRE_PTR("render", shade);
+    COSY_REQUIRE(mesh->V > 0 && mesh->F > 0, "render: V=%d F=%d (both must be positive)", mesh->V, mesh->F);
+    const float *verts = mesh->verts, *colors = mesh->colors;
+    const int *faces = mesh->faces, *n_faces = mesh->n_faces;
+    COSY_REQUIRE_PTR("render", verts);
+    COSY_REQUIRE_PTR("render", colors);
+    COSY_REQUIRE_PTR("render", faces);
+    COSY_REQUIRE_PTR("render", n_faces);
+    COSY_REQUIRE(!shade->smooth || mesh->normals, "render: smooth shading needs vertex normals (null normals)");
+    COSY_REQUIRE(!mesh->tex || (mesh->uvs && mesh->TH > 0 && mesh->TW > 0), "render: a texture needs uvs and its size (uvs %s, TH=%d TW=%d)",
+                 mesh->uvs ? "given" : "null", mesh->TH, mesh->TW);
     *m = MeshView{mesh->verts, mesh->colors, mesh->normals, mesh->uvs, mesh->tex, mesh->faces, mesh->V, mesh->F, mesh->TH, mesh->TW};
     *sp = ShadeParams{shade->ambient, shade->diffuse, shade->specular, shade->shininess, shade->light[0], shade->light[1], shade->light[2],
                       shade->light_frame, shade->smooth, shade->quantize};
@@ -184,10 +196,19 @@ int render_crop_pack(void* x, int dtype, const cosy_mesh_t* mesh, const cosy_sha
     MeshView m; ShadeParams sp;
     int rc;
     if ((rc = check_mesh_shade(mesh, shade, &m, &sp))) return rc;
-    COSY_REQUIRE(B >= 0 && H > 0 && W > 0 && h > 0 && w > 0, "render_crop_pack: B=%d H=%d W=%d h=%d w=%d", B, H, W, h, w);
+    COSY_REQUIRE(B >= 0 && B <= COSY_MAX_GRID_Y, "render_crop_pack: B=%d outside [0, %d]", B, COSY_MAX_GRID_Y);   // B is gridDim.y of the z-buffer pass
+    COSY_REQUIRE(H > 0 && W > 0 && h > 0 && w > 0, "render_crop_pack: bad sizes H=%d W=%d h=%d w=%d", H, W, h, w);
     COSY_REQUIRE(dtype == COSY_F32 || dtype == COSY_BF16 || dtype == COSY_F16, "render_crop_pack: dtype %d", dtype);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(x && obj_id && TCO && K_crop && frames4 && boxes && scratch, "render_crop_pack: null pointer");
+    const void* x_nhwc8 = x;
+    const float *frames_nhwc4 = frames4, *boxes_crop = boxes;
+    COSY_REQUIRE_PTR("render_crop_pack", x_nhwc8);
+    COSY_REQUIRE_PTR("render_crop_pack", obj_id);
+    COSY_REQUIRE_PTR("render_crop_pack", TCO);
+    COSY_REQUIRE_PTR("render_crop_pack", K_crop);
+    COSY_REQUIRE_PTR("render_crop_pack", frames_nhwc4);
+    COSY_REQUIRE_PTR("render_crop_pack", boxes_crop);
+    COSY_REQUIRE_PTR("render_crop_pack", scratch);
     if ((rc = launch_render_zbuffer(m.verts, m.faces, mesh->n_faces, obj_id, TCO, K_crop, B, m.V, m.F, H, W, scratch, s))) return rc;
     return launch_render_crop_pack(x, dtype, frames4, im_id, boxes, scratch, m, obj_id, TCO, sp, B, h, w, H, W, s);
 }
@@ -208,9 +229,14 @@ int cosy_render_meshes_ex(const cosy_mesh_t* mesh, const cosy_shade_t* shade, co
     MeshView m; ShadeParams sp;
     int rc;
     if ((rc = check_mesh_shade(mesh, shade, &m, &sp))) return rc;
-    COSY_REQUIRE(B >= 0 && H > 0 && W > 0, "render_meshes: B=%d H=%d W=%d", B, H, W);
+    COSY_REQUIRE(B >= 0 && B <= COSY_MAX_GRID_Y, "render_meshes: B=%d outside [0, %d]", B, COSY_MAX_GRID_Y);   // B is gridDim.y of every pass
+    COSY_REQUIRE(H > 0 && W > 0, "render_meshes: bad sizes H=%d W=%d", H, W);
     if (B == 0) return COSY_OK;
-    COSY_REQUIRE(obj_id && TCO && K && rgb && scratch, "render_meshes: null pointer");
+    COSY_REQUIRE_PTR("render_meshes", obj_id);
+    COSY_REQUIRE_PTR("render_meshes", TCO);
+    COSY_REQUIRE_PTR("render_meshes", K);
+    COSY_REQUIRE_PTR("render_meshes", rgb);
+    COSY_REQUIRE_PTR("render_meshes", scratch);
     if ((rc = launch_render_zbuffer(m.verts, m.faces, mesh->n_faces, obj_id, TCO, K, B, m.V, m.F, H, W, scratch, s))) return rc;
     const unsigned long long* zbuf = (const unsigned long long*)scratch;
     const float* uvz = (const float*)(zbuf + (size_t)B * H * W);
@@ -222,7 +248,6 @@ int cosy_render_meshes_ex(const cosy_mesh_t* mesh, const cosy_shade_t* shade, co
 int cosy_render_meshes(const float* verts, const float* colors, const int* faces, const int* n_faces, const int* obj_id,
                        const float* TCO, const float* K, int B, int V, int F, int H, int W, float ambient, float diffuse,
                        float light_x, float light_y, float light_z, float* rgb, float* depth, void* scratch, cosy_stream_t stream) {
-    COSY_REQUIRE(B >= 0 && V > 0 && F > 0 && H > 0 && W > 0, "render_meshes: B=%d V=%d F=%d H=%d W=%d", B, V, F, H, W);
     cosy_mesh_t mesh{verts, colors, nullptr, nullptr, nullptr, faces, n_faces, V, F, 0, 0};
     cosy_shade_t shade{ambient, diffuse, 0.f, 1.f, {light_x, light_y, light_z}, 0, 0, 0};
     return cosy_render_meshes_ex(&mesh, &shade, obj_id, TCO, K, B, H, W, rgb, depth, scratch, stream);

@@ -333,7 +333,12 @@ int cosy_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  * (n_obj,V,3), faces (n_obj,F,3) int32 (padded), n_faces (n_obj); per crop obj_id, TCO (B,4,4), K (B,3,3) ->
  * rgb (B,3,H,W) in [0,1] (black background, non-finite poses -> black) and optional depth (B,H,W) in metres.
  * Shading = vertex colour x (ambient + diffuse |n.l|), l = light direction in the camera frame (PyBullet's OpenGL shading
- * is third-party: pixel values parity-unpinned).  `scratch`: cosy_render_scratch_bytes(B,V,H,W) bytes. */
+ * is third-party: pixel values parity-unpinned).  `scratch`: cosy_render_scratch_bytes(B,V,H,W) bytes.
+ * Limits, checked before anything is launched (COSY_EINVAL, cosy_last_error() names the argument): 0 <= B <= 65535 (the batch is
+ * the grid's y dimension); H, W, V, F > 0; with B > 0 every pointer except `depth` non-null ("null TCO").  B = 0 returns COSY_OK
+ * and touches no pointer.  depth = NULL: no depth is written.  A triangle with any vertex at z <= 0.01 is dropped whole (OpenGL
+ * would clip it at the near plane).  The light direction must be a UNIT vector: it is used as given, neither checked nor
+ * normalised (cosypose_amd.rasterizer.HipBatchRenderer normalises it for its callers). */
 size_t cosy_render_scratch_bytes(int B, int V, int H, int W);
 int cosy_render_meshes(const float* verts, const float* colors, const int* faces, const int* n_faces, const int* obj_id,
                        const float* TCO, const float* K, int B, int V, int F, int H, int W, float ambient, float diffuse,
@@ -358,18 +363,22 @@ typedef struct {
 } cosy_mesh_t;
 typedef struct {
     float ambient, diffuse, specular, shininess;
-    float light[3];       /* unit vector from the surface towards the light */
+    float light[3];       /* unit vector from the surface towards the light: a precondition, not checked, not normalised */
     int light_frame;      /* 0: camera frame, 1: object (PyBullet world) frame */
     int smooth;           /* 0: flat two-sided face normals, 1: interpolated vertex normals */
     int quantize;         /* 1: round colours to multiples of 1/255 */
 } cosy_shade_t;
+/* Limits as cosy_render_meshes; in addition smooth = 1 without mesh->normals and mesh->tex without mesh->uvs or with TH / TW <= 0
+ * are refused (COSY_EINVAL). */
 int cosy_render_meshes_ex(const cosy_mesh_t* mesh, const cosy_shade_t* shade, const int* obj_id, const float* TCO, const float* K, int B,
                           int H, int W, float* rgb, float* depth, void* scratch, cosy_stream_t stream);
 
 /* Render + crop + pack in one pass (replaces renderer.render -> cosy_crop_pack when the renderer is this library's): the
  * resolve pass of the rasteriser also samples the observed frame (roi_align, as cosy_crop_pack) and writes the network's
  * 8-channel NHWC input pixel directly -- no fp32 (B,3,H,W) render tensor is written or read.  K = K_crop (B,3,3); the
- * render resolution is the network's input resolution. */
+ * render resolution is the network's input resolution.  Same limits as cosy_render_meshes_ex (0 <= B <= 65535; H, W, h, w > 0; mesh
+ * with V, F > 0 and verts / colors / faces / n_faces; smooth shading needs normals, a texture needs uvs and TH, TW > 0); im_id may
+ * be NULL (crop b reads frame b); dtype is COSY_F32, COSY_BF16 or COSY_F16. */
 int cosy_render_crop_pack(cosy_net_t* net, const cosy_mesh_t* mesh, const cosy_shade_t* shade, const int* obj_id, const float* TCO,
                           const float* K_crop, const float* frames_nhwc4, const int* im_id, const float* boxes_crop, int B, int N, int h,
                           int w, void* scratch, cosy_stream_t stream);

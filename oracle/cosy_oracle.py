@@ -246,7 +246,9 @@ def dists_add(pred, gt, points, symmetric=False):
 
 def rasterize(verts, colors, faces, n_faces, obj, TCO, K, H, W, ambient=0.6, diffuse=0.4, light_dir=(0., 0., -1.), normals=None, uvs=None,
               tex=None, specular=0.0, shininess=1.0, light_frame=0, smooth=0, quantize=0):
-    """CPU twin of the HIP mesh rasteriser -> rgb (B,3,H,W), depth (B,H,W), zbuf (B,H,W) uint64.  tex: (n_obj,TH,TW,4)."""
+    """CPU twin of the HIP mesh rasteriser -> rgb (B,3,H,W), depth (B,H,W), zbuf (B,H,W) uint64.  tex: (n_obj,TH,TW,4).
+    `light_dir` is passed through AS GIVEN (rounded to float32): it must already be a unit vector.  HipBatchRenderer normalises
+    its light; hand this function the same normalised float32 vector when comparing the two."""
     verts, vp = _f(verts); colors, cp = _f(colors); faces, fp = _i(faces); n_faces, nfp = _i(n_faces); obj, op = _i(obj)
     TCO, tp = _f(TCO); K, kp = _f(K)
     shade, sp = _f(np.array([ambient, diffuse, specular, shininess, *light_dir, light_frame, smooth, quantize], np.float32))
