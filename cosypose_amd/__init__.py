@@ -25,6 +25,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'multiview_candidate_matching':
         from .multiview_matching import multiview_candidate_matching
         return multiview_candidate_matching
+    if name == 'PoseErrorMeter':
+        from .pose_meters import PoseErrorMeter
+        return PoseErrorMeter
     if name == 'h_pose':
         from .pose_forward_loss import h_pose
         return h_pose

@@ -42,6 +42,8 @@ _SIGNATURES = {
     'cosy_loss_co_symmetric': ([_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
     'cosy_loss_refiner_disentangled': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
     'cosy_dists_add': ([_P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
+    'cosy_pose_errors_workspace_bytes': ([_I, _I], _SZ),
+    'cosy_pose_errors': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P], _I),
     'cosy_render_scratch_bytes': ([_I, _I, _I, _I], _c.c_size_t),
     'cosy_render_meshes': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P], _I),
     'cosy_render_meshes_ex': ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),

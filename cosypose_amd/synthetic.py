@@ -283,3 +283,63 @@ def ba_scene_collections(scene, make_mesh_db, dtype=None, device=None, collectio
     cams = PandasTensorCollection(pd.DataFrame(dict(view_id=scene['cam_view_id'])), K=t(scene['cam_K']))
     pairs = PandasTensorCollection(pd.DataFrame(dict(view1=scene['pair_view1'], view2=scene['pair_view2'])), TC1C2=t(scene['pair_TC1C2']))
     return cand, cams, pairs, mesh_db
+
+
+# ---- evaluation scenes for the pose meter (cosypose_amd/pose_meters.py) -------------------------------------------------------------
+EVAL_N_POINTS = (150, 257, 400, 640, 900, 1100, 1500)      # points per label: all different, one just past a 256-point boundary
+
+
+def make_eval_meshes(seed, n_points=EVAL_N_POINTS):
+    """Meshes of different sizes for the pose meter -> (labels, points (n_obj, max n, 3) float32 padded by repeating each mesh's first
+    point, infos {label: dict(label, n_points, n_sym, is_symmetric, diameter_m)}).  Every second label is symmetric; the diameter is
+    the diagonal of the bounding box."""
+    rs = np.random.RandomState(seed)
+    labels = [f'obj_{n + 1:06d}' for n in range(len(n_points))]
+    pts = np.zeros((len(labels), max(n_points), 3), dtype=np.float32)
+    infos = {}
+    for n, (label, P) in enumerate(zip(labels, n_points)):
+        ext = rs.uniform(0.03, 0.12, 3)
+        p = (rs.uniform(-1, 1, (P, 3)) * ext).astype(np.float32)
+        pts[n, :P] = p
+        pts[n, P:] = p[0]
+        diameter = float(np.linalg.norm(p.max(0).astype(np.float64) - p.min(0).astype(np.float64)))
+        infos[label] = dict(label=label, n_points=P, n_sym=1, is_symmetric=bool(n % 2), diameter_m=diameter)
+    return labels, pts, infos
+
+
+def make_eval_scene(seed, labels, infos, scene_ids=(3, 7), n_views=3):
+    """Ground truth and predictions of a few views for the pose meter -> dict of columns (numpy): gt_scene_id, gt_view_id, gt_label
+    (index into labels), gt_visib_fract, gt_poses (n,4,4) float32; pred_scene_id, pred_view_id, pred_label, pred_score (all
+    different), pred_poses.  Up to three instances of a label per view, the later ones within a diameter of the first; a
+    prediction per ground truth with probability 0.85, noisy by 0.5 % / 4 % / 12 % / 40 % of the diameter (and 0.01-0.3 rad), plus
+    spurious predictions, predictions of labels that are not in the view and predictions in a view without ground truth."""
+    rs = np.random.RandomState(seed)
+    gt, pred = [], []
+    for scene_id in scene_ids:
+        for view_id in range(n_views):
+            present = rs.permutation(len(labels))[:rs.randint(4, len(labels) + 1)]
+            for l in present:
+                d = infos[labels[l]]['diameter_m']
+                base = make_TCO(rs.randint(1 << 30), 1)[0].astype(np.float64)
+                for inst in range(rs.randint(1, 4)):
+                    T = base.copy()
+                    if inst:
+                        T = T @ _rigid_noise(rs, 1.0, 0.35 * d)
+                    gt.append((scene_id, view_id, l, rs.uniform(0.05, 1.0), T))
+                    if rs.uniform() < 0.85:
+                        level = rs.randint(4)
+                        noise = _rigid_noise(rs, (0.01, 0.05, 0.15, 0.3)[level], (0.005, 0.04, 0.12, 0.4)[level] * d / np.sqrt(3))
+                        pred.append((scene_id, view_id, l, T @ noise))
+                if rs.uniform() < 0.3:      # a spurious prediction near the object
+                    pred.append((scene_id, view_id, l, base @ _rigid_noise(rs, 1.0, 0.5 * d)))
+            absent = [l for l in range(len(labels)) if l not in present]
+            if absent:                      # a label the view does not hold
+                pred.append((scene_id, view_id, absent[0], make_TCO(rs.randint(1 << 30), 1)[0].astype(np.float64)))
+    pred.append((scene_ids[0], n_views + 5, 0, make_TCO(rs.randint(1 << 30), 1)[0].astype(np.float64)))      # a view without ground truth
+    order = rs.permutation(len(pred))
+    pred = [pred[n] for n in order]
+    score = rs.permutation(len(pred)).astype(np.float64) / len(pred) * 0.9 + 0.05
+    return dict(gt_scene_id=np.array([g[0] for g in gt]), gt_view_id=np.array([g[1] for g in gt]), gt_label=np.array([g[2] for g in gt]),
+                gt_visib_fract=np.array([g[3] for g in gt]), gt_poses=np.stack([g[4] for g in gt]).astype(np.float32),
+                pred_scene_id=np.array([p[0] for p in pred]), pred_view_id=np.array([p[1] for p in pred]),
+                pred_label=np.array([p[2] for p in pred]), pred_score=score, pred_poses=np.stack([p[3] for p in pred]).astype(np.float32))

@@ -207,6 +207,25 @@ int cosy_loss_refiner_disentangled(const float* TCO_possible_gt, const float* TC
 int cosy_dists_add(const float* TXO_pred, const float* TXO_gt, const float* pts_table, const int* obj_id, int B, int P,
                    int symmetric, float* dists, cosy_stream_t stream);
 
+/* ---- pose evaluation (cosypose/evaluation/meters/pose_meters.py:53-92) ----------------------------------------------
+ * PoseErrorMeter.compute_errors for B tentative (prediction, ground truth) pairs in one call, on points[:n_points[obj]] of each
+ * pair's object: errors (B,8) = norm_avg, xyz_avg[3], TCO_xyz[3], TCO_norm.  The per-point vector is the one cosy_dists_add
+ * produces, bit for bit: gt point minus predicted point where mode[b] = 0 (ADD), minus the NEAREST predicted point (first minimum
+ * of the squared distance) where mode[b] != 0 (ADD-S); the mode is per pair, so ADD(-S) is one call.  norm_avg = mean of the
+ * vectors' norms, xyz_avg = mean of |components|, both accumulated in float64 in a fixed order (per-tile partial sums in the
+ * workspace, then tile order): no floating-point atomics, the same bits from run to run, and a pair's result does not depend on
+ * what else is in the batch.  TCO_xyz = |t_pred - t_gt|, TCO_norm its norm.
+ * pts_table (n_obj,n_max,3), n_points (n_obj) int32 on the device.  B is bounded only by B * ceil(n_max / 1024) < 2^31.
+ * Checked on the host before any launch (COSY_EINVAL, cosy_last_error() names the argument): B >= 0, n_obj >= 1, n_max >= 1,
+ * every pointer non-null, workspace 16-byte aligned with workspace_bytes >= cosy_pose_errors_workspace_bytes(B, n_max); B = 0
+ * returns COSY_OK at once with null pointers.  The VALUES of obj_id / n_points live on the device and are checked there: an
+ * obj_id outside [0, n_obj) reads nothing and gives NaN norm_avg / xyz_avg for its pair, n_points is clamped to [0, n_max]
+ * (0 points: NaN, the mean of nothing). */
+size_t cosy_pose_errors_workspace_bytes(int B, int n_max);
+int cosy_pose_errors(const float* TXO_pred, const float* TXO_gt, const int* obj_id, const int* mode, const float* pts_table,
+                     const int* n_points, int B, int n_obj, int n_max, float* errors, void* workspace, size_t workspace_bytes,
+                     cosy_stream_t stream);
+
 /* ---- training step of the refiner network, fp32, activations NHWC = rows x channels --------------
  * Every piece of cosypose/training/train_pose.py:317-331's step: the 1x1 convolutions and their gradients on the library's own
  * fp32 MFMA GEMMs (cosy_train_gemm / cosy_wgrad below), BatchNorm, depthwise, squeeze-excite scaling, loss gradient, clip +
