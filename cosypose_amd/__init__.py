@@ -19,6 +19,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('HipBatchRenderer', 'RenderMeshes'):
         from . import rasterizer
         return getattr(rasterizer, name)
+    if name in ('HipSceneRenderer', 'scene_visibility'):
+        from . import scene_renderer
+        return getattr(scene_renderer, name)
     if name == 'MultiviewScenePredictor':
         from .multiview_predictor import MultiviewScenePredictor
         return MultiviewScenePredictor

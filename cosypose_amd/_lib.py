@@ -49,6 +49,8 @@ _SIGNATURES = {
     'cosy_render_meshes_ex': ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
     'cosy_render_crop_pack': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     'cosy_render_crop_pack_to': ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    'cosy_render_scene_scratch_bytes': ([_I, _I, _I, _I, _I], _SZ),
+    'cosy_render_scene': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     'cosy_train_workspace_bytes': ([], _c.c_size_t),
     'cosy_crop_pack_to': ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     'cosy_crop_pack_to_ws': ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),

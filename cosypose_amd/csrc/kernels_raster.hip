@@ -28,15 +28,6 @@
 namespace cosy {
 namespace {
 
-__device__ __forceinline__ bool pose_finite(const float* T, const float* K) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ok = ok && isfinite(T[i]);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ok = ok && isfinite(K[i]);
-    return ok;
-}
-
 __global__ __launch_bounds__(256) void raster_clear_kernel(unsigned long long* __restrict__ zbuf, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) zbuf[i] = ~0ull;
@@ -62,13 +53,8 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
 // one pixel of one triangle: edge functions at the pixel centre, perspective-correct depth, 64-bit atomicMin of (depth | face)
 __device__ __forceinline__ void raster_pixel(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
                                              float inv_area, int f, int x, int y, int W, unsigned long long* zb) {
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const float w0 = edge_fn(bx, by, cx, cy, px, py) * inv_area;
-    const float w1 = edge_fn(cx, cy, ax, ay, px, py) * inv_area;
-    const float w2 = edge_fn(ax, ay, bx, by, px, py) * inv_area;
-    if (!(w0 >= 0.f && w1 >= 0.f && w2 >= 0.f)) return;
-    const float iz = (w0 / az + w1 / bz) + w2 / cz;
-    const float z = 1.f / iz;
+    float z;
+    if (!raster_pixel_depth(ax, ay, az, bx, by, bz, cx, cy, cz, inv_area, x, y, z)) return;
     const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned int)f;
     atomicMin(zb + (size_t)y * W + x, key);
 }
@@ -86,26 +72,10 @@ __global__ __launch_bounds__(256) void raster_tri_kernel(const float* __restrict
     const int o = obj[b];
     unsigned long long* zb = zbuf + (size_t)b * H * W;
     bool live = f < n_faces[o] && pose_finite(TCO + (size_t)b * 16, K + (size_t)b * 9);
-    float ax = 0.f, ay = 0.f, az = 1.f, bx = 0.f, by = 0.f, bz = 1.f, cx = 0.f, cy = 0.f, cz = 1.f, inv_area = 0.f;
-    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-    if (live) {
-        const int* tri = faces + ((size_t)o * F + f) * 3;
-        const float* base = uvz + (size_t)b * V * 3;
-        ax = base[tri[0] * 3]; ay = base[tri[0] * 3 + 1]; az = base[tri[0] * 3 + 2];
-        bx = base[tri[1] * 3]; by = base[tri[1] * 3 + 1]; bz = base[tri[1] * 3 + 2];
-        cx = base[tri[2] * 3]; cy = base[tri[2] * 3 + 1]; cz = base[tri[2] * 3 + 2];
-        const float near = 0.01f;
-        const float area = edge_fn(ax, ay, bx, by, cx, cy);
-        live = (az > near && bz > near && cz > near) && !(area == 0.f || !isfinite(area));
-        if (live) {
-            const float xmin = fminf(ax, fminf(bx, cx)), xmax = fmaxf(ax, fmaxf(bx, cx));
-            const float ymin = fminf(ay, fminf(by, cy)), ymax = fmaxf(ay, fmaxf(by, cy));
-            x0 = max((int)floorf(xmin - 0.5f), 0); y0 = max((int)floorf(ymin - 0.5f), 0);
-            x1 = min((int)ceilf(xmax - 0.5f), W - 1); y1 = min((int)ceilf(ymax - 0.5f), H - 1);
-            inv_area = 1.f / area;
-            live = x1 >= x0 && y1 >= y0;
-        }
-    }
+    RasterTri t{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0, -1, 0, -1};
+    if (live) live = raster_tri_setup(uvz + (size_t)b * V * 3, faces + ((size_t)o * F + f) * 3, H, W, t);
+    const float ax = t.ax, ay = t.ay, az = t.az, bx = t.bx, by = t.by, bz = t.bz, cx = t.cx, cy = t.cy, cz = t.cz, inv_area = t.inv_area;
+    const int x0 = t.x0, x1 = t.x1, y0 = t.y0, y1 = t.y1;
     const bool big = live && (long)(x1 - x0 + 1) * (y1 - y0 + 1) > BIG;
     if (live && !big) {
         for (int y = y0; y <= y1; ++y)

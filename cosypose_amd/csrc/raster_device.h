@@ -37,9 +37,58 @@ __device__ __forceinline__ float edge_fn(float ax, float ay, float bx, float by,
     return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
 }
 
-// colour (3, in [0,1]) and depth of pixel (x, y) of crop b given its z-buffer key; black / 0 for background
+// every entry of the pose and of the camera finite (bullet_batch_renderer.py:25-36 skips such poses: nothing is drawn)
+__device__ __forceinline__ bool pose_finite(const float* T, const float* K) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) ok = ok && isfinite(T[i]);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ok = ok && isfinite(K[i]);
+    return ok;
+}
+
+// One projected triangle of the z-buffer pass and its pixel box clipped to the frame.  Liveness: all three vertices beyond the near
+// plane 0.01, finite non-zero area, a box that meets the frame.
+struct RasterTri {
+    float ax, ay, az, bx, by, bz, cx, cy, cz, inv_area;
+    int x0, x1, y0, y1;
+};
+__device__ __forceinline__ bool raster_tri_setup(const float* __restrict__ base, const int* __restrict__ tri, int H, int W, RasterTri& t) {
+#pragma clang fp contract(off)
+    t.ax = base[tri[0] * 3]; t.ay = base[tri[0] * 3 + 1]; t.az = base[tri[0] * 3 + 2];
+    t.bx = base[tri[1] * 3]; t.by = base[tri[1] * 3 + 1]; t.bz = base[tri[1] * 3 + 2];
+    t.cx = base[tri[2] * 3]; t.cy = base[tri[2] * 3 + 1]; t.cz = base[tri[2] * 3 + 2];
+    const float near = 0.01f;
+    const float area = edge_fn(t.ax, t.ay, t.bx, t.by, t.cx, t.cy);
+    if (!((t.az > near && t.bz > near && t.cz > near) && !(area == 0.f || !isfinite(area)))) return false;
+    const float xmin = fminf(t.ax, fminf(t.bx, t.cx)), xmax = fmaxf(t.ax, fmaxf(t.bx, t.cx));
+    const float ymin = fminf(t.ay, fminf(t.by, t.cy)), ymax = fmaxf(t.ay, fmaxf(t.by, t.cy));
+    t.x0 = max((int)floorf(xmin - 0.5f), 0); t.y0 = max((int)floorf(ymin - 0.5f), 0);
+    t.x1 = min((int)ceilf(xmax - 0.5f), W - 1); t.y1 = min((int)ceilf(ymax - 0.5f), H - 1);
+    t.inv_area = 1.f / area;
+    return t.x1 >= t.x0 && t.y1 >= t.y0;
+}
+
+// one pixel of one triangle: edge functions at the pixel centre, perspective-correct depth; false when the centre is outside
+__device__ __forceinline__ bool raster_pixel_depth(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                   float inv_area, int x, int y, float& z) {
+#pragma clang fp contract(off)
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const float w0 = edge_fn(bx, by, cx, cy, px, py) * inv_area;
+    const float w1 = edge_fn(cx, cy, ax, ay, px, py) * inv_area;
+    const float w2 = edge_fn(ax, ay, bx, by, px, py) * inv_area;
+    if (!(w0 >= 0.f && w1 >= 0.f && w2 >= 0.f)) return false;
+    const float iz = (w0 / az + w1 / bz) + w2 / cz;
+    z = 1.f / iz;
+    return true;
+}
+
+// colour (3, in [0,1]) and depth of pixel (x, y) of crop b given its z-buffer key; black / 0 for background.  `flat_rgb` (3 floats, the
+// scene renderer's colour override) stands in for the colour of all three vertices and for the texel: the pixel is what a mesh of
+// that one vertex colour and no texture gives.
 __device__ __forceinline__ void resolve_pixel(unsigned long long key, const float* __restrict__ uvz_b, const MeshView& m, int o,
-                                              const float* __restrict__ T, int x, int y, const ShadeParams& sp, float* out, float& zo) {
+                                              const float* __restrict__ T, int x, int y, const ShadeParams& sp, float* out, float& zo,
+                                              const float* __restrict__ flat_rgb = nullptr) {
 #pragma clang fp contract(off)
     out[0] = out[1] = out[2] = 0.f; zo = 0.f;
     if (key == ~0ull) return;
@@ -109,11 +158,11 @@ __device__ __forceinline__ void resolve_pixel(unsigned long long key, const floa
         if (!sp.smooth) nh = fabsf(nh);
         spec = nh > 0.f ? sp.specular * powf(nh, sp.shininess) : 0.f;
     }
-    const float* ca = m.colors + ((size_t)o * m.V + i0) * 3;
-    const float* cb = m.colors + ((size_t)o * m.V + i1) * 3;
-    const float* cc = m.colors + ((size_t)o * m.V + i2) * 3;
+    const float* ca = flat_rgb ? flat_rgb : m.colors + ((size_t)o * m.V + i0) * 3;
+    const float* cb = flat_rgb ? flat_rgb : m.colors + ((size_t)o * m.V + i1) * 3;
+    const float* cc = flat_rgb ? flat_rgb : m.colors + ((size_t)o * m.V + i2) * 3;
     float texel[3] = {1.f, 1.f, 1.f};
-    if (m.tex && m.uvs) {
+    if (m.tex && m.uvs && !flat_rgb) {
         // bilinear, repeat wrap; texel centres at (i + 0.5) / size, v = 0 at the first row
         const float* ua = m.uvs + ((size_t)o * m.V + i0) * 2;
         const float* ub = m.uvs + ((size_t)o * m.V + i1) * 2;

@@ -81,6 +81,20 @@ FLAT = dict(ambient=0.6, diffuse=0.4, specular=0.0, shininess=1.0, light_dir=(0.
             quantize=False)
 
 
+def make_shade(shading='flat', ambient=None, diffuse=None, light_dir=None):
+    """The cosy_shade_t of a renderer (HipBatchRenderer and HipSceneRenderer share it): shading = 'flat', 'opengl' or a dict with the
+    keys of `OPENGL_LIKE`; ambient / diffuse / light_dir override single entries.  -> (Shade, the resolved table with a unit light)"""
+    cfg = dict(FLAT if shading == 'flat' else OPENGL_LIKE if shading == 'opengl' else shading)
+    for k, v in (('ambient', ambient), ('diffuse', diffuse), ('light_dir', light_dir)):
+        if v is not None:
+            cfg[k] = v
+    l = np.asarray(cfg['light_dir'], np.float64); l = l / np.linalg.norm(l)
+    cfg.update(ambient=float(cfg['ambient']), diffuse=float(cfg['diffuse']), light_dir=tuple(float(v) for v in l))
+    shade = Shade(cfg['ambient'], cfg['diffuse'], float(cfg['specular']), float(cfg['shininess']), (ctypes.c_float * 3)(*cfg['light_dir']),
+                  1 if cfg['light_frame'] == 'object' else 0, int(bool(cfg['smooth'])), int(bool(cfg['quantize'])))
+    return shade, cfg
+
+
 class HipBatchRenderer:
     """shading='flat' (round 1's model, default) or 'opengl' (PyBullet-like: smooth normals, texture, highlight, world-frame
     light, 8-bit output) or a dict with the keys of `OPENGL_LIKE`; ambient / diffuse / light_dir override single entries.
@@ -95,15 +109,8 @@ class HipBatchRenderer:
 
     def __init__(self, meshes, ambient=None, diffuse=None, light_dir=None, shading='flat'):
         self.meshes = meshes
-        cfg = dict(FLAT if shading == 'flat' else OPENGL_LIKE if shading == 'opengl' else shading)
-        for k, v in (('ambient', ambient), ('diffuse', diffuse), ('light_dir', light_dir)):
-            if v is not None:
-                cfg[k] = v
-        l = np.asarray(cfg['light_dir'], np.float64); l = l / np.linalg.norm(l)
-        self.ambient, self.diffuse = float(cfg['ambient']), float(cfg['diffuse'])
-        self.light = tuple(float(v) for v in l)
-        self.shade = Shade(self.ambient, self.diffuse, float(cfg['specular']), float(cfg['shininess']), (ctypes.c_float * 3)(*self.light),
-                           1 if cfg['light_frame'] == 'object' else 0, int(bool(cfg['smooth'])), int(bool(cfg['quantize'])))
+        self.shade, cfg = make_shade(shading, ambient, diffuse, light_dir)
+        self.ambient, self.diffuse, self.light = cfg['ambient'], cfg['diffuse'], cfg['light_dir']
         self._scratch = {}       # per HIP stream: renders issued on different streams may overlap
 
     def _prepare(self, obj_infos, TCO, K, H, W):

@@ -405,6 +405,39 @@ int cosy_render_crop_pack_to(void* x_nhwc8, int dtype, const cosy_mesh_t* mesh, 
                              const float* TCO, const float* K_crop, const float* frames_nhwc4, const int* im_id, const float* boxes_crop,
                              int B, int N, int h, int w, int H, int W, void* scratch, cosy_stream_t stream);
 
+/* ---- scene renderer: many object instances in many views, one shared z-buffer per view (interface of BulletSceneRenderer.render_scene,
+ * cosypose/rendering/bullet_scene_renderer.py:12-64; camera model, near plane, non-finite poses and shading as cosy_render_meshes_ex).
+ * A ROW is one object instance in one view: obj_id (N), view_id (N) in [0, n_views), TCO (N,4,4), optional color (N,4); K (n_views,3,3);
+ * one resolution H x W per call.  Rows may come in any order, a view may have no row.
+ *
+ * Z-buffer key, 64 bits:  depth bits (32) | slot (COSY_SCENE_SLOT_BITS = 10) | face id (COSY_SCENE_FACE_BITS = 22),
+ * slot = the row's rank among the rows of its view, in call order.  Per pixel the smaller depth wins; at equal depth bits the row that
+ * comes first in the call; then the smaller face id.  Hence at most COSY_SCENE_MAX_FACES = 2^22 faces per mesh (mesh->F) and
+ * COSY_SCENE_MAX_INSTANCES = 2^10 rows per view; a call outside either is refused before any launch.
+ *
+ * obj_id and view_id are HOST arrays (they are checked, ranked and uploaded by the call); background: 3 HOST floats.  Everything else is
+ * device memory.  color: a row with color[r][3] >= 0 is drawn in the flat colour color[r][0..2] in place of the mesh's vertex colours and
+ * texture (shading still applies; the alpha value itself is ignored); color[r][3] < 0, or color = NULL: the mesh's own colours.
+ * Outputs: rgb (n_views,3,H,W) in [0,1]; optional depth (n_views,H,W) metres; optional mask (n_views,H,W) int32 = the ROW INDEX of the
+ * winner.  Background pixels: the background colour, depth 0, mask -1.  Optional per-row statistics (all four pointers or none):
+ * px_count_all (N) int32 = pixels of the row's silhouette (covered by any of its live triangles, whatever is in front),
+ * px_count_visib (N) int32 = pixels the row wins, bbox_obj / bbox_visib (N,4) float32 = xyxy boxes of inclusive pixel indices of the two
+ * sets, (-1,-1,-1,-1) when empty.  Integer atomics only: equal inputs give equal bits.
+ * scratch: cosy_render_scene_scratch_bytes(N, n_views, mesh->V, H, W) bytes = [z-buffers (n_views,H,W) u64 | projected vertices (N,V,3) |
+ * id table (4 N + n_views + 1 int32) | silhouette bits (N, ceil(H W / 32)) u32 | statistics (N,10) int32], each padded to 32 bytes.  Do
+ * not share one scratch between streams.
+ * Limits (COSY_EINVAL, cosy_last_error() names the argument): 0 <= N, n_views <= 65535 (grid y); H, W > 0; with N > 0 obj_id, view_id,
+ * TCO, K non-null; with n_views > 0 background, rgb, scratch non-null.  N = 0 is legal: every view is background. */
+#define COSY_SCENE_FACE_BITS 22
+#define COSY_SCENE_SLOT_BITS (32 - COSY_SCENE_FACE_BITS)
+#define COSY_SCENE_MAX_FACES (1 << COSY_SCENE_FACE_BITS)
+#define COSY_SCENE_MAX_INSTANCES (1 << COSY_SCENE_SLOT_BITS)
+size_t cosy_render_scene_scratch_bytes(int N, int n_views, int V, int H, int W);
+int cosy_render_scene(const cosy_mesh_t* mesh, const cosy_shade_t* shade, const int* host_obj_id, const int* host_view_id, const float* TCO,
+                      const float* color, const float* K, int N, int n_views, int H, int W, const float* background, float* rgb, float* depth,
+                      int* mask, int* px_count_all, int* px_count_visib, float* bbox_obj, float* bbox_visib, void* scratch,
+                      cosy_stream_t stream);
+
 /* ---- scene-level bundle adjustment (cosypose/multiview/bundle_adjustment.py:164-222), ALL FLOAT64 ----
  * States are 9-D poses (ortho6d rotation, translation; transform_ops.py:54-64): TWO_9d (n_obj,9) of the objects, TCW_9d (n_views,9) of the
  * cameras.  Candidate c observes object cand_obj[c] in view cand_view[c] with pose cand_TCO[c] (n_cand,4,4); K (n_views,3,3).  Points and
