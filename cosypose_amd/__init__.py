@@ -34,4 +34,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'h_pose':
         from .pose_forward_loss import h_pose
         return h_pose
+    if name in ('augment_batch', 'draw_sample_params', 'pack_params'):
+        from . import augmentations
+        return getattr(augmentations, name)
     raise AttributeError(name)

@@ -99,6 +99,8 @@ _SIGNATURES = {
     'cosy_ransac_score': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P], _I),
     'cosy_ransac_best': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P],
                          _I),
+    'cosy_augment_workspace_bytes': ([_I, _I, _I], _SZ),
+    'cosy_augment_batch': ([_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _SZ, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -96,13 +96,16 @@ class DevicePrefetcher:
     are valid until the NEXT batch is requested (requesting batch j enqueues the upload of batch j+1 into the slot batch j-1 used, gated
     only on the work enqueued so far); a consumer that keeps them longer -- logging the previous batch during the next step -- must clone them.  Batches are shallow
     copies: the caller's objects keep their host tensors.  Host tensors should be page-locked (DataLoader(pin_memory=True)) --
-    pageable ones are uploaded synchronously by the runtime and only the ordering benefit remains."""
+    pageable ones are uploaded synchronously by the runtime and only the ordering benefit remains.
+    `transform`, when given, is called with every uploaded batch on the consumer's stream, after that stream has been made to wait for
+    the upload, and what it returns is handed out in the batch's place: the place of device-side augmentation
+    (cosypose_amd.augmentations.augment_batch; it may write into the batch's own tensors, which are the slot's)."""
     FIELDS = ('images', 'K', 'TCO', 'bboxes')
 
-    def __init__(self, batches, device=None, fields=FIELDS):
+    def __init__(self, batches, device=None, fields=FIELDS, transform=None):
         if not torch.cuda.is_available():
             raise RuntimeError('DevicePrefetcher uploads to an MI355X: no GPU visible')
-        self.batches, self.fields = batches, tuple(fields)
+        self.batches, self.fields, self.transform = batches, tuple(fields), transform
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self._slots, self._free = [{}, {}], [None, None]
@@ -159,6 +162,8 @@ class DevicePrefetcher:
             except StopIteration:
                 pass
             consumer.wait_event(ready)
+            if self.transform is not None:
+                batch = self.transform(batch)
             yield batch
             j += 1
 

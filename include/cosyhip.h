@@ -506,6 +506,29 @@ int cosy_ransac_best(const float* cand_poses, const int* cand_mesh, const float*
                      int n_min_inliers, int skip_hypothesis_0, const long long* hyp_dist_off, const float* dists_in, int* best_hyp,
                      int* n_matches, int* match_cand1, int* match_cand2, cosy_stream_t stream);
 
+/* ---- training augmentations of PoseDataset.get_data (cosypose/datasets/pose_dataset.py:82-87, datasets/augmentations.py:40-125), uint8 ----
+ * images / out (B,3,H,W) uint8, masks (B,H,W) uint8 or NULL, backgrounds (n_bg,3,H,W) uint8 or NULL, params (B) records:
+ *   bg      row of `backgrounds` pasted where masks == 0, or -1 (then masks / backgrounds are not read for this image);
+ *   flags   COSY_AUG_GATE: the Pillow chain runs (without it the image is only pasted); COSY_AUG_SHARPNESS / _CONTRAST / _BRIGHTNESS /
+ *           _COLOR: that ImageEnhance stage runs with its factor below; COSY_AUG_GRAY: the float32 grey conversion runs last;
+ *   k       GaussianBlur radius 1, 2 or 3 (read only under COSY_AUG_GATE, where the blur always runs).
+ * Every byte equals what Pillow 12 gives for the same record (DESIGN.md section 14 holds the arithmetic): integer box passes, float32
+ * products and sums each rounded on their own, an integer sum of L for Contrast's mean.  No floating-point atomics: equal inputs give
+ * equal bytes.  out may alias images (images is read by the first launch only, out is written by the last and by the images whose gate
+ * is off, point by point).  workspace: cosy_augment_workspace_bytes(B, H, W) bytes, 16-byte aligned; it holds the two intermediate
+ * batches and the per-image sums.  A bg outside [-1, n_bg) or a k outside 1..3 under the gate is refused on the device: the image is
+ * copied unchanged to out and nothing outside the tables is read (callers check their records on the host). */
+enum { COSY_AUG_GATE = 1, COSY_AUG_SHARPNESS = 2, COSY_AUG_CONTRAST = 4, COSY_AUG_BRIGHTNESS = 8, COSY_AUG_COLOR = 16, COSY_AUG_GRAY = 32 };
+typedef struct cosy_aug_params {
+    int bg, flags, k;
+    float sharpness, contrast, brightness, color;
+    int reserved; /* 32 bytes per record */
+} cosy_aug_params_t;
+size_t cosy_augment_workspace_bytes(int B, int H, int W);
+int cosy_augment_batch(const unsigned char* images, const unsigned char* masks, const unsigned char* backgrounds, int n_bg,
+                       const cosy_aug_params_t* params, int B, int H, int W, unsigned char* out, void* workspace, size_t workspace_bytes,
+                       cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
