@@ -31,6 +31,15 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'PoseErrorMeter':
         from .pose_meters import PoseErrorMeter
         return PoseErrorMeter
+    if name == 'BopModels':
+        from .bop_errors import BopModels
+        return BopModels
+    if name == 'bop_errors':      # the function and its module share the name: the module is callable (see its last lines)
+        import importlib
+        return importlib.import_module('.bop_errors', __name__)
+    if name == 'BopScoreMeter':
+        from .bop_meters import BopScoreMeter
+        return BopScoreMeter
     if name == 'h_pose':
         from .pose_forward_loss import h_pose
         return h_pose

@@ -101,6 +101,13 @@ _SIGNATURES = {
                          _I),
     'cosy_augment_workspace_bytes': ([_I, _I, _I], _SZ),
     'cosy_augment_batch': ([_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _SZ, _P], _I),
+    'cosy_bop_mssd_mspd_workspace_bytes': ([_I, _I], _SZ),
+    'cosy_bop_mssd_mspd': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P], _I),
+    'cosy_bop_instance_boxes': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    'cosy_bop_windows_workspace_bytes': ([_c.c_longlong], _SZ),
+    'cosy_bop_render_windows': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _P, _SZ, _P], _I),
+    'cosy_bop_vsd_workspace_bytes': ([_I], _SZ),
+    'cosy_bop_vsd_counts': ([_P, _P, _P, _P, _P, _P, _c.c_longlong, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

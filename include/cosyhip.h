@@ -529,6 +529,48 @@ int cosy_augment_batch(const unsigned char* images, const unsigned char* masks, 
                        const cosy_aug_params_t* params, int B, int H, int W, unsigned char* out, void* workspace, size_t workspace_bytes,
                        cosy_stream_t stream);
 
+/* ---- BOP pose errors (Hodan et al., "BOP Challenge 2020", section 2.2): MSSD, MSPD and the pixel counts of VSD, float32 ----
+ * A pair is one estimate TCO_pred, one ground truth TCO_gt, one object obj_id and one view view_id; lengths in metres, pixel
+ * coordinates are integer indices (no + 0.5), K (n_views,3,3) is per view.  Object tables: verts (n_obj,V,3) with n_verts (n_obj)
+ * used rows, sym_table (n_obj,S,4,4) with n_sym (n_obj) used rows (the identity first), faces (n_obj,F,3) with n_faces (n_obj).
+ * DESIGN.md section 15 states the arithmetic; every product and sum is rounded on its own (no contraction), nothing uses
+ * floating-point atomics: equal inputs give equal bits, and a pair's result does not depend on what else is in the call.
+ * All three steps check on the host, before any launch (COSY_EINVAL, cosy_last_error() names the argument): counts >= 0, table sizes
+ * and H, W > 0, every pointer that is read non-null, workspace 16-byte aligned and at least its *_workspace_bytes; B = 0 (N = 0)
+ * returns COSY_OK at once with null pointers.  Ids are device values and are checked there: an obj_id / view_id / instance id outside
+ * its table, or a non-finite entry in a pose or in the view's K, reads nothing and gives NaN errors, an empty box and zero counts;
+ * n_verts, n_sym and n_faces are clamped to [0, V], [0, S] and [0, F].
+ *
+ * Step 1.  mssd[b] = min over s < n_sym of max over x of |P_est x - P_gt S x|, mspd[b] the same on the projections
+ * (fx X / Z + cx, fy Y / Z + cy), Z not clamped.  The maxima are combined as integer maxima of float bit patterns.  B is bounded by
+ * B * ceil(V / 1024) * ceil(S / 8) < 2^31. */
+size_t cosy_bop_mssd_mspd_workspace_bytes(int B, int S);
+int cosy_bop_mssd_mspd(const float* TCO_pred, const float* TCO_gt, const int* obj_id, const int* view_id, const float* K, const float* verts,
+                       const int* n_verts, const float* sym_table, const int* n_sym, int B, int n_obj, int n_views, int V, int S, float* mssd,
+                       float* mspd, void* workspace, size_t workspace_bytes, cosy_stream_t stream);
+/* Step 2.  An instance is one (object, view, pose).  cosy_bop_instance_boxes: boxes (N,4) int32 = x0, y0, x1, y1 (inclusive) of the
+ * instance's vertices beyond the near plane, clipped to the (H,W) frame; empty (x1 < x0 or y1 < y0) when nothing can be drawn, with
+ * x1 = y1 = -2 for an instance whose ids lie outside the tables or whose pose or K is not finite (a pair with such an instance gets zero
+ * counts in step 3, whatever its other instance shows).  The
+ * caller reads the boxes, gives every non-empty box a window of (x1 - x0 + 1) (y1 - y0 + 1) floats at win_offset[n] (int64, in
+ * floats) of a store of n_pixels floats = the workspace, and calls cosy_bop_render_windows: window pixel (x - x0, y - y0) receives
+ * the depth cosy_render_meshes_ex writes at (x, y) of that instance's (H,W) depth image, bit for bit, 0 = background.  A window that
+ * does not fit its box or the store is skipped, never written past. */
+int cosy_bop_instance_boxes(const float* TCO, const int* obj_id, const int* view_id, const float* K, const float* verts, const int* n_verts,
+                            int N, int n_obj, int n_views, int V, int H, int W, int* boxes, cosy_stream_t stream);
+size_t cosy_bop_windows_workspace_bytes(long long n_pixels);
+int cosy_bop_render_windows(const float* TCO, const int* obj_id, const int* view_id, const float* K, const float* verts, const int* faces,
+                            const int* n_faces, const int* boxes, const long long* win_offset, int N, int n_obj, int n_views, int V, int F, int H,
+                            int W, long long n_pixels, void* workspace, size_t workspace_bytes, cosy_stream_t stream);
+/* Step 3.  Pair b compares the windows of instances est_inst[b] and gt_inst[b] (both of view inst_view[.]) with the measured depth
+ * depth_test (n_views,H,W), 0 = missing, over the union box of the two windows.  counts (B, 2 + n_tau) int32 = |U|, |I|, c_1..c_n_tau
+ * with taus (B,n_tau) absolute metres, 1 <= n_tau <= 16, delta the visibility tolerance in metres. */
+size_t cosy_bop_vsd_workspace_bytes(int B);
+int cosy_bop_vsd_counts(const int* est_inst, const int* gt_inst, const int* inst_view, const int* boxes, const long long* win_offset,
+                        const float* windows, long long n_pixels, const float* depth_test, const float* K, const float* taus, float delta, int B,
+                        int N, int n_views, int n_tau, int H, int W, int* counts, void* workspace, size_t workspace_bytes,
+                        cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
