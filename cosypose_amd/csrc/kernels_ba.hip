@@ -13,6 +13,7 @@
 // is off so that a value does not depend on which multiply-adds the compiler chose to fuse.  Every sum runs in a fixed order: two runs
 // on the same inputs give the same bits.
 #include "cosy_common.h"
+#include "reduce_device.h"
 
 #pragma clang fp contract(off)
 
@@ -30,17 +31,6 @@ constexpr int BA_SOLVE_THREADS = 1024;
 template <typename T> __device__ __forceinline__ T t_sqrt(T v);
 template <> __device__ __forceinline__ float t_sqrt<float>(float v) { return sqrtf(v); }
 template <> __device__ __forceinline__ double t_sqrt<double>(double v) { return sqrt(v); }
-
-// sum over the 256 threads of a workgroup in a fixed order (lanes by xor tree, then waves 0..3); total in every thread
-template <typename T>
-__device__ __forceinline__ T block_sum256(T v, T* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
 
 template <typename T>
 __device__ __forceinline__ void mat4_mul(const T* A, const T* B, T* C) {

@@ -2,7 +2,7 @@
 // (estimate, ground truth) pairs.  DESIGN.md section 15 holds the contract and the arithmetic; tests/bop_ref.py restates it in numpy.
 //
 // Step 1, MSSD + MSPD in one pass.  Work = a flat list of (pair, tile of BOP_TILE vertices, chunk of BOP_CH symmetries) items found
-// from a prefix sum of the pairs' item counts (the scheme of kernels_eval.hip): workgroups draw items from an integer counter, so
+// from a prefix sum of the pairs' item counts (the queue of work_items.h): workgroups draw items from an integer counter, so
 // the batch is no grid dimension and mixed mesh sizes keep the CUs busy.  Per item the chunk's ground-truth transforms P_gt S sit in
 // LDS, every thread transforms its vertices once by P_est and keeps, per symmetry of the chunk, the running maximum of the squared
 // 3-D and squared 2-D distance AS THE BIT PATTERN of a non-negative float.  Lanes, waves and tiles are combined by an integer max
@@ -11,9 +11,9 @@
 //
 // Step 2, depth windows.  An instance is one (object, view, pose).  bop_box_kernel finds the pixel box of its live projected
 // vertices clipped to the frame (integer min / max); the host sizes a packed store from the boxes; bop_zpass_kernel is the z-buffer
-// pass of kernels_raster.hip -- raster_tri_setup / raster_pixel_depth at FULL-FRAME pixel coordinates, minimum of the depth bits --
+// pass of kernels_raster.hip -- raster_walk of raster_device.h at FULL-FRAME pixel coordinates, minimum of the depth bits --
 // writing into the instance's window, so a window holds the bits the full-frame render has there.  The vertices are projected by the
-// triangle's own thread with the expression of raster_project_kernel: no (N, V, 3) table of projected vertices exists.
+// triangle's own thread with project_vertex of raster_device.h: no (N, V, 3) table of projected vertices exists.
 //
 // Step 3, VSD counts.  Work = a flat list of (pair, strip of VSD_STRIP pixels of the union box of the pair's two windows) items.
 // Per pixel: the three distances from the three depths, the visibility masks, |U|, |I| and the n_tau cost counts by ballots and
@@ -23,6 +23,7 @@
 #include <limits.h>
 #include "cosy_common.h"
 #include "raster_device.h"
+#include "work_items.h"
 
 #pragma clang fp contract(off)
 
@@ -36,13 +37,6 @@ constexpr int BOP_CH = 8;                    // symmetries per work item
 constexpr int BOP_GRID = 256 * 4;            // workgroups that draw items
 constexpr int VSD_STRIP = 256 * 8;           // pixels per work item of step 3
 constexpr int VSD_MAX_TAU = 16;
-
-struct BopPlan {      // head of a workspace
-    int total;        // number of items
-    int next;         // the item counter
-};
-
-size_t plan_bytes(int B) { return (sizeof(BopPlan) + ((size_t)B + 1) * sizeof(int) + 15) / 16 * 16; }
 
 // ---- step 1 ---------------------------------------------------------------------------------------------------------------------
 struct PairTables {
@@ -77,55 +71,16 @@ struct PairItems {
     }
 };
 
-// start[b] = number of items before row b (start[B] = total), by one workgroup: every thread sums a contiguous run of rows, the 256
-// run totals are scanned in LDS, every thread writes its run.  Also resets the item counter.
-template <class Items>
-__global__ __launch_bounds__(256) void bop_plan_kernel(Items items, int B, BopPlan* __restrict__ plan, int* __restrict__ start) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x, run = (B + 255) / 256;
-    const int b0 = min(B, tid * run), b1 = min(B, b0 + run);
-    int sum = 0;
-    for (int b = b0; b < b1; ++b) sum += items(b);
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {   // Hillis-Steele inclusive scan
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int at = part[tid] - sum;
-    for (int b = b0; b < b1; ++b) {
-        start[b] = at;
-        at += items(b);
-    }
-    if (tid == 255) { start[B] = part[255]; plan->total = part[255]; plan->next = 0; }
-}
-
-// the row of an item: the last b with start[b] <= item (rows without items share their successor's start)
-__device__ __forceinline__ int row_of_item(const int* __restrict__ start, int B, int item) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (start[mid] <= item) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ unsigned nonneg_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }     // a NaN stays a NaN and wins every max
 
-__global__ __launch_bounds__(256) void bop_dist_kernel(PairTables t, BopPlan* __restrict__ plan, const int* __restrict__ start,
+__global__ __launch_bounds__(256) void bop_dist_kernel(PairTables t, WorkPlan* __restrict__ plan, const int* __restrict__ start,
                                                        unsigned* __restrict__ maxbits) {
     __shared__ float M[BOP_CH][12];          // rows 0..2 of P_gt S per symmetry of the chunk
     __shared__ unsigned red[2 * BOP_CH];
-    __shared__ int item_s;
     const int tid = threadIdx.x;
     const int total = plan->total;
     for (;;) {
-        __syncthreads();                       // item_s, M and red of the previous item are no longer read
-        if (tid == 0) item_s = atomicAdd(&plan->next, 1);
-        __syncthreads();
-        const int item = item_s;
+        const int item = next_item(plan);      // (a barrier: M and red of the previous item are no longer read)
         if (item >= total) return;
         const int b = row_of_item(start, t.B, item);
         int nv, ns;
@@ -179,11 +134,7 @@ __global__ __launch_bounds__(256) void bop_dist_kernel(PairTables t, BopPlan* __
         }
 #pragma unroll
         for (int s = 0; s < BOP_CH; ++s) {
-#pragma unroll
-            for (int w = 32; w > 0; w >>= 1) {
-                m3[s] = max(m3[s], (unsigned)__shfl_xor((int)m3[s], w));
-                m2[s] = max(m2[s], (unsigned)__shfl_xor((int)m2[s], w));
-            }
+            m3[s] = wave_max(m3[s]); m2[s] = wave_max(m2[s]);
             if ((tid & 63) == 0 && s < nsc) { atomicMax(&red[2 * s], m3[s]); atomicMax(&red[2 * s + 1], m2[s]); }
         }
         __syncthreads();
@@ -226,16 +177,6 @@ __device__ __forceinline__ bool inst_live(const InstTables& t, int n) {
     return pose_finite(t.TCO + (size_t)n * 16, t.K + (size_t)v * 9);
 }
 
-// (u, v, z) of one vertex: the expression of raster_project_kernel
-__device__ __forceinline__ void project_vertex(const float* __restrict__ T, const float* __restrict__ Kv, const float* __restrict__ p, float* o) {
-    float c[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c[i] = ((T[i * 4] * p[0] + T[i * 4 + 1] * p[1]) + T[i * 4 + 2] * p[2]) + T[i * 4 + 3];
-    o[0] = Kv[0] * c[0] / c[2] + Kv[2];
-    o[1] = Kv[4] * c[1] / c[2] + Kv[5];
-    o[2] = c[2];
-}
-
 // empty boxes: x1 = y1 = -1 for an instance that can be drawn, BOX_DEAD for one that cannot (ids outside the tables, a non-finite pose or K):
 // a pair with such an instance has no pixels at all, whatever its other instance shows
 constexpr int BOX_DEAD = -2;
@@ -271,11 +212,7 @@ __global__ __launch_bounds__(256) void bop_box_kernel(InstTables t, const int* _
     }
     if (tid < 4) red[tid] = tid < 2 ? INT_MAX : -1;
     __syncthreads();
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) {
-        x0 = min(x0, __shfl_xor(x0, w)); y0 = min(y0, __shfl_xor(y0, w));
-        x1 = max(x1, __shfl_xor(x1, w)); y1 = max(y1, __shfl_xor(y1, w));
-    }
+    x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1);
     if ((tid & 63) == 0) { atomicMin(&red[0], x0); atomicMin(&red[1], y0); atomicMax(&red[2], x1); atomicMax(&red[3], y1); }
     __syncthreads();
     if (tid < 2) atomicMin(boxes + n * 4 + tid, red[tid]);
@@ -317,26 +254,18 @@ __device__ __forceinline__ long window_index(const Window& w, int x, int y) {
     return at < w.room ? w.off + at : -1;
 }
 
-__device__ __forceinline__ void window_pixel(const RasterTri& t, int x, int y, const Window& w, unsigned* __restrict__ store) {
-    float z;
-    if (!raster_pixel_depth(t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz, t.inv_area, x, y, z)) return;
-    const long at = window_index(w, x, y);
-    if (at >= 0) atomicMin(store + at, __float_as_uint(z));
-}
-
-// The z-buffer pass of raster_tri_kernel (kernels_raster.hip) on depth bits alone: one thread per (instance, triangle); triangles
-// whose pixel box holds more than 64 pixels are shared by the 64 lanes of the wave.
+// The z-buffer pass of the batch rasteriser (raster_walk of raster_device.h) on depth bits alone: one thread per (instance, triangle),
+// the three vertices projected on the spot, 32-bit atomicMin into the instance's window.
 __global__ __launch_bounds__(256) void bop_zpass_kernel(InstTables t, const int* __restrict__ faces, const int* __restrict__ n_faces, int F,
                                                         int tiles, int H, int W, const int* __restrict__ boxes,
                                                         const long long* __restrict__ win_offset, unsigned* __restrict__ store, long n_px) {
-    constexpr int BIG = 64;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles, lane = threadIdx.x & 63;
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
     if (!inst_live(t, n)) return;            // block-uniform
     const Window w = window_of(boxes, win_offset, n_px, n, H, W);
     if (w.bw == 0) return;                   // block-uniform
     const int o = t.obj_id[n], f = tile * 256 + threadIdx.x;
     bool live = f < min(max(n_faces[o], 0), F);
-    RasterTri tr{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0, -1, 0, -1};
+    RasterTri tr;
     if (live) {
         const int* tri = faces + ((size_t)o * F + f) * 3;
         float uvz[9];
@@ -350,27 +279,10 @@ __global__ __launch_bounds__(256) void bop_zpass_kernel(InstTables t, const int*
         }
         live = in_table && raster_tri_setup(uvz, idx, H, W, tr);
     }
-    const bool big = live && (long)(tr.x1 - tr.x0 + 1) * (tr.y1 - tr.y0 + 1) > BIG;
-    if (live && !big) {
-        for (int y = tr.y0; y <= tr.y1; ++y)
-            for (int x = tr.x0; x <= tr.x1; ++x) window_pixel(tr, x, y, w, store);
-    }
-    unsigned long long todo = __ballot(big);
-    while (todo) {                                   // wave-uniform loop over the wave's big triangles
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        auto bc = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); };
-        RasterTri u;
-        u.ax = bc(tr.ax); u.ay = bc(tr.ay); u.az = bc(tr.az); u.bx = bc(tr.bx); u.by = bc(tr.by); u.bz = bc(tr.bz);
-        u.cx = bc(tr.cx); u.cy = bc(tr.cy); u.cz = bc(tr.cz); u.inv_area = bc(tr.inv_area);
-        u.x0 = __builtin_amdgcn_readlane(tr.x0, src); u.x1 = __builtin_amdgcn_readlane(tr.x1, src);
-        u.y0 = __builtin_amdgcn_readlane(tr.y0, src); u.y1 = __builtin_amdgcn_readlane(tr.y1, src);
-        const int bw = u.x1 - u.x0 + 1, npx = bw * (u.y1 - u.y0 + 1);
-        for (int i = lane; i < npx; i += 64) {
-            const int yy = i / bw, xx = i - yy * bw;
-            window_pixel(u, u.x0 + xx, u.y0 + yy, w, store);
-        }
-    }
+    raster_walk(live, tr, f, [&](int, int x, int y, float z) {
+        const long at = window_index(w, x, y);
+        if (at >= 0) atomicMin(store + at, __float_as_uint(z));
+    });
 }
 
 // ---- step 3 ---------------------------------------------------------------------------------------------------------------------
@@ -435,17 +347,13 @@ __device__ __forceinline__ float depth_to_dist(float z, float xc, float yc, floa
     return sqrtf((X * X + Y * Y) + z * z);
 }
 
-__global__ __launch_bounds__(256) void bop_vsd_kernel(VsdTables t, const float* __restrict__ taus, int n_tau, float delta, BopPlan* __restrict__ plan,
+__global__ __launch_bounds__(256) void bop_vsd_kernel(VsdTables t, const float* __restrict__ taus, int n_tau, float delta, WorkPlan* __restrict__ plan,
                                                       const int* __restrict__ start, int* __restrict__ counts) {
     __shared__ int red[4][2 + VSD_MAX_TAU];
-    __shared__ int item_s;
     const int tid = threadIdx.x, wave = tid >> 6;
     const int total = plan->total;
     for (;;) {
-        __syncthreads();
-        if (tid == 0) item_s = atomicAdd(&plan->next, 1);
-        __syncthreads();
-        const int item = item_s;
+        const int item = next_item(plan);
         if (item >= total) return;
         const int b = row_of_item(start, t.B, item);
         Window we, wg;
@@ -507,7 +415,7 @@ extern "C" {
 
 size_t cosy_bop_mssd_mspd_workspace_bytes(int B, int S) {
     if (B <= 0 || S <= 0) return 0;
-    return plan_bytes(B) + (size_t)B * S * 2 * sizeof(unsigned);
+    return work_plan_bytes(B) + (size_t)B * S * 2 * sizeof(unsigned);
 }
 
 int cosy_bop_mssd_mspd(const float* TCO_pred, const float* TCO_gt, const int* obj_id, const int* view_id, const float* K, const float* verts,
@@ -528,12 +436,12 @@ int cosy_bop_mssd_mspd(const float* TCO_pred, const float* TCO_gt, const int* ob
     COSY_REQUIRE(workspace_bytes >= cosy_bop_mssd_mspd_workspace_bytes(B, S), "cosy_bop_mssd_mspd: workspace_bytes=%zu < %zu", workspace_bytes,
                  cosy_bop_mssd_mspd_workspace_bytes(B, S));
     COSY_REQUIRE(((uintptr_t)workspace & 15) == 0, "cosy_bop_mssd_mspd: workspace not 16-byte aligned");
-    BopPlan* plan = (BopPlan*)workspace;
+    WorkPlan* plan = (WorkPlan*)workspace;
     int* start = (int*)(plan + 1);
-    unsigned* maxbits = (unsigned*)((char*)workspace + plan_bytes(B));
+    unsigned* maxbits = (unsigned*)((char*)workspace + work_plan_bytes(B));
     const PairTables t{TCO_pred, TCO_gt, obj_id, view_id, K, verts, n_verts, sym_table, n_sym, B, n_obj, n_views, V, S};
     COSY_CHECK_HIP(hipMemsetAsync(maxbits, 0, (size_t)B * S * 2 * sizeof(unsigned), s));
-    hipLaunchKernelGGL(bop_plan_kernel<PairItems>, dim3(1), dim3(256), 0, s, PairItems{t}, B, plan, start);
+    hipLaunchKernelGGL(work_plan_kernel<PairItems>, dim3(1), dim3(256), 0, s, PairItems{t}, B, plan, start);
     COSY_CHECK_HIP(hipGetLastError());
     const long max_items = (long)B * per_pair;
     hipLaunchKernelGGL(bop_dist_kernel, dim3((unsigned)(max_items < BOP_GRID ? max_items : BOP_GRID)), dim3(256), 0, s, t, plan, (const int*)start,
@@ -595,7 +503,7 @@ int cosy_bop_render_windows(const float* TCO, const int* obj_id, const int* view
     return COSY_OK;
 }
 
-size_t cosy_bop_vsd_workspace_bytes(int B) { return B <= 0 ? 0 : plan_bytes(B); }
+size_t cosy_bop_vsd_workspace_bytes(int B) { return B <= 0 ? 0 : work_plan_bytes(B); }
 
 int cosy_bop_vsd_counts(const int* est_inst, const int* gt_inst, const int* inst_view, const int* boxes, const long long* win_offset,
                         const float* windows, long long n_pixels, const float* depth_test, const float* K, const float* taus, float delta, int B,
@@ -617,11 +525,11 @@ int cosy_bop_vsd_counts(const int* est_inst, const int* gt_inst, const int* inst
     COSY_REQUIRE(workspace_bytes >= cosy_bop_vsd_workspace_bytes(B), "cosy_bop_vsd_counts: workspace_bytes=%zu < %zu", workspace_bytes,
                  cosy_bop_vsd_workspace_bytes(B));
     COSY_REQUIRE(((uintptr_t)workspace & 15) == 0, "cosy_bop_vsd_counts: workspace not 16-byte aligned");
-    BopPlan* plan = (BopPlan*)workspace;
+    WorkPlan* plan = (WorkPlan*)workspace;
     int* start = (int*)(plan + 1);
     const VsdTables t{est_inst, gt_inst, inst_view, boxes, win_offset, windows, (long)n_pixels, depth_test, K, B, N, n_views, H, W};
     COSY_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * (2 + n_tau) * sizeof(int), s));
-    hipLaunchKernelGGL(bop_plan_kernel<VsdItems>, dim3(1), dim3(256), 0, s, VsdItems{t}, B, plan, start);
+    hipLaunchKernelGGL(work_plan_kernel<VsdItems>, dim3(1), dim3(256), 0, s, VsdItems{t}, B, plan, start);
     COSY_CHECK_HIP(hipGetLastError());
     const long max_items = (long)B * cdiv((long)H * W, VSD_STRIP);
     hipLaunchKernelGGL(bop_vsd_kernel, dim3((unsigned)(max_items < BOP_GRID ? max_items : BOP_GRID)), dim3(256), 0, s, t, taus, n_tau, delta, plan,

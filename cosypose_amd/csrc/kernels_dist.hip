@@ -10,24 +10,13 @@
 // follow the reference's tie rule: strict <, first index wins.
 #include "cosy_common.h"
 #include "dist_device.h"
+#include "reduce_device.h"
 
 #pragma clang fp contract(off)
 
 namespace cosy {
 
 namespace {
-
-// sum over the 256 threads of a workgroup in a fixed order: lanes by xor-shuffle tree, then waves 0..3 in sequence.
-// `scratch` = 4 floats of LDS per reduced value.  Returns the total in every thread.
-__device__ __forceinline__ float block_sum(float v, float* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();   // scratch may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
 
 // torch.min / argmin treat NaN as the smallest value: the first NaN wins and later values never replace it.
 // (A plain `c < best` would skip a NaN that is not the first candidate.)
@@ -64,8 +53,8 @@ __global__ __launch_bounds__(256) void symmetric_distance_kernel(const float* __
             sum_sq += sq;
             sum_n += sqrtf(sq);
         }
-        sum_n = block_sum(sum_n, red);
-        sum_sq = block_sum(sum_sq, red + 4);
+        sum_n = block_sum256(sum_n, red);
+        sum_sq = block_sum256(sum_sq, red + 4);
         const float c = mode == 0 ? sum_n / (float)P : sum_sq / (float)P;
         // mode 0 is the reference's C++ scan (strict <: a NaN stays only where it comes first), mode 1 its torch argmin
         if (best < 0 || (mode == 0 ? c < best_c : torch_min_takes(c, best_c))) { best = s; best_c = c; best_d = sum_n / (float)P; }
@@ -90,7 +79,7 @@ __device__ __forceinline__ void co_symmetric(const float* pred /*regs*/, const f
             xform_pt(g, x, y, z, q2);
             acc += fabsf(q1[0] - q2[0]); acc += fabsf(q1[1] - q2[1]); acc += fabsf(q1[2] - q2[2]);
         }
-        const float l = block_sum(acc, red) / (float)(3 * P);
+        const float l = block_sum256(acc, red) / (float)(3 * P);
         if (arg < 0 || torch_min_takes(l, loss)) { arg = s; loss = l; }
     }
 }
@@ -216,13 +205,7 @@ __global__ __launch_bounds__(256) void expand_ids_kernel(const int* __restrict__
     for (int base = 0; base < B; base += 256) {
         const int n = base + tid < B ? n_sym_item[base + tid] : 0;
         part[tid] = n;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {   // Hillis-Steele inclusive scan
-            const int v = tid >= o ? part[tid - o] : 0;
-            __syncthreads();
-            part[tid] += v;
-            __syncthreads();
-        }
+        block_scan256(part);
         const int start = carry + part[tid] - n;
         for (int k = 0; k < n; ++k) { ids_expand[start + k] = base + tid; sym_ids[start + k] = k; }
         __syncthreads();

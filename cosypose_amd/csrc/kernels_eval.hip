@@ -7,8 +7,8 @@
 // unconditionally (a NaN there stays).  No |g|^2 + |q|^2 - 2 g.q form.
 //
 // Work = a flat list of (candidate, tile of EVAL_TILE ground-truth points) items, found from a prefix sum of the candidates' tile
-// counts (eval_plan_kernel); workgroups draw items from an integer counter, so a batch of mixed mesh sizes keeps every CU busy and
-// B is not bounded by a grid dimension.  Which workgroup computes an item has no effect on the result: every item writes its own
+// counts (the queue of work_items.h); workgroups draw items from an integer counter, so a batch of mixed mesh sizes keeps every CU
+// busy and B is not bounded by a grid dimension.  Which workgroup computes an item has no effect on the result: every item writes its own
 // 4 float64 partial sums, summed within the workgroup in a fixed order (lane tree, then waves 0..3), and eval_final_kernel adds a
 // candidate's tiles in tile order.  No floating-point atomics; a candidate's result depends on its own pose and points only.
 //
@@ -19,6 +19,7 @@
 // the scan).
 #include "cosy_common.h"
 #include "dist_device.h"
+#include "work_items.h"
 
 #pragma clang fp contract(off)
 
@@ -31,11 +32,6 @@ constexpr int EVAL_TILE = 256 * EVAL_G;      // ground-truth points per work ite
 constexpr int EVAL_CHUNK = 2048;             // predicted points staged in LDS per pass (32 KB as float4)
 constexpr int EVAL_GRID = 256 * 4;           // workgroups that draw items: 4 per CU fit beside their 32 KB of LDS
 
-struct EvalPlan {     // head of the workspace
-    int total;        // number of items
-    int next;         // the item counter
-};
-
 __device__ __forceinline__ int eval_points_of(const int* __restrict__ obj_id, const int* __restrict__ n_points, int b, int n_obj, int n_max) {
     const int o = obj_id[b];
     if (o < 0 || o >= n_obj) return 0;                 // a row outside the table contributes nothing: its errors come out NaN
@@ -43,63 +39,26 @@ __device__ __forceinline__ int eval_points_of(const int* __restrict__ obj_id, co
     return n < 0 ? 0 : (n > n_max ? n_max : n);
 }
 
-// start[b] = number of items before candidate b (start[B] = total), by one workgroup: every thread sums a contiguous run of
-// candidates, the 256 run totals are scanned in LDS, every thread writes its run.  Also resets the item counter.
-__global__ __launch_bounds__(256) void eval_plan_kernel(const int* __restrict__ obj_id, const int* __restrict__ n_points, int B, int n_obj,
-                                                        int n_max, EvalPlan* __restrict__ plan, int* __restrict__ start) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x, run = (B + 255) / 256;
-    const int b0 = min(B, tid * run), b1 = min(B, b0 + run);
-    int sum = 0;
-    for (int b = b0; b < b1; ++b) sum += (eval_points_of(obj_id, n_points, b, n_obj, n_max) + EVAL_TILE - 1) / EVAL_TILE;
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {   // Hillis-Steele inclusive scan
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int at = part[tid] - sum;
-    for (int b = b0; b < b1; ++b) {
-        start[b] = at;
-        at += (eval_points_of(obj_id, n_points, b, n_obj, n_max) + EVAL_TILE - 1) / EVAL_TILE;
-    }
-    if (tid == 255) { start[B] = part[255]; plan->total = part[255]; plan->next = 0; }
-}
-
-// fixed-order float64 sum over the workgroup: lanes by xor-shuffle tree, then waves 0..3 in sequence; result valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
+struct EvalItems {    // tiles of a candidate
+    const int* obj_id;
+    const int* n_points;
+    int n_obj, n_max;
+    __device__ int operator()(int b) const { return (eval_points_of(obj_id, n_points, b, n_obj, n_max) + EVAL_TILE - 1) / EVAL_TILE; }
+};
 
 __global__ __launch_bounds__(256) void eval_tiles_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                          const int* __restrict__ obj_id, const int* __restrict__ mode,
                                                          const float* __restrict__ pts, const int* __restrict__ n_points, int B, int n_obj,
-                                                         int n_max, EvalPlan* __restrict__ plan, const int* __restrict__ start,
+                                                         int n_max, WorkPlan* __restrict__ plan, const int* __restrict__ start,
                                                          double* __restrict__ partial) {
     __shared__ float4 pp[EVAL_CHUNK];
     __shared__ double red[16];
-    __shared__ int item_s;
     const int tid = threadIdx.x;
     const int total = plan->total;
     for (;;) {
-        __syncthreads();                       // item_s, pp and red of the previous item are no longer read
-        if (tid == 0) item_s = atomicAdd(&plan->next, 1);
-        __syncthreads();
-        const int item = item_s;
+        const int item = next_item(plan);      // (a barrier: pp and red of the previous item are no longer read)
         if (item >= total) return;
-        // candidate of this item: the last b with start[b] <= item (candidates without points share their successor's start)
-        int lo = 0, hi = B;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (start[mid] <= item) lo = mid; else hi = mid;
-        }
-        const int b = lo, tile = item - start[b];
+        const int b = row_of_item(start, B, item), tile = item - start[b];
         const int P = eval_points_of(obj_id, n_points, b, n_obj, n_max);
         const float* p = pts + (size_t)obj_id[b] * n_max * 3;      // P > 0 here, so obj_id[b] is a row of the table
         const bool symmetric = mode[b] != 0;
@@ -169,12 +128,15 @@ __global__ __launch_bounds__(256) void eval_tiles_kernel(const float* __restrict
                 s[0] += (double)sqrtf((r[k][0] * r[k][0] + r[k][1] * r[k][1]) + r[k][2] * r[k][2]);
                 s[1] += (double)fabsf(r[k][0]); s[2] += (double)fabsf(r[k][1]); s[3] += (double)fabsf(r[k][2]);
             }
+        // fixed-order float64 sums over the workgroup, the order of block_sum256 without its leading barrier: the four sums use
+        // disjoint parts of red, and the barrier of next_item protects its reuse
 #pragma unroll
-        for (int c = 0; c < 4; ++c) s[c] = block_sum_f64(s[c], red + 4 * c);
-        if (tid == 0) {
-            double* o = partial + (size_t)item * 4;
-            o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3];
+        for (int c = 0; c < 4; ++c) {
+            s[c] = wave_sum(s[c]);
+            if ((tid & 63) == 0) red[4 * c + (tid >> 6)] = s[c];
         }
+        __syncthreads();
+        if (tid < 4) partial[(size_t)item * 4 + tid] = ((red[4 * tid] + red[4 * tid + 1]) + red[4 * tid + 2]) + red[4 * tid + 3];
     }
 }
 
@@ -199,8 +161,6 @@ __global__ __launch_bounds__(256) void eval_final_kernel(const float* __restrict
     e[7] = sqrtf((dx * dx + dy * dy) + dz * dz);
 }
 
-size_t eval_head_bytes(int B) { return (sizeof(EvalPlan) + ((size_t)B + 1) * sizeof(int) + 15) / 16 * 16; }
-
 }  // namespace
 
 }  // namespace cosy
@@ -211,7 +171,7 @@ extern "C" {
 
 size_t cosy_pose_errors_workspace_bytes(int B, int n_max) {
     if (B <= 0 || n_max <= 0) return 0;
-    return eval_head_bytes(B) + (size_t)B * cdiv(n_max, EVAL_TILE) * 4 * sizeof(double);
+    return work_plan_bytes(B) + (size_t)B * cdiv(n_max, EVAL_TILE) * 4 * sizeof(double);
 }
 
 int cosy_pose_errors(const float* TXO_pred, const float* TXO_gt, const int* obj_id, const int* mode, const float* pts_table,
@@ -229,10 +189,10 @@ int cosy_pose_errors(const float* TXO_pred, const float* TXO_gt, const int* obj_
     COSY_REQUIRE(workspace_bytes >= cosy_pose_errors_workspace_bytes(B, n_max), "cosy_pose_errors: workspace_bytes=%zu < %zu",
                  workspace_bytes, cosy_pose_errors_workspace_bytes(B, n_max));
     COSY_REQUIRE(((uintptr_t)workspace & 15) == 0, "cosy_pose_errors: workspace not 16-byte aligned");
-    EvalPlan* plan = (EvalPlan*)workspace;
+    WorkPlan* plan = (WorkPlan*)workspace;
     int* start = (int*)(plan + 1);
-    double* partial = (double*)((char*)workspace + eval_head_bytes(B));
-    hipLaunchKernelGGL(eval_plan_kernel, dim3(1), dim3(256), 0, s, obj_id, n_points, B, n_obj, n_max, plan, start);
+    double* partial = (double*)((char*)workspace + work_plan_bytes(B));
+    hipLaunchKernelGGL(work_plan_kernel<EvalItems>, dim3(1), dim3(256), 0, s, EvalItems{obj_id, n_points, n_obj, n_max}, B, plan, start);
     COSY_CHECK_HIP(hipGetLastError());
     const long max_items = (long)B * cdiv(n_max, EVAL_TILE);
     hipLaunchKernelGGL(eval_tiles_kernel, dim3((unsigned)(max_items < EVAL_GRID ? max_items : EVAL_GRID)), dim3(256), 0, s, TXO_pred, TXO_gt,

@@ -3,6 +3,7 @@
 // CPU oracle (oracle/cosy_oracle.c), which restates the reference's torch arithmetic.
 #include "cosy_common.h"
 #include "raster_device.h"
+#include "reduce_device.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -14,15 +15,6 @@ namespace cosy {
 // project_points_robust + boxes_from_uv (camera_geometry.py:18-42), deepim_boxes
 // (cropping.py:7-47), get_K_crop_resize (camera_geometry.py:45-87).
 // ----------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __device__ __forceinline__ void k_times_t(const float* K, const float* T, float* P) {
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 4; ++j) {
@@ -464,14 +456,6 @@ __global__ __launch_bounds__(256) void crop_pack_kernel(T* __restrict__ x, const
 // walked in 2 or 4 passes of fewer rows; tap entries wider than 4 pixels (bins above ~2.6) take the per-pixel path.
 // ----------------------------------------------------------------------------------------
 constexpr int CROP_TW = 64, CROP_TH = 16, CROP_LDS_PX = 2048;      // 32 KB of frame pixels (fp32 RGB + pad) per workgroup
-__device__ __forceinline__ int wave_min_i(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 template <typename T>
 __global__ __launch_bounds__(256, 4) void crop_pack_tile_kernel(T* __restrict__ x, const float* __restrict__ frames4,
                                                                 const int* __restrict__ im_id, const float* __restrict__ boxes,
@@ -493,7 +477,7 @@ __global__ __launch_bounds__(256, 4) void crop_pack_tile_kernel(T* __restrict__ 
     // instead -- a superset with a pixel of margin, so that the window's loads wait for no tap entry -- were measured SLOWER: 206 vs 180 us per
     // launch, the margins push more tiles over the LDS budget into two passes; profiles/r06_crop_tiled.txt)
     const bool xvalid = colok && tx.span >= 0;
-    const int xf = wave_min_i(xvalid ? tx.first : 0x7fffffff), xl = wave_max_i(xvalid ? tx.first + tx.span : -1);
+    const int xf = wave_min(xvalid ? tx.first : 0x7fffffff), xl = wave_max(xvalid ? tx.first + tx.span : -1);
     const bool xwide = __ballot(colok && tx.span >= 4) != 0;        // entries wider than 4 pixels: per-pixel path
     const int ncols = xl >= 0 ? xl - xf + 1 : 0;       // (no valid column in the tile: nothing is loaded, every pixel of it is zero)
     const float* bx = boxes + (size_t)b * 4;
@@ -511,7 +495,7 @@ __global__ __launch_bounds__(256, 4) void crop_pack_tile_kernel(T* __restrict__ 
         const bool rok = lane < rp && rq < PH;
         const CropTap tq = tb[min(rq, PH - 1)];
         const bool yvalid = rok && tq.span >= 0;
-        const int yf = wave_min_i(yvalid ? tq.first : 0x7fffffff), yl = wave_max_i(yvalid ? tq.first + tq.span : -1);
+        const int yf = wave_min(yvalid ? tq.first : 0x7fffffff), yl = wave_max(yvalid ? tq.first + tq.span : -1);
         const bool ywide = __ballot(rok && tq.span >= 4) != 0;
         const int nrows = yl >= 0 ? yl - yf + 1 : 0;
         const bool any = xl >= 0 && yl >= 0;                        // else: no valid sample in the pass -> zeros

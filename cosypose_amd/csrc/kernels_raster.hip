@@ -9,9 +9,9 @@
 //
 // Pipeline per call, all crops at once (meshes of a few 10^3..10^4 triangles, a few pixels each at crop resolution):
 //   1. project: one thread per (crop, vertex) -> (u, v, z_cam)
-//   2. z-buffer: one thread per (crop, triangle) walks the triangle's pixel bounding box (boxes of more than 64 pixels are
-//      shared by the 64 lanes of the wave); edge functions at pixel centres; 64-bit atomicMin of (depth bits << 32 | face
-//      id): order-independent, hence deterministic
+//   2. z-buffer: one thread per (crop, triangle) walks the triangle's pixel bounding box (raster_walk of raster_device.h: boxes
+//      of more than 64 pixels are shared by the 64 lanes of the wave); edge functions at pixel centres; 64-bit atomicMin of
+//      (depth bits << 32 | face id): order-independent, hence deterministic
 //   3. resolve: one thread per pixel re-derives the barycentrics of the winning face, perspective-correct colour
 //      interpolation, Lambert term from the camera-space face normal, clamps, writes planar RGB (+ depth).
 // Near plane, where this differs from OpenGL: a triangle with ANY vertex at z <= 0.01 is dropped whole (the z-buffer pass tests the
@@ -38,65 +38,23 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
                                                              float* __restrict__ uvz) {
     const int b = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
-    const float* T = TCO + (size_t)b * 16;
-    const float* Kb = K + (size_t)b * 9;
-    const float* p = verts + ((size_t)obj[b] * V + v) * 3;
-    float c[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c[i] = ((T[i * 4] * p[0] + T[i * 4 + 1] * p[1]) + T[i * 4 + 2] * p[2]) + T[i * 4 + 3];
-    float* o = uvz + ((size_t)b * V + v) * 3;
-    o[0] = Kb[0] * c[0] / c[2] + Kb[2];
-    o[1] = Kb[4] * c[1] / c[2] + Kb[5];
-    o[2] = c[2];
+    project_vertex(TCO + (size_t)b * 16, K + (size_t)b * 9, verts + ((size_t)obj[b] * V + v) * 3, uvz + ((size_t)b * V + v) * 3);
 }
 
-// one pixel of one triangle: edge functions at the pixel centre, perspective-correct depth, 64-bit atomicMin of (depth | face)
-__device__ __forceinline__ void raster_pixel(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                                             float inv_area, int f, int x, int y, int W, unsigned long long* zb) {
-    float z;
-    if (!raster_pixel_depth(ax, ay, az, bx, by, bz, cx, cy, cz, inv_area, x, y, z)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned int)f;
-    atomicMin(zb + (size_t)y * W + x, key);
-}
-
-// Triangles whose pixel box holds more than BIG pixels are not walked by their own thread (one thread per triangle serialises
-// a coarse mesh: a cube that fills a 256x256 crop is 12 triangles of ~10^4 pixels each): the wave takes them one after the
-// other (ballot + readlane broadcast of the triangle) and its 64 lanes share the box.  Same per-pixel arithmetic, and the
-// z-buffer merge is an order-independent min: results are identical to the one-thread walk.
+// one thread per (crop, triangle): the walk of raster_device.h, 64-bit atomicMin of (depth | face) into the crop's z-buffer
 __global__ __launch_bounds__(256) void raster_tri_kernel(const float* __restrict__ uvz, const int* __restrict__ faces,
                                                          const int* __restrict__ n_faces, const int* __restrict__ obj,
                                                          const float* __restrict__ TCO, const float* __restrict__ K, int V, int F, int H,
                                                          int W, unsigned long long* __restrict__ zbuf) {
-    constexpr int BIG = 64;
-    const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
     const int o = obj[b];
     unsigned long long* zb = zbuf + (size_t)b * H * W;
     bool live = f < n_faces[o] && pose_finite(TCO + (size_t)b * 16, K + (size_t)b * 9);
-    RasterTri t{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0, -1, 0, -1};
+    RasterTri t;
     if (live) live = raster_tri_setup(uvz + (size_t)b * V * 3, faces + ((size_t)o * F + f) * 3, H, W, t);
-    const float ax = t.ax, ay = t.ay, az = t.az, bx = t.bx, by = t.by, bz = t.bz, cx = t.cx, cy = t.cy, cz = t.cz, inv_area = t.inv_area;
-    const int x0 = t.x0, x1 = t.x1, y0 = t.y0, y1 = t.y1;
-    const bool big = live && (long)(x1 - x0 + 1) * (y1 - y0 + 1) > BIG;
-    if (live && !big) {
-        for (int y = y0; y <= y1; ++y)
-            for (int x = x0; x <= x1; ++x) raster_pixel(ax, ay, az, bx, by, bz, cx, cy, cz, inv_area, f, x, y, W, zb);
-    }
-    unsigned long long todo = __ballot(big);
-    while (todo) {                                   // wave-uniform loop over the wave's big triangles
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        auto bc = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); };
-        const float tax = bc(ax), tay = bc(ay), taz = bc(az), tbx = bc(bx), tby = bc(by), tbz = bc(bz), tcx = bc(cx), tcy = bc(cy), tcz = bc(cz);
-        const float tinv = bc(inv_area);
-        const int tx0 = __builtin_amdgcn_readlane(x0, src), tx1 = __builtin_amdgcn_readlane(x1, src);
-        const int ty0 = __builtin_amdgcn_readlane(y0, src), ty1 = __builtin_amdgcn_readlane(y1, src);
-        const int tf = __builtin_amdgcn_readlane(f, src);
-        const int bw = tx1 - tx0 + 1, npx = bw * (ty1 - ty0 + 1);
-        for (int i = lane; i < npx; i += 64) {
-            const int yy = i / bw, xx = i - yy * bw;
-            raster_pixel(tax, tay, taz, tbx, tby, tbz, tcx, tcy, tcz, tinv, tf, tx0 + xx, ty0 + yy, W, zb);
-        }
-    }
+    raster_walk(live, t, f, [&](int tf, int x, int y, float z) {
+        atomicMin(zb + (size_t)y * W + x, ((unsigned long long)__float_as_uint(z) << 32) | (unsigned int)tf);
+    });
 }
 
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const unsigned long long* __restrict__ zbuf, const float* __restrict__ uvz,

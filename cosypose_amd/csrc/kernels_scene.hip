@@ -7,8 +7,8 @@
 // Passes of one call:
 //   0. clear:   z-buffers to ~0, silhouette bits to 0, statistics to (0, empty box)
 //   1. project: one thread per (row, vertex), the batch rasteriser's expression, K of the row's view
-//   2. z-buffer: one thread per (row, triangle); liveness, pixel walk (boxes above 64 pixels shared by the wave) and per-pixel
-//      arithmetic are the batch rasteriser's (raster_device.h).  64-bit atomicMin into the VIEW's z-buffer of
+//   2. z-buffer: one thread per (row, triangle); liveness, pixel walk (raster_walk: boxes above 64 pixels shared by the wave) and
+//      per-pixel arithmetic are the batch rasteriser's (raster_device.h).  64-bit atomicMin into the VIEW's z-buffer of
 //          key = depth bits << 32 | slot << COSY_SCENE_FACE_BITS | face,
 //      slot = the row's rank among the rows of its view in call order: the smaller depth wins, at equal depth bits the row that
 //      comes first in the call, then the smaller face id.  An order-independent min: bit-reproducible.
@@ -25,6 +25,7 @@
 
 #include "cosy_common.h"
 #include "raster_device.h"
+#include "reduce_device.h"
 
 #pragma clang fp contract(off)
 
@@ -74,107 +75,63 @@ __global__ __launch_bounds__(256) void scene_project_kernel(const float* __restr
                                                             const float* __restrict__ K, int V, float* __restrict__ uvz) {
     const int r = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
-    const float* T = TCO + (size_t)r * 16;
-    const float* Kb = K + (size_t)view[r] * 9;
-    const float* p = verts + ((size_t)obj[r] * V + v) * 3;
-    float c[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c[i] = ((T[i * 4] * p[0] + T[i * 4 + 1] * p[1]) + T[i * 4 + 2] * p[2]) + T[i * 4 + 3];
-    float* o = uvz + ((size_t)r * V + v) * 3;
-    o[0] = Kb[0] * c[0] / c[2] + Kb[2];
-    o[1] = Kb[4] * c[1] / c[2] + Kb[5];
-    o[2] = c[2];
+    project_vertex(TCO + (size_t)r * 16, K + (size_t)view[r] * 9, verts + ((size_t)obj[r] * V + v) * 3, uvz + ((size_t)r * V + v) * 3);
 }
 
-// depth of one pixel of one triangle into the view's z-buffer; true when the pixel centre is covered
-__device__ __forceinline__ bool scene_pixel(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                                            float inv_area, unsigned low, int x, int y, int W, unsigned long long* zb) {
-    float z;
-    if (!raster_pixel_depth(ax, ay, az, bx, by, bz, cx, cy, cz, inv_area, x, y, z)) return false;
-    atomicMin(zb + (size_t)y * W + x, ((unsigned long long)__float_as_uint(z) << 32) | low);
-    return true;
-}
+// The silhouette of a row as the hook of raster_walk: one bit per covered pixel into the row's bit map `sb` (null: none is
+// recorded), without per-pixel atomics.
+struct Silhouette {
+    unsigned* sb;
+    int W;
+    int word = -1;
+    unsigned bits = 0u;                              // own walk: covered pixels of the current word of the bit map
+    __device__ __forceinline__ void thread_hit(int x, int y) {
+        const int p = y * W + x;
+        if ((p >> 5) != word) {
+            thread_row_end();
+            word = p >> 5;
+        }
+        bits |= 1u << (p & 31);
+    }
+    __device__ __forceinline__ void thread_row_end() {
+        if (bits && sb) atomicOr(sb + word, bits);
+        bits = 0u;
+    }
+    __device__ __forceinline__ void wave_step(bool in, bool hit, int x, int y, int xx, int bw) {
+        const int lane = threadIdx.x & 63;
+        const unsigned long long hits = __ballot(hit);
+        if (sb && hits && in) {
+            // Lanes lane, lane + 1, ... walk consecutive pixels of one box row: the first lane of each word of the bit map
+            // (lane 0, the first pixel of a box row, or a pixel index that is a multiple of 32) writes the bits of all of them
+            const int p = y * W + x;
+            if (lane == 0 || xx == 0 || (p & 31) == 0) {
+                const int run = min(min(bw - xx, 32 - (p & 31)), 64 - lane);
+                const unsigned bits = ((unsigned)(hits >> lane) & (run >= 32 ? ~0u : (1u << run) - 1u)) << (p & 31);
+                if (bits) atomicOr(sb + (p >> 5), bits);
+            }
+        }
+    }
+};
 
-// The walk of raster_tri_kernel with the row's view, slot and silhouette.  sil == nullptr: no silhouette is recorded.
+// one thread per (row, triangle): the walk of raster_device.h into the view's z-buffer, with the row's slot in the key and its
+// silhouette.  sil == nullptr: no silhouette is recorded.
 __global__ __launch_bounds__(256) void scene_tri_kernel(const float* __restrict__ uvz, const int* __restrict__ faces,
                                                         const int* __restrict__ n_faces, const int* __restrict__ obj,
                                                         const int* __restrict__ view, const int* __restrict__ slot,
                                                         const float* __restrict__ TCO, const float* __restrict__ K, int V, int F, int H, int W,
                                                         unsigned long long* __restrict__ zbuf, unsigned* __restrict__ sil, int words) {
-    constexpr int BIG = 64;
-    const int r = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int r = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
     const int o = obj[r], vw = view[r];
     unsigned long long* zb = zbuf + (size_t)vw * H * W;
-    unsigned* sb = sil ? sil + (size_t)r * words : nullptr;
     const unsigned slot_bits = (unsigned)slot[r] << FACE_BITS;
     bool live = f < n_faces[o] && pose_finite(TCO + (size_t)r * 16, K + (size_t)vw * 9);
-    RasterTri t{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0, -1, 0, -1};
+    RasterTri t;
     if (live) live = raster_tri_setup(uvz + (size_t)r * V * 3, faces + ((size_t)o * F + f) * 3, H, W, t);
-    const bool big = live && (long)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > BIG;
-    if (live && !big) {
-        const unsigned low = slot_bits | (unsigned)f;
-        for (int y = t.y0; y <= t.y1; ++y) {
-            int word = -1;
-            unsigned bits = 0u;                      // covered pixels of the current word of the bit map
-            for (int x = t.x0; x <= t.x1; ++x) {
-                if (!scene_pixel(t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz, t.inv_area, low, x, y, W, zb)) continue;
-                const int p = y * W + x;
-                if ((p >> 5) != word) {
-                    if (bits && sb) atomicOr(sb + word, bits);
-                    word = p >> 5; bits = 0u;
-                }
-                bits |= 1u << (p & 31);
-            }
-            if (bits && sb) atomicOr(sb + word, bits);
-        }
-    }
-    unsigned long long todo = __ballot(big);
-    while (todo) {                                   // wave-uniform loop over the wave's big triangles
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        auto bc = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); };
-        const float tax = bc(t.ax), tay = bc(t.ay), taz = bc(t.az), tbx = bc(t.bx), tby = bc(t.by), tbz = bc(t.bz), tcx = bc(t.cx), tcy = bc(t.cy),
-                    tcz = bc(t.cz);
-        const float tinv = bc(t.inv_area);
-        const int tx0 = __builtin_amdgcn_readlane(t.x0, src), tx1 = __builtin_amdgcn_readlane(t.x1, src);
-        const int ty0 = __builtin_amdgcn_readlane(t.y0, src), ty1 = __builtin_amdgcn_readlane(t.y1, src);
-        const unsigned low = slot_bits | (unsigned)__builtin_amdgcn_readlane(f, src);
-        const int bw = tx1 - tx0 + 1, npx = bw * (ty1 - ty0 + 1);
-        for (int base = 0; base < npx; base += 64) { // wave-uniform: every lane takes part in the ballot
-            const int i = base + lane;
-            const int yy = i / bw, xx = i - yy * bw;
-            const bool hit = i < npx && scene_pixel(tax, tay, taz, tbx, tby, tbz, tcx, tcy, tcz, tinv, low, tx0 + xx, ty0 + yy, W, zb);
-            const unsigned long long hits = __ballot(hit);
-            if (sb && hits && i < npx) {
-                // Lanes lane, lane + 1, ... walk consecutive pixels of one box row: the first lane of each word of the bit map
-                // (lane 0, the first pixel of a box row, or a pixel index that is a multiple of 32) writes the bits of all of them
-                const int p = (ty0 + yy) * W + tx0 + xx;
-                if (lane == 0 || xx == 0 || (p & 31) == 0) {
-                    const int run = min(min(bw - xx, 32 - (p & 31)), 64 - lane);
-                    const unsigned bits = ((unsigned)(hits >> lane) & (run >= 32 ? ~0u : (1u << run) - 1u)) << (p & 31);
-                    if (bits) atomicOr(sb + (p >> 5), bits);
-                }
-            }
-        }
-    }
+    raster_walk(live, t, f, [&](int tf, int x, int y, float z) {
+        atomicMin(zb + (size_t)y * W + x, ((unsigned long long)__float_as_uint(z) << 32) | slot_bits | (unsigned)tf);
+    }, Silhouette{sil ? sil + (size_t)r * words : nullptr, W});
 }
 
-// wave-wide integer reductions (butterfly; every lane of the wave takes part, lanes without a value pass the neutral element)
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 __device__ __forceinline__ void stat_box(int* box, int x0, int y0, int x1, int y1) {
     atomicMin(box, x0); atomicMin(box + 1, y0); atomicMax(box + 2, x1); atomicMax(box + 3, y1);
 }

@@ -13,6 +13,7 @@
 // (deterministic, no atomics).
 #include "cosy_common.h"
 #include "kernels_net.h"
+#include "reduce_device.h"
 #include <algorithm>
 
 namespace cosy {
@@ -968,14 +969,6 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------
 // gradient of loss_refiner_CO_disentangled wrt the network outputs (B,9)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum256(float v, float* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
 __device__ __forceinline__ void xform3(const float* T, float x, float y, float z, float* q) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) q[i] = T[i * 4 + 0] * x + T[i * 4 + 1] * y + T[i * 4 + 2] * z + T[i * 4 + 3];

@@ -1,5 +1,7 @@
-// Per-pixel resolve of the mesh rasteriser (shared by kernels_raster.hip and the fused render + crop kernel in
-// kernels_geom.hip).  fp32 with contraction off: oracle/cosy_oracle.c restates the same arithmetic in scalar loops.
+// Device code of the mesh rasterisers, each piece defined once: the vertex projection and the z-buffer walk of one triangle
+// (kernels_raster.hip, kernels_scene.hip, kernels_bop.hip) and the per-pixel resolve (kernels_raster.hip, kernels_scene.hip and the
+// fused render + crop kernel in kernels_geom.hip).  fp32 with contraction off, set inside every function because not every user is
+// built with it off: oracle/cosy_oracle.c restates the same arithmetic in scalar loops.
 #pragma once
 #include "cosy_common.h"
 
@@ -47,11 +49,22 @@ __device__ __forceinline__ bool pose_finite(const float* T, const float* K) {
     return ok;
 }
 
-// One projected triangle of the z-buffer pass and its pixel box clipped to the frame.  Liveness: all three vertices beyond the near
-// plane 0.01, finite non-zero area, a box that meets the frame.
+// (u, v, z_cam) of mesh vertex p under the pose T (4x4) and the camera K (3x3)
+__device__ __forceinline__ void project_vertex(const float* __restrict__ T, const float* __restrict__ K, const float* __restrict__ p, float* o) {
+#pragma clang fp contract(off)
+    float c[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c[i] = ((T[i * 4] * p[0] + T[i * 4 + 1] * p[1]) + T[i * 4 + 2] * p[2]) + T[i * 4 + 3];
+    o[0] = K[0] * c[0] / c[2] + K[2];
+    o[1] = K[4] * c[1] / c[2] + K[5];
+    o[2] = c[2];
+}
+
+// One projected triangle of the z-buffer pass and its pixel box clipped to the frame (as declared: no triangle, an empty box).
+// Liveness: all three vertices beyond the near plane 0.01, finite non-zero area, a box that meets the frame.
 struct RasterTri {
-    float ax, ay, az, bx, by, bz, cx, cy, cz, inv_area;
-    int x0, x1, y0, y1;
+    float ax = 0.f, ay = 0.f, az = 1.f, bx = 0.f, by = 0.f, bz = 1.f, cx = 0.f, cy = 0.f, cz = 1.f, inv_area = 0.f;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
 };
 __device__ __forceinline__ bool raster_tri_setup(const float* __restrict__ base, const int* __restrict__ tri, int H, int W, RasterTri& t) {
 #pragma clang fp contract(off)
@@ -70,17 +83,71 @@ __device__ __forceinline__ bool raster_tri_setup(const float* __restrict__ base,
 }
 
 // one pixel of one triangle: edge functions at the pixel centre, perspective-correct depth; false when the centre is outside
-__device__ __forceinline__ bool raster_pixel_depth(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                                                   float inv_area, int x, int y, float& z) {
+__device__ __forceinline__ bool raster_pixel_depth(const RasterTri& t, int x, int y, float& z) {
 #pragma clang fp contract(off)
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const float w0 = edge_fn(bx, by, cx, cy, px, py) * inv_area;
-    const float w1 = edge_fn(cx, cy, ax, ay, px, py) * inv_area;
-    const float w2 = edge_fn(ax, ay, bx, by, px, py) * inv_area;
+    const float w0 = edge_fn(t.bx, t.by, t.cx, t.cy, px, py) * t.inv_area;
+    const float w1 = edge_fn(t.cx, t.cy, t.ax, t.ay, px, py) * t.inv_area;
+    const float w2 = edge_fn(t.ax, t.ay, t.bx, t.by, px, py) * t.inv_area;
     if (!(w0 >= 0.f && w1 >= 0.f && w2 >= 0.f)) return false;
-    const float iz = (w0 / az + w1 / bz) + w2 / cz;
+    const float iz = (w0 / t.az + w1 / t.bz) + w2 / t.cz;
     z = 1.f / iz;
     return true;
+}
+
+// Triangles whose pixel box holds more than RASTER_BIG pixels are not walked by their own thread (one thread per triangle serialises
+// a coarse mesh: a cube that fills a 256x256 crop is 12 triangles of ~10^4 pixels each): the wave takes them one after the other
+// (ballot + raster_tri_of_lane) and its 64 lanes share the box.
+constexpr int RASTER_BIG = 64;
+__device__ __forceinline__ bool raster_tri_big(bool live, const RasterTri& t) {
+    return live && (long)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > RASTER_BIG;
+}
+// lane src's triangle in every lane of the wave
+__device__ __forceinline__ RasterTri raster_tri_of_lane(const RasterTri& t, int src) {
+    auto bci = [&](int v) { return __builtin_amdgcn_readlane(v, src); };
+    auto bc = [&](float v) { return __builtin_bit_cast(float, bci(__builtin_bit_cast(int, v))); };
+    return RasterTri{bc(t.ax), bc(t.ay), bc(t.az), bc(t.bx), bc(t.by), bc(t.bz), bc(t.cx), bc(t.cy), bc(t.cz), bc(t.inv_area),
+                     bci(t.x0), bci(t.x1), bci(t.y0), bci(t.y1)};
+}
+
+// What a walk reports beyond the depths of the covered pixels.  This one reports nothing and compiles away; kernels_scene.hip
+// records a silhouette with the same three calls.
+struct WalkNoHook {
+    __device__ __forceinline__ void thread_hit(int, int) {}                      // own walk: pixel (x, y) is covered
+    __device__ __forceinline__ void thread_row_end() {}                          // own walk: a row of the box is done
+    __device__ __forceinline__ void wave_step(bool, bool, int, int, int, int) {} // shared walk: all 64 lanes, once per 64 pixels
+};
+
+// The z-buffer walk of one triangle per thread: `live` and `t` from raster_tri_setup, `f` the triangle's face id; every thread of the
+// wave must make the call.  pixel(f, x, y, z) merges the depth of a covered pixel; the merge must not depend on the order (a min),
+// so that the thread's own walk and the wave-shared walk give the same result.
+template <class Pixel, class Hook = WalkNoHook>
+__device__ __forceinline__ void raster_walk(bool live, const RasterTri& t, int f, Pixel pixel, Hook hook = Hook()) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const bool big = raster_tri_big(live, t);
+    float z;
+    if (live && !big) {
+        for (int y = t.y0; y <= t.y1; ++y) {
+            for (int x = t.x0; x <= t.x1; ++x)
+                if (raster_pixel_depth(t, x, y, z)) { pixel(f, x, y, z); hook.thread_hit(x, y); }
+            hook.thread_row_end();
+        }
+    }
+    unsigned long long todo = __ballot(big);
+    while (todo) {                                   // wave-uniform loop over the wave's big triangles
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const RasterTri u = raster_tri_of_lane(t, src);
+        const int uf = __builtin_amdgcn_readlane(f, src), bw = u.x1 - u.x0 + 1, npx = bw * (u.y1 - u.y0 + 1);
+        for (int base = 0; base < npx; base += 64) { // wave-uniform: the hook may combine the 64 lanes
+            const int i = base + lane;
+            const int yy = i / bw, xx = i - yy * bw, x = u.x0 + xx, y = u.y0 + yy;
+            const bool hit = i < npx && raster_pixel_depth(u, x, y, z);
+            if (hit) pixel(uf, x, y, z);
+            hook.wave_step(i < npx, hit, x, y, xx, bw);
+        }
+    }
 }
 
 // colour (3, in [0,1]) and depth of pixel (x, y) of crop b given its z-buffer key; black / 0 for background.  `flat_rgb` (3 floats, the
