@@ -32,6 +32,20 @@ constexpr int RANSAC_MAX_TM = 4096;     // tentative matches per ordered view pa
 constexpr int RANSAC_THREADS = 128;     // ransac_score_kernel / ransac_best_kernel: the production scene averages 111 matches per hypothesis
 constexpr unsigned long long KEY_NONE = ~0ull;
 
+// Sort key of an inlier: (distance, list position).  The distance goes through the usual order-preserving float -> unsigned map
+// (negative: all bits flipped, otherwise: sign bit set), so that given distances below zero (the public find_ransac_inliers takes
+// any float) sort before the positive ones as the reference's `<` puts them; -0 is keyed as +0, which `<` ties with it, so that
+// the list position decides.  NaN never gets here (it fails dist <= thr); +inf maps to 0xff800000, below KEY_NONE.
+__device__ __forceinline__ unsigned long long sort_key(float dist, int i) {
+    const unsigned u = __float_as_uint(dist + 0.f);
+    const unsigned m = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)m << 32) | (unsigned)i;
+}
+__device__ __forceinline__ float key_dist(unsigned long long key) {
+    const unsigned m = (unsigned)(key >> 32);
+    return __uint_as_float((m & 0x80000000u) ? (m ^ 0x80000000u) : ~m);
+}
+
 struct RansacScene {
     const float* poses;      // (n_cand,4,4) TCO of every candidate
     const int* cand_mesh;    // (n_cand) row of the candidate's label in the tables
@@ -193,7 +207,7 @@ __device__ __forceinline__ Walk score_and_walk(const RansacScene& sc, const floa
             }
             if (dists_out) dists_out[i] = dist;
             const bool ok = (unsigned)m.z < (unsigned)n_tm && (unsigned)m.w < (unsigned)n_tm;
-            if (ok && dist <= thr) key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)i;     // dist >= +0: its bits order as it does
+            if (ok && dist <= thr) key = sort_key(dist, i);
         }
         keys[i] = key;
     }
@@ -221,7 +235,7 @@ __device__ __forceinline__ Walk score_and_walk(const RansacScene& sc, const floa
             if ((used1[m.z >> 5] & b1) || (used2[m.w >> 5] & b2)) continue;
             used1[m.z >> 5] |= b1; used2[m.w >> 5] |= b2;
             if (WRITE) { out_c1[w.n_inliers] = m.x; out_c2[w.n_inliers] = m.y; }
-            w.dists_sum += __uint_as_float((unsigned)(key >> 32));
+            w.dists_sum += dists_in ? dists_in[(unsigned)key] : key_dist(key);      // the stored distance where there is one
             w.n_inliers += 1;
         }
     }

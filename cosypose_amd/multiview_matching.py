@@ -167,7 +167,10 @@ class _Plan:
         for col, c in ((2, c1), (3, c2)):                       # rank of the candidate among the pair's candidates on that side
             _, rank = np.unique(pair_of * span + c, return_inverse=True)
             rank = np.asarray(rank).reshape(-1)
-            table[:, col] = rank - np.minimum.reduceat(rank, tm.pair_off[:-1])[pair_of] if len(rank) else rank
+            first = np.zeros(self.n_pairs, rank.dtype)              # a pair without matches (the last one too) has no rank to reduce
+            if len(rank):
+                first[sizes > 0] = np.minimum.reduceat(rank, tm.pair_off[:-1][sizes > 0])
+            table[:, col] = rank - first[pair_of]
         order = np.argsort(tm.hyp_pair, kind='stable')
         pair_hyp_off = np.concatenate([[0], np.cumsum(np.bincount(tm.hyp_pair, minlength=self.n_pairs))])
         self.hyp_off_host = tm.hyp_offsets()
