@@ -309,7 +309,8 @@ __global__ __launch_bounds__(BA_ROWS) void ba_linearize_kernel(const double* __r
 #pragma unroll
                 for (int i = 0; i < 9; ++i) J_view[gr * 9 + i] = row[9 + i];
             const double e2 = e * e;
-            loss_acc += e2 < threshold ? e2 : threshold;   // torch.min(residuals, threshold): the clamp enters the loss only
+            // torch.min(residuals, threshold): the clamp enters the loss only, and a NaN residual stays NaN (NaN > threshold is false)
+            loss_acc += e2 > threshold ? threshold : e2;
         } else {
 #pragma unroll
             for (int i = 0; i < BA_W; ++i) row[i] = 0.;

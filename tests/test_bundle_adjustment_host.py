@@ -1,6 +1,7 @@
 """Host side of the bundle adjustment (cosypose_amd/bundle_adjustment.py) against the reference's outputs in
 tests/golden/reference_golden_ba.npz (tests/golden/generate_golden_ba.py).  No GPU and no libcosyhip.so: the constructor and the
-initialisation walk are pandas / numpy code."""
+initialisation walk are pandas / numpy code.  Also pins tests/ba_ref.py, the float64 reference of the GPU tests, to the reference's
+stored autograd runs."""
 import pathlib
 
 import numpy as np
@@ -8,6 +9,7 @@ import pandas as pd
 import pytest
 import torch
 
+import ba_ref
 from cosypose_amd import bundle_adjustment as ba
 from cosypose_amd import synthetic as syn
 from cosypose_amd.mesh_db import BatchedMeshes
@@ -94,3 +96,43 @@ def test_sampler_error_for_a_view_without_pair_path(golden):
     p = ba.MultiviewRefinement(*syn.ba_scene_collections(scene, BatchedMeshes))
     with pytest.raises(ba.SamplerError):
         p.sample_initial_TWO_TWC(0)
+
+
+GOLDEN_JAC = GOLDEN.with_name('reference_golden_ba_jac.npz')
+LIN_CEILING = 1e-9       # as in test_bundle_adjustment.py: anything above is not float64 in another order
+# 10 x the worst max |got - want| / max |want| of ba_ref against the stored runs over the six states: errors 8.5e-14, loss 8.6e-15,
+# J_TWO / J_TCW 4.7e-16, align distances 4.9e-15
+REF_TOL = dict(errors=8.5e-13, loss=8.6e-14, J_TWO=4.7e-15, J_TCW=4.7e-15, align_dists=4.9e-14)
+
+
+@pytest.mark.parametrize('prefix,tag', [(s, tag) for s in ('s1_', 's2_', 's4_') for tag in ('init', 'final')])
+def test_ba_ref_vs_stored_autograd_runs(golden, prefix, tag):
+    """tests/ba_ref.py, the float64 reference that tests/test_ba_kernels.py holds the kernels to, against the reference project's own
+    stored float64 autograd runs at the initial and final states of scenes 1, 2, 4: errors, loss, the compact Jacobian, and at the
+    initial states (where they are stored) the align distances and chosen symmetries.  A wrong reference cannot hide a wrong kernel."""
+    g = dict(golden)
+    g.update(np.load(GOLDEN_JAC, allow_pickle=False))
+    r = ba_ref.reference(g[f'{prefix}TWO_9d_{tag}'], g[f'{prefix}TCW_9d_{tag}'], g[prefix + 'in_cand_poses'], g[prefix + 'in_cam_K'],
+                         g[prefix + 'obj_ids'], g[prefix + 'view_ids'], g[prefix + 'in_cand_label_id'], g[prefix + 'objinfo_label'],
+                         g[prefix + 'in_pts'], g[prefix + 'in_sym'], g[prefix + 'in_n_sym'], 25)
+
+    def rel(got, want):
+        return float(np.abs(np.asarray(got) - want).max() / np.abs(want).max())
+    figs = {k: rel(r[k], g[f'{prefix}{tag}_{k}']) for k in ('errors', 'loss', 'J_TWO', 'J_TCW')}
+    if tag == 'init':
+        figs['align_dists'] = rel(r['dists'][np.arange(len(r['best'])), r['best']], g[prefix + 'align_dists'])
+        assert np.array_equal(r['best'], g[prefix + 'align_sym'])
+        assert rel(r['aligned'], g[prefix + 'align_TCO']) < LIN_CEILING
+        assert r['margin'].min() >= 1e-3                     # the fixture generator's own rule
+    print(f'FIGURE ba_ref vs stored run {prefix}{tag}', figs)
+    for k, v in figs.items():
+        assert v <= min(REF_TOL[k], LIN_CEILING), figs
+    # the dense forms are the compact ones scattered: A and b from them
+    J, e = r['J'], r['errors']
+    assert J.shape == (len(e), 9 * (len(g[prefix + 'objinfo_obj_id']) + len(g[prefix + 'in_cam_view_id'])))
+    rows, per_cand = np.arange(len(e))[:, None], len(e) // len(g[prefix + 'obj_ids'])
+    cols_o = np.repeat(g[prefix + 'obj_ids'], per_cand)[:, None] * 9 + np.arange(9)
+    cols_v = (len(g[prefix + 'objinfo_obj_id']) + np.repeat(g[prefix + 'view_ids'], per_cand))[:, None] * 9 + np.arange(9)
+    assert np.array_equal(J[rows, cols_o], r['J_TWO']) and np.array_equal(J[rows, cols_v], r['J_TCW'])
+    assert np.count_nonzero(J) == np.count_nonzero(r['J_TWO']) + np.count_nonzero(r['J_TCW'])
+    assert rel(r['A'], J.T @ J) < 1e-14 and np.abs(r['b'] - J.T @ e).max() <= 1e-14 * np.abs(r['b_scale']).max()
