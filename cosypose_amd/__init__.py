@@ -46,4 +46,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('augment_batch', 'draw_sample_params', 'pack_params'):
         from . import augmentations
         return getattr(augmentations, name)
+    if name in ('DetectionMeter', 'box_iou', 'box_iou_pairs'):
+        from . import detection_meters
+        return getattr(detection_meters, name)
+    if name in ('mask_instance_stats', 'make_detections_from_segmentation', 'visible_ids', 'instance_masks', 'detection_targets'):
+        from . import mask_ops
+        return getattr(mask_ops, name)
     raise AttributeError(name)

@@ -8,6 +8,7 @@ import os
 from .build import LIB
 
 COSY_F32, COSY_BF16, COSY_F16 = 0, 1, 2
+COSY_MASK_U8, COSY_MASK_I32 = 0, 1
 _lib = None
 
 _c = ctypes
@@ -108,6 +109,10 @@ _SIGNATURES = {
     'cosy_bop_render_windows': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _P, _SZ, _P], _I),
     'cosy_bop_vsd_workspace_bytes': ([_I], _SZ),
     'cosy_bop_vsd_counts': ([_P, _P, _P, _P, _P, _P, _c.c_longlong, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P], _I),
+    'cosy_mask_instance_stats': ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    'cosy_instance_masks': ([_P, _I, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    'cosy_box_iou_pairs': ([_P, _P, _I, _P, _P], _I),
+    'cosy_box_iou_matrix': ([_P, _P, _I, _I, _P, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

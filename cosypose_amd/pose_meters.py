@@ -196,16 +196,16 @@ def _vector_column(array):
     return col
 
 
-def _left_fill(left, right, on, names):
+def _left_fill(left, right, on, names, fill_values=FILL_VALUES):
     """xr_merge (utils/xarray.py:4-42) for frames: the columns `names` of `right` brought to the rows of `left` that share `on` (at
-    most one row of `right` each), the other rows filled by FILL_VALUES; dtypes as the reference's: that of the fill value."""
+    most one row of `right` each), the other rows filled by fill_values; dtypes as the reference's: that of the fill value."""
     idx = left[on].merge(right[on].assign(_idx2=np.arange(len(right))), on=on, how='left')['_idx2'].values.astype(np.float64)
     assert len(idx) == len(left), 'more than one match for a row'
     has = np.isfinite(idx)
     src = idx[has].astype(int)
     out = {}
     for k in names:
-        fill = FILL_VALUES.get(k, float('nan'))
+        fill = fill_values.get(k, float('nan'))
         if k in VECTOR_SHAPES:
             arr = np.empty((len(left),) + VECTOR_SHAPES[k], dtype=np.array(fill).dtype)
             arr[:] = fill

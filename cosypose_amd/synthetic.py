@@ -343,3 +343,77 @@ def make_eval_scene(seed, labels, infos, scene_ids=(3, 7), n_views=3):
                 gt_visib_fract=np.array([g[3] for g in gt]), gt_poses=np.stack([g[4] for g in gt]).astype(np.float32),
                 pred_scene_id=np.array([p[0] for p in pred]), pred_view_id=np.array([p[1] for p in pred]),
                 pred_label=np.array([p[2] for p in pred]), pred_score=score, pred_poses=np.stack([p[3] for p in pred]).astype(np.float32))
+
+
+# ---- detection scenes for the detection meter (cosypose_amd/detection_meters.py) and instance masks (cosypose_amd/mask_ops.py) -------
+def make_det_scene(seed, n_labels=6, scene_ids=(3, 7), n_views=3):
+    """Ground-truth and predicted boxes of a few views for the detection meter -> dict of columns (numpy): gt_scene_id, gt_view_id,
+    gt_label (index below n_labels), gt_visib_fract, gt_bboxes (n,4) float32 xyxy; pred_scene_id, pred_view_id, pred_label,
+    pred_score (all different), pred_bboxes.  One to three instances of a label per view, all around one base box (so the boxes of
+    a (scene, view, label) group overlap one another); a prediction per ground truth with probability 0.85, jittered by up to 1 % /
+    5 % / 15 % / 30 % of the box size, sometimes a duplicate of it, plus false positives near the group, predictions of labels that
+    are not in the view and one in a view without ground truth.  The LAST label has one instance per view and predictions shifted by
+    30-40 % of the box along both axes: it never has a true positive at an IoU threshold of 0.5."""
+    rs = np.random.RandomState(seed)
+    gt, pred = [], []
+
+    def moved(box, shift, scale):
+        cx, cy, w, h = (box[0] + box[2]) / 2, (box[1] + box[3]) / 2, box[2] - box[0], box[3] - box[1]
+        cx, cy = cx + shift[0] * w, cy + shift[1] * h
+        w, h = w * scale[0], h * scale[1]
+        return np.array([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2])
+
+    for scene_id in scene_ids:
+        for view_id in range(n_views):
+            present = rs.permutation(n_labels - 1)[:rs.randint(3, n_labels)].tolist() + [n_labels - 1]
+            for l in present:
+                w, h = rs.uniform(60, 160, 2)
+                x, y = rs.uniform(0, 640 - w), rs.uniform(0, 480 - h)
+                base = np.array([x, y, x + w, y + h])
+                if l == n_labels - 1:
+                    gt.append((scene_id, view_id, l, rs.uniform(0.05, 1.0), base))
+                    sign = rs.choice([-1., 1.], 2)
+                    pred.append((scene_id, view_id, l, moved(base, sign * rs.uniform(0.3, 0.4, 2), (1., 1.))))
+                    continue
+                for inst in range(rs.randint(1, 4)):
+                    box = moved(base, rs.uniform(-0.2, 0.2, 2), rs.uniform(0.9, 1.1, 2)) if inst else base
+                    gt.append((scene_id, view_id, l, rs.uniform(0.05, 1.0), box))
+                    if rs.uniform() < 0.85:
+                        level = (0.01, 0.05, 0.15, 0.3)[rs.randint(4)]
+                        pred.append((scene_id, view_id, l, moved(box, rs.uniform(-level, level, 2), 1 + rs.uniform(-level, level, 2) / 3)))
+                        if rs.uniform() < 0.25:      # a duplicate detection of the same object
+                            pred.append((scene_id, view_id, l, moved(box, rs.uniform(-0.05, 0.05, 2), 1 + rs.uniform(-0.02, 0.02, 2))))
+                if rs.uniform() < 0.4:               # a false positive near the group
+                    pred.append((scene_id, view_id, l, moved(base, rs.uniform(-0.4, 0.4, 2), rs.uniform(0.9, 1.1, 2))))
+            absent = [l for l in range(n_labels) if l not in present]
+            if absent:                               # a label the view does not hold
+                pred.append((scene_id, view_id, absent[0], np.array([10., 10., 90., 70.]) + rs.uniform(0, 300)))
+    pred.append((scene_ids[0], n_views + 5, 0, np.array([20., 30., 120., 140.])))      # a view without ground truth
+    order = rs.permutation(len(pred))
+    pred = [pred[n] for n in order]
+    score = rs.permutation(len(pred)).astype(np.float64) / len(pred) * 0.9 + 0.05
+    return dict(gt_scene_id=np.array([g[0] for g in gt]), gt_view_id=np.array([g[1] for g in gt]), gt_label=np.array([g[2] for g in gt]),
+                gt_visib_fract=np.array([g[3] for g in gt]), gt_bboxes=np.stack([g[4] for g in gt]).astype(np.float32),
+                pred_scene_id=np.array([p[0] for p in pred]), pred_view_id=np.array([p[1] for p in pred]),
+                pred_label=np.array([p[2] for p in pred]), pred_score=score, pred_bboxes=np.stack([p[3] for p in pred]).astype(np.float32))
+
+
+def make_instance_masks(seed, B, H, W, n_inst):
+    """(B,H,W) uint8 instance-id masks: background 0, then instances 1..n_inst drawn in that order (a later one covers an earlier one),
+    alternately axis-aligned rectangles and ellipses of random place and size; some end up partly or wholly covered, some cut by the frame."""
+    rs = np.random.RandomState(seed)
+    masks = np.zeros((B, H, W), dtype=np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for b in range(B):
+        for n in range(1, n_inst + 1):
+            cx, cy = rs.uniform(0, W), rs.uniform(0, H)
+            rx, ry = rs.uniform(0.02, 0.2) * W + 0.5, rs.uniform(0.02, 0.2) * H + 0.5
+            x0, x1 = max(int(cx - rx), 0), min(int(cx + rx) + 1, W)
+            y0, y1 = max(int(cy - ry), 0), min(int(cy + ry) + 1, H)
+            if n % 2:
+                masks[b, y0:y1, x0:x1] = n
+            else:
+                win = (slice(y0, y1), slice(x0, x1))
+                inside = ((xx[win] - cx) / rx) ** 2 + ((yy[win] - cy) / ry) ** 2 <= 1.
+                masks[b][win][inside] = n
+    return masks

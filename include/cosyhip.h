@@ -571,6 +571,29 @@ int cosy_bop_vsd_counts(const int* est_inst, const int* gt_inst, const int* inst
                         int N, int n_views, int n_tau, int H, int W, int* counts, void* workspace, size_t workspace_bytes,
                         cosy_stream_t stream);
 
+/* ---- detection side: instance-id masks -> counts, boxes and binary masks; box IoU (cosypose/datasets/utils.py:27-40,
+ * datasets/detection_dataset.py:61-80, evaluation/meters/detection_meters.py:31-35) ----
+ * masks (B,H,W) of uint8 (COSY_MASK_U8) or int32 (COSY_MASK_I32), contiguous; the base address needs the element's alignment only and
+ * W may be odd.  All four functions check on the host, before any launch (COSY_EINVAL, cosy_last_error() names the argument): counts
+ * >= 0, H, W > 0 with H W < 2^30, n_ids in [1, 1024], B and N of the mask functions <= 65535, every pointer that is read non-null;
+ * B = 0 (N = 0) returns COSY_OK at once with null pointers.  Nothing is allocated; every output is written in full.
+ *
+ * cosy_mask_instance_stats: stats (B,n_ids,5) int32 = count, x1, y1, x2, y2 of the pixels that hold id i: inclusive pixel indices,
+ * the np.min / np.max of np.where; an absent id gives 0, -1, -1, -1, -1.  A pixel whose value lies outside [0, n_ids) is skipped (the
+ * scene renderer's -1 background).  Integer atomics only: equal inputs give equal bytes, whatever else is in the batch. */
+enum { COSY_MASK_U8 = 0, COSY_MASK_I32 = 1 };
+int cosy_mask_instance_stats(const void* masks, int dtype, int B, int H, int W, int n_ids, int* stats, cosy_stream_t stream);
+/* out (N,H,W) uint8: out[n] = masks[row_image[n]] == row_id[n] (1 or 0); row_image, row_id (N) int32 on the device.  A row whose image
+ * index lies outside [0, B) is written as zeros and reads nothing. */
+int cosy_instance_masks(const void* masks, int dtype, const int* row_image, const int* row_id, int B, int H, int W, int N, unsigned char* out,
+                        cosy_stream_t stream);
+/* xyxy boxes, float32: a, b (N,4) -> iou (N); a (N,4), b (M,4) -> iou (N,M), N M < 2^39.  torchvision.ops.box_iou's arithmetic, every
+ * operation rounded to float32 on its own: area = (x2 - x1) (y2 - y1); w = max(min(ax2, bx2) - max(ax1, bx1), 0), h likewise;
+ * inter = w h; iou = inter / ((area_a + area_b) - inter).  max, min and the clamp propagate NaN as torch's do, nothing is special-cased:
+ * two zero-area boxes at one point give 0 / 0 = NaN, inverted boxes follow the formula. */
+int cosy_box_iou_pairs(const float* a, const float* b, int N, float* iou, cosy_stream_t stream);
+int cosy_box_iou_matrix(const float* a, const float* b, int N, int M, float* iou, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
