@@ -46,6 +46,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('augment_batch', 'draw_sample_params', 'pack_params'):
         from . import augmentations
         return getattr(augmentations, name)
+    if name == 'resize_images':
+        from .resize import resize_images
+        return resize_images
     if name in ('DetectionMeter', 'box_iou', 'box_iou_pairs'):
         from . import detection_meters
         return getattr(detection_meters, name)

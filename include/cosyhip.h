@@ -594,6 +594,39 @@ int cosy_instance_masks(const void* masks, int dtype, const int* row_image, cons
 int cosy_box_iou_pairs(const float* a, const float* b, int N, float* iou, cosy_stream_t stream);
 int cosy_box_iou_matrix(const float* a, const float* b, int N, int M, float* iou, cosy_stream_t stream);
 
+/* ---- Pillow 12's Image.resize of 8-bit images, bilinear and bicubic (BackgroundAugmentation.__call__, cosypose/datasets/
+ * augmentations.py:120-124: im_bg.resize((w, h)) of a background of any size), uint8, byte for byte ----
+ * DESIGN.md section 17 holds the arithmetic.  An axis of input length `in` and output length `out` has a table of bounds
+ * (out,2) int32 = xmin, xmax (first tap and number of taps of every output index) and of coefficients (out,ksize) int32 in 2^-22,
+ * computed in double on the HOST by cosy_resize_coeffs (no device, no stream): it writes both, returns ksize = cosy_resize_ksize(in,
+ * out, filter), and needs capacity >= out * ksize ints in `k` and 2 * out ints in `bounds`; in, out < 1 or another filter give
+ * COSY_EINVAL, a capacity too small COSY_ESIZE (both negative).
+ *
+ * cosy_resize_u8: n images of C planes each, image i (C,h_i,w_i) contiguous at items[i].src, all resized to out (n,C,H,W).  items and
+ * tables are DEVICE memory; tables (n_tables int32) holds the bounds and coefficient tables of the axes the items name by offset (in
+ * ints): hb / vb the bounds of the horizontal (w -> W) and vertical (h -> H) axis, hk / vk their coefficients, hks / vks their ksize.
+ * ksize 0 means the pass is skipped, which needs w == W (h == H); with both skipped the image is copied.  The horizontal pass comes
+ * first and its result is rounded to bytes, as in Pillow.  Two launches: rows (items -> workspace, or -> out where there is no vertical
+ * pass), then columns (-> out); workspace is cosy_resize_workspace_bytes(n, C, max_h, W) bytes, 16-byte aligned, with max_h >= every
+ * h_i.  Integer arithmetic only; equal inputs give equal bytes.  out needs no alignment.
+ * Checked on the host before any launch (COSY_EINVAL, cosy_last_error() names the argument): 0 <= n <= 65535, C, H, W, max_h >= 1,
+ * max_h <= 262140, C max_h W and C H W < 2^31, non-null pointers, the workspace size; n = 0 returns COSY_OK at once.  The items live on the
+ * device and are checked there: an item with a null src, h or w < 1, h > max_h, a table outside [0, n_tables), or a skipped pass
+ * whose lengths differ leaves its image of `out` UNTOUCHED and reads nothing; a bounds entry that would read outside its line (xmin <
+ * 0, xmax outside [0, ksize], xmin + xmax > in) leaves that output byte untouched.  Callers build the tables with cosy_resize_coeffs. */
+enum { COSY_RESIZE_BILINEAR = 2, COSY_RESIZE_BICUBIC = 3 };   /* Pillow's Image.BILINEAR, Image.BICUBIC */
+typedef struct cosy_resize_item {
+    const unsigned char* src;
+    int h, w;
+    int hb, hk, hks;
+    int vb, vk, vks; /* 40 bytes per item */
+} cosy_resize_item_t;
+int cosy_resize_ksize(int in, int out, int filter);
+int cosy_resize_coeffs(int in, int out, int filter, int* bounds, int* k, size_t capacity);
+size_t cosy_resize_workspace_bytes(int n, int C, int max_h, int W);
+int cosy_resize_u8(const cosy_resize_item_t* items, int n, int C, int H, int W, int max_h, const int* tables, long n_tables,
+                   unsigned char* out, void* workspace, size_t workspace_bytes, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
