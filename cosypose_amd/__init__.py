@@ -49,6 +49,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'resize_images':
         from .resize import resize_images
         return resize_images
+    if name == 'resize_frames':
+        from .frames import resize_frames
+        return resize_frames
     if name in ('DetectionMeter', 'box_iou', 'box_iou_pairs'):
         from . import detection_meters
         return getattr(detection_meters, name)

@@ -627,6 +627,34 @@ size_t cosy_resize_workspace_bytes(int n, int C, int max_h, int W);
 int cosy_resize_u8(const cosy_resize_item_t* items, int n, int C, int H, int W, int max_h, const int* tables, long n_tables,
                    unsigned char* out, void* workspace, size_t workspace_bytes, cosy_stream_t stream);
 
+/* ---- The frames' own resize (CropResizeToAspectAugmentation.__call__, cosypose/datasets/augmentations.py:137-192, for a frame of the
+ * target aspect): image through float32 bilinear interpolation with half-pixel centres and a truncating cast, mask through nearest ----
+ * DESIGN.md section 18 holds the arithmetic.  Everything that divides is computed by the CALLER in float32 and handed over in `tables`
+ * (n_tables int32 of DEVICE memory, 16-byte aligned): for an axis n_in -> n_out a tap table (n_out,4) = i0, i1, bits of l0, bits of l1
+ * (offset a multiple of 4 ints) and a nearest table (n_out) = source index; and at offset `lut` the bits of the 256 floats
+ * float32(u) / 255f.
+ *
+ * cosy_resize_frames_u8: n frames, frame i an image (3,h_i,w_i) uint8 contiguous at items[i].image and, where items[i].mask is not
+ * null, a mask (h_i,w_i) uint8; images go to out_images (n,3,H,W), masks to out_masks (n,H,W) (may be null when no item has a mask).
+ * xb / yb: offsets (in ints) of the tap tables of the horizontal (w -> W) and vertical (h -> H) axis, xn / yn of the nearest tables
+ * (read only for a mask).  A frame with h == H and w == W is copied and its offsets are not read.  ONE launch, no workspace; per byte
+ *   top = fma(lx0, p00, lx1 * p01), bot = fma(lx0, p10, lx1 * p11), v = fma(ly0, top, ly1 * bot), byte = (uint8) trunc(v * 255f)
+ * with every product rounded once.  Equal inputs give equal bytes.  The outputs need no alignment.
+ * Checked on the host before the launch (COSY_EINVAL, cosy_last_error() names the argument): 0 <= n <= 16383, H, W >= 1, H <= 524280,
+ * 3 H W < 2^31, lut + 256 <= n_tables, non-null items / tables / out_images and their alignment; n = 0 returns COSY_OK at once.  The
+ * items live on the device and are checked there: an item with a null image (mask), h or w < 1, or a table outside [0, n_tables) or
+ * misaligned leaves its frame of out_images (out_masks) UNTOUCHED and reads nothing; a tap or nearest index outside its line is
+ * clamped into it. */
+typedef struct cosy_frame_item {
+    const unsigned char* image;
+    const unsigned char* mask;
+    int h, w;
+    int xb, yb;
+    int xn, yn; /* 40 bytes per item */
+} cosy_frame_item_t;
+int cosy_resize_frames_u8(const cosy_frame_item_t* items, int n, int H, int W, const int* tables, long n_tables, int lut,
+                          unsigned char* out_images, unsigned char* out_masks, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
