@@ -25,6 +25,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'MultiviewScenePredictor':
         from .multiview_predictor import MultiviewScenePredictor
         return MultiviewScenePredictor
+    if name in ('MultiviewRefinement', 'solve_problems'):
+        from . import bundle_adjustment
+        return getattr(bundle_adjustment, name)
     if name == 'multiview_candidate_matching':
         from .multiview_matching import multiview_candidate_matching
         return multiview_candidate_matching

@@ -95,6 +95,14 @@ _SIGNATURES = {
     'cosy_ba_align': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
     'cosy_ba_linearize': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     'cosy_ba_solve': ([_P, _P, _I, _D, _P, _P, _P], _I),
+    'cosy_ba_batch_table_bytes': ([_I, _I, _I], _SZ),
+    'cosy_ba_batch_workspace_bytes': ([_I, _I, _c.c_longlong], _SZ),
+    'cosy_ba_batch_upload': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _c.POINTER(_c.c_longlong), _c.POINTER(_I), _P], _I),
+    'cosy_ba_batch_linearize': ([_P, _I, _P], _I),
+    'cosy_ba_batch_solve_step': ([_P, _P], _I),
+    'cosy_ba_batch_record': ([_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_ba_batch_decide': ([_P, _I, _D, _D, _D, _P, _I, _I, _P, _P, _P, _P, _P], _I),
+    'cosy_ba_batch_iterate': ([_P, _I, _I, _P], _I),
     'cosy_ransac_max_tmatches': ([], _I),
     'cosy_ransac_hypotheses': ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
     'cosy_ransac_score': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P], _I),
@@ -131,6 +139,17 @@ class MeshSet(ctypes.Structure):       # cosy_mesh_t
 class Shade(ctypes.Structure):         # cosy_shade_t
     _fields_ = [('ambient', _F), ('diffuse', _F), ('specular', _F), ('shininess', _F), ('light', _F * 3),
                 ('light_frame', _I), ('smooth', _I), ('quantize', _I)]
+
+
+class BaCtrl(ctypes.Structure):        # cosy_ba_ctrl_t
+    _fields_ = [('loss', _D), ('next_loss', _D), ('lambd', _D), ('done', _I), ('prev_update', _I), ('finished', _I), ('n_hist', _I)]
+
+
+class BaBatch(ctypes.Structure):       # cosy_ba_batch_t
+    _fields_ = [(k, _I) for k in ('G', 'n_cand', 'n_obj', 'n_views', 'n_mesh', 'P', 'S', 'max_blocks', 'n_hist_rows', 'optimize_cameras')] + [
+        ('a_total', _c.c_longlong)] + [(k, _D) for k in ('residuals_threshold', 'L_down', 'L_up', 'eps')] + [
+        (k, _P) for k in ('table', 'cand_TCO', 'K', 'pts_table', 'sym_table', 'n_sym', 'TWO_9d', 'TCW_9d', 'TWO_9d_updated', 'TCW_9d_updated',
+                          'ctrl', 'hist_iteration', 'hist_lambda', 'hist_loss', 'hist_TWO_9d', 'hist_TCW_9d', 'workspace')]
 
 
 class ProfRec(ctypes.Structure):

@@ -10,7 +10,14 @@ the measurements that made float32 unusable); poses come back in the candidates'
 Host work: the constructor (id maps, visibility matrix, pair map: pandas / numpy, no device access), the initialisation walk over the
 view graph (a few 4x4 products per view, float64 numpy), and the accept / reject logic of the loop, which reads ONE scalar -- the
 loss -- back per linearisation.
+
+`solve_problems` takes MANY problems through one set of launches: the batch is their concatenation (`_batch_plan`), the accept / reject /
+stop logic runs on the device per problem (cosy_ba_batch_decide / cosy_ba_batch_record), and the host reads back only the number of
+unfinished problems, once per `poll_every` iterations.  The kernels share their device code with the single-problem entries, so a
+problem gets the same bits from both.
 """
+import ctypes
+import math
 import time
 from collections import defaultdict
 
@@ -424,3 +431,165 @@ class MultiviewRefinement:
         t3 = time.time()
         return dict(objects_init=objects_init, cameras_init=cameras_init, objects=objects, cameras=cameras, history=history,
                     time_init=t1 - t0, time_opt=t2 - t1, time_misc=t3 - t2)
+
+
+# ---- many problems per call ------------------------------------------------------------------------------------------------------
+def _batch_plan(problems):
+    """The id and offset tables of a batch = the concatenation of `problems`, as numpy arrays (no device is touched, so CPU-tensor
+    problems do).  Candidates carry GLOBAL object and view rows: cand_obj[c] = obj_off[g] + the problem's own object id, cand_view[c]
+    = view_off[g] + its view id; cand_mesh / obj_mesh are rows of the shared mesh table.  cand_off, obj_off, view_off, par_off (9 x
+    blocks) and A_off (n_g^2) are exclusive prefix sums with G + 1 entries; n = 9 (objects + views) per problem.  Raises ValueError for
+    problems that do not share one mesh_db (the same `points` and `symmetries` tensors) and for one over MAX_BLOCKS."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError('_batch_plan: no problems')
+    mesh_db = problems[0].mesh_db
+    for g, p in enumerate(problems):
+        if p.mesh_db is not mesh_db and (p.mesh_db.points is not mesh_db.points or p.mesh_db.symmetries is not mesh_db.symmetries):
+            raise ValueError(f'solve_problems: problem {g} has another mesh_db than problem 0 (a batch shares one points / symmetries table)')
+        if p.n_objects + p.n_views > MAX_BLOCKS:
+            raise ValueError(f'solve_problems: problem {g}: {p.n_objects} objects + {p.n_views} views > {MAX_BLOCKS}')
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    prefix = lambda sizes: np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))])
+    cand_off, obj_off, view_off = (prefix([getattr(p, k) for p in problems]) for k in ('n_candidates', 'n_objects', 'n_views'))
+    blocks = np.asarray([p.n_objects + p.n_views for p in problems], dtype=np.int64)
+    l2i = mesh_db.label_to_id
+    return dict(
+        G=len(problems), n=9 * blocks, max_blocks=int(blocks.max()),
+        cand_obj=i32(np.concatenate([np.asarray(p.cand_obj_ids, dtype=np.int64) + obj_off[g] for g, p in enumerate(problems)])),
+        cand_view=i32(np.concatenate([np.asarray(p.cand_view_ids, dtype=np.int64) + view_off[g] for g, p in enumerate(problems)])),
+        cand_mesh=i32([l2i[l] for p in problems for l in p.cand_labels]),
+        obj_mesh=i32([l2i[l] for p in problems for l in p.obj_infos['label']]),
+        cand_off=i32(cand_off), obj_off=i32(obj_off), view_off=i32(view_off), par_off=9 * prefix(blocks), A_off=prefix((9 * blocks) ** 2))
+
+
+def _pose9d_np(T):
+    """MultiviewRefinement.extract_pose9d on numpy: copies only"""
+    return np.concatenate([np.swapaxes(T[..., :3, :2], -1, -2).reshape(*T.shape[:-2], 6), T[..., :3, 3]], axis=-1)
+
+
+class _Batch:
+    """The device side of one solve_problems call: tables, states, control records, history rows, workspace."""
+
+    def __init__(self, problems, plan, TWO_9d, TCW_9d, optimize_cameras, n_iterations, residuals_threshold, lambd0, L_down, L_up, eps,
+                 history):
+        from ._lib import BaBatch, BaCtrl
+        mesh_db = problems[0].mesh_db
+        f64 = torch.float64
+        cand_TCO = torch.cat([p.cand_TCO.detach() for p in problems]).to(f64).contiguous()
+        K = torch.cat([p.K.detach() for p in problems]).to(f64).contiguous()
+        pts = mesh_db.points.detach().to(f64).contiguous()
+        sym = mesh_db.symmetries.detach().to(f64).contiguous()
+        require_device(cand_TCO, K, pts, sym, TWO_9d, TCW_9d)
+        dev = cand_TCO.device
+        G, nc, no, nv = plan['G'], len(plan['cand_obj']), len(plan['obj_mesh']), int(plan['view_off'][-1])
+        n_mesh = pts.shape[0]
+        n_sym = torch.as_tensor(np.fromiter((mesh_db.infos[l]['n_sym'] for l in mesh_db.labels), dtype=np.int32, count=n_mesh)).to(dev)
+        table = torch.empty(lib().cosy_ba_batch_table_bytes(G, nc, no), dtype=torch.uint8, device=dev)
+        a_total, max_blocks = ctypes.c_longlong(0), ctypes.c_int(0)
+        check(lib().cosy_ba_batch_upload(*(plan[k].ctypes.data for k in ('cand_obj', 'cand_view', 'cand_mesh', 'obj_mesh', 'cand_off', 'obj_off',
+                                                                         'view_off')),
+                                         G, n_mesh, ptr(table), ctypes.byref(a_total), ctypes.byref(max_blocks), stream()))
+        assert a_total.value == int(plan['A_off'][-1]) and max_blocks.value == plan['max_blocks']
+        ctrl = np.zeros(G, dtype=np.dtype(BaCtrl))
+        ctrl['lambd'] = lambd0
+        self.ctrl = torch.from_numpy(ctrl.view(np.uint8).reshape(G, -1)).to(dev)
+        self.ctrl_dtype = ctrl.dtype
+        rows = n_iterations
+        self.TWO, self.TCW = TWO_9d.to(f64).contiguous().clone(), TCW_9d.to(f64).contiguous().clone()
+        self.TWO_updated, self.TCW_updated = torch.empty_like(self.TWO), torch.empty_like(self.TCW)
+        self.hist_iteration = torch.empty(G, rows, dtype=torch.int32, device=dev)
+        self.hist_lambda = torch.empty(G, rows, dtype=f64, device=dev)
+        self.hist_loss = torch.empty(G, rows, dtype=f64, device=dev)
+        self.hist_TWO = torch.empty(rows, no, 9, dtype=f64, device=dev) if history else None
+        self.hist_TCW = torch.empty(rows, nv, 9, dtype=f64, device=dev) if history else None
+        self.ws = torch.empty(lib().cosy_ba_batch_workspace_bytes(nc, no + nv, a_total.value), dtype=torch.uint8, device=dev)
+        self._keep = (table, cand_TCO, K, pts, sym, n_sym)
+        self.c = BaBatch(G=G, n_cand=nc, n_obj=no, n_views=nv, n_mesh=n_mesh, P=pts.shape[1], S=sym.shape[1], max_blocks=max_blocks.value,
+                         n_hist_rows=rows, optimize_cameras=int(bool(optimize_cameras)), a_total=a_total.value,
+                         residuals_threshold=float(residuals_threshold), L_down=float(L_down), L_up=float(L_up), eps=float(eps),
+                         table=ptr(table), cand_TCO=ptr(cand_TCO), K=ptr(K), pts_table=ptr(pts), sym_table=ptr(sym), n_sym=ptr(n_sym),
+                         TWO_9d=ptr(self.TWO), TCW_9d=ptr(self.TCW), TWO_9d_updated=ptr(self.TWO_updated),
+                         TCW_9d_updated=ptr(self.TCW_updated), ctrl=ptr(self.ctrl), hist_iteration=ptr(self.hist_iteration),
+                         hist_lambda=ptr(self.hist_lambda), hist_loss=ptr(self.hist_loss), hist_TWO_9d=ptr(self.hist_TWO),
+                         hist_TCW_9d=ptr(self.hist_TCW), workspace=ptr(self.ws))
+
+    def iterate(self, n_first, n_count):
+        check(lib().cosy_ba_batch_iterate(ctypes.addressof(self.c), n_first, n_count, stream()))
+
+    def n_unfinished(self):
+        """ONE host read: how many problems have not met their stop rule"""
+        finished = self.ctrl.view(torch.int32)[:, self.ctrl_dtype.fields['finished'][1] // 4]
+        return int((finished == 0).sum().item())
+
+
+def solve_problems(problems, sample_n_init=1, optimize_cameras=True, n_iterations=50, residuals_threshold=25, lambd0=1e-3, L_down=9,
+                   L_up=11, eps=1e-5, history=True, poll_every=8):
+    """`MultiviewRefinement.solve` of every problem of `problems`, all of them advancing through the same launches -> one dict per
+    problem with solve's keys objects_init, cameras_init, objects, cameras, history, and TWO_9d / TCW_9d: the final float64 states.
+    history holds `iteration` (ints), `lambda` (floats) and `loss` (0-d float64 device tensors) and, with history=True, the states
+    `TWO_9d` / `TCW_9d` of every entry; the per-entry `objects` / `cameras` collections are not built (problem.convert_history adds
+    them).  A problem gets the same bits as from its own `solve`, whatever else is in the batch.
+
+    The problems must share one mesh_db (ValueError otherwise, before any launch).  The initial states come from each problem's host
+    walk (with sample_n_init > 1 each problem picks its best start on the device first, as solve does).  The host launches
+    `poll_every` iterations at a time and then reads ONE number back, how many problems are still running, to stop early; one more
+    read at the end fetches the history's lengths, lambdas and iteration numbers.  Batch-level figures go on the FIRST dict: `n_host_reads`,
+    `n_iterations_launched`, `time_init`, `time_opt`, `time_misc` (seconds, as solve's, for the whole batch)."""
+    problems = list(problems)
+    if not problems:
+        return []
+    if n_iterations < 1 or poll_every < 1 or not lambd0 > 0:
+        raise ValueError(f'solve_problems: n_iterations={n_iterations} poll_every={poll_every} lambd0={lambd0}')
+    t0 = time.time()
+    plan = _batch_plan(problems)                      # refuses mixed mesh tables and oversized problems before any launch
+    require_device(*(p.cand_TCO for p in problems), problems[0].mesh_db.points, problems[0].mesh_db.symmetries)
+    dev = problems[0].cand_TCO.device
+    if sample_n_init == 1:
+        starts = [p._sample_initial(0) for p in problems]
+        TWO_9d_init = torch.as_tensor(np.concatenate([_pose9d_np(TWO) for TWO, _ in starts])).to(dev)
+        TCW_9d_init = torch.as_tensor(np.concatenate([_pose9d_np(_invert_T_np(TWC)) for _, TWC in starts])).to(dev)
+    else:
+        starts = [p.robust_initialization_TWO_TCW(n_init=sample_n_init) for p in problems]
+        TWO_9d_init, TCW_9d_init = torch.cat([a for a, _ in starts]), torch.cat([c for _, c in starts])
+    batch = _Batch(problems, plan, TWO_9d_init, TCW_9d_init, optimize_cameras, n_iterations, residuals_threshold, lambd0, L_down, L_up, eps,
+                   history)
+    torch.cuda.synchronize()
+    t1 = time.time()
+
+    n_host_reads, n = 0, 0
+    while n < n_iterations:
+        count = min(poll_every, n_iterations - n)
+        batch.iterate(n, count)
+        n += count
+        if n < n_iterations:
+            n_host_reads += 1
+            if batch.n_unfinished() == 0:
+                break
+    # the last read: the records (history lengths) and the small history columns
+    n_hist = batch.ctrl.cpu().numpy().view(batch.ctrl_dtype)['n_hist'].ravel()
+    host_iteration, host_lambda = batch.hist_iteration.cpu().numpy(), batch.hist_lambda.cpu().numpy()
+    n_host_reads += 1
+    t2 = time.time()
+
+    # 4x4 outputs of all problems: one batched conversion of [final | initial] states
+    TWO = compute_transform_from_pose9d(torch.stack([batch.TWO, TWO_9d_init]))
+    TWC = invert_T(compute_transform_from_pose9d(torch.stack([batch.TCW, TCW_9d_init])))
+    outs = []
+    for g, p in enumerate(problems):
+        o0, o1, v0, v1, k = plan['obj_off'][g], plan['obj_off'][g + 1], plan['view_off'][g], plan['view_off'][g + 1], int(n_hist[g])
+        hist = {'iteration': host_iteration[g, :k].tolist(), 'lambda': host_lambda[g, :k].tolist(),
+                'loss': list(batch.hist_loss[g, :k].unbind(0))}
+        if history:
+            hist['TWO_9d'] = list(batch.hist_TWO[:k, o0:o1].unbind(0))
+            hist['TCW_9d'] = list(batch.hist_TCW[:k, v0:v1].unbind(0))
+        TWO_p, TWC_p = TWO[:, o0:o1].to(p.dtype), TWC[:, v0:v1].to(p.dtype)
+        outs.append(dict(objects_init=tc.PandasTensorCollection(infos=p.obj_infos, TWO=TWO_p[1]),
+                         cameras_init=tc.PandasTensorCollection(infos=p.cam_infos, TWC=TWC_p[1], K=p.K),
+                         objects=tc.PandasTensorCollection(infos=p.obj_infos, TWO=TWO_p[0]),
+                         cameras=tc.PandasTensorCollection(infos=p.cam_infos, TWC=TWC_p[0], K=p.K), history=hist,
+                         TWO_9d=batch.TWO[o0:o1], TCW_9d=batch.TCW[v0:v1]))
+    torch.cuda.synchronize()
+    t3 = time.time()
+    outs[0].update(n_host_reads=n_host_reads, n_iterations_launched=n, time_init=t1 - t0, time_opt=t2 - t1, time_misc=t3 - t2)
+    return outs

@@ -12,6 +12,9 @@
 // All of the bundle adjustment is float64 (DESIGN.md "Bundle adjustment": the problem is too ill-conditioned for float32); contraction
 // is off so that a value does not depend on which multiply-adds the compiler chose to fuse.  Every sum runs in a fixed order: two runs
 // on the same inputs give the same bits.
+#include <stdlib.h>
+#include <string.h>
+
 #include "cosy_common.h"
 #include "reduce_device.h"
 
@@ -175,16 +178,15 @@ __device__ __forceinline__ bool cand_ids(const int* __restrict__ ids, int c, int
     return m_obj >= 0 && m_obj < n_mesh;
 }
 
-__global__ __launch_bounds__(256) void ba_align_kernel(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
-                                                       const double* __restrict__ cand_TCO, const double* __restrict__ K,
-                                                       const int* __restrict__ ids, const double* __restrict__ pts,
-                                                       const double* __restrict__ sym, const int* __restrict__ n_sym, int n_cand, int n_obj,
-                                                       int n_views, int n_mesh, int P, int S, double* __restrict__ dists,
-                                                       int* __restrict__ best_sym, double* __restrict__ aligned) {
-    __shared__ double red[4];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    int o, v, m, mo;
-    if (!cand_ids(ids, c, n_cand, n_obj, n_views, n_mesh, o, v, m, mo)) return;
+// The alignment of candidate c (object row o, view row v, mesh m; all checked by the caller), shared by the single-problem and the
+// batched kernel so that both compute the same bits.  dists / best_sym may be null.
+__device__ __forceinline__ void ba_align_body(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                              const double* __restrict__ cand_TCO, const double* __restrict__ K,
+                                              const double* __restrict__ pts, const double* __restrict__ sym,
+                                              const int* __restrict__ n_sym, int c, int o, int v, int m, int P, int S,
+                                              double* __restrict__ dists, int* __restrict__ best_sym, double* __restrict__ aligned,
+                                              double* red) {
+    const int tid = threadIdx.x;
     double a[9], Two[16], Tcw[16], Tco[16], t1[16], k[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) a[i] = TWO_9d[(size_t)o * 9 + i];
@@ -199,14 +201,20 @@ __global__ __launch_bounds__(256) void ba_align_kernel(const double* __restrict_
     for (int i = 0; i < 9; ++i) k[i] = K[(size_t)v * 9 + i];
     const int ns = min(n_sym[m], S);
     if (ns <= 0) {   // a mesh without a symmetry (the identity counts as one): marked with NaNs, which the loss then shows
-        if (tid == 0) { dists[c] = __builtin_nan(""); best_sym[c] = -1; }
+        if (tid == 0) {
+            if (dists) dists[c] = __builtin_nan("");
+            if (best_sym) best_sym[c] = -1;
+        }
         if (tid < 16) aligned[(size_t)c * 16 + tid] = __builtin_nan("");
         return;
     }
     double d;
     const double* sm = sym + (size_t)m * S * 16;
     const int best = reprojected_best_symmetry<double>(t1, Tco, k, pts + (size_t)m * P * 3, sm, ns, P, red, d);
-    if (tid == 0) { dists[c] = d; best_sym[c] = best; }
+    if (tid == 0) {
+        if (dists) dists[c] = d;
+        if (best_sym) best_sym[c] = best;
+    }
     if (tid < 16 && best >= 0) {   // TCO_cand_aligned = cand_TCO @ S
         const int i = tid >> 2, j = tid & 3;
         double acc = 0.;
@@ -216,22 +224,32 @@ __global__ __launch_bounds__(256) void ba_align_kernel(const double* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void ba_align_kernel(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                                       const double* __restrict__ cand_TCO, const double* __restrict__ K,
+                                                       const int* __restrict__ ids, const double* __restrict__ pts,
+                                                       const double* __restrict__ sym, const int* __restrict__ n_sym, int n_cand, int n_obj,
+                                                       int n_views, int n_mesh, int P, int S, double* __restrict__ dists,
+                                                       int* __restrict__ best_sym, double* __restrict__ aligned) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    int o, v, m, mo;
+    if (!cand_ids(ids, c, n_cand, n_obj, n_views, n_mesh, o, v, m, mo)) return;
+    ba_align_body(TWO_9d, TCW_9d, cand_TCO, K, pts, sym, n_sym, c, o, v, m, P, S, dists, best_sym, aligned, red);
+}
+
 // One workgroup per candidate.  Thread t of a pass owns residual row r = pass*256 + t: point r/2, coordinate r%2 (the reference's order,
 // bundle_adjustment.py:93-110).  The rows of a pass are staged in LDS, then thread t < 189 adds the pass' contribution to its entry of
 // the upper triangle of J_c^T J_c (171) or of J_c^T e_c (18), rows in order.
-__global__ __launch_bounds__(BA_ROWS) void ba_linearize_kernel(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
-                                                               const double* __restrict__ aligned, const double* __restrict__ K,
-                                                               const int* __restrict__ ids, const double* __restrict__ pts, int n_cand,
-                                                               int n_obj, int n_views, int n_mesh, int P, double threshold,
-                                                               double* __restrict__ errors, double* __restrict__ J_obj,
-                                                               double* __restrict__ J_view, double* __restrict__ blk,
-                                                               double* __restrict__ loss_part) {
-    __shared__ double rows[BA_ROWS * BA_W];
-    __shared__ double dRo[6 * 9], dRc[6 * 9];
-    __shared__ double red[4];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    int o, v, m, mo;
-    const bool ok = cand_ids(ids, c, n_cand, n_obj, n_views, n_mesh, o, v, m, mo);
+// The body is shared by the single-problem and the batched kernel (the same bits from both); `ok` = the candidate's ids are inside
+// their tables (o, v: object and view row, mo: the object's mesh).  errors, J_obj, J_view may be null.  rows: BA_ROWS * BA_W doubles of
+// LDS, dRo / dRc: 54 each, red: 4.
+__device__ __forceinline__ void ba_linearize_body(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                                  const double* __restrict__ aligned, const double* __restrict__ K,
+                                                  const double* __restrict__ pts, bool ok, int c, int o, int v, int mo, int P,
+                                                  double threshold, double* __restrict__ errors, double* __restrict__ J_obj,
+                                                  double* __restrict__ J_view, double* __restrict__ blk, double* __restrict__ loss_part,
+                                                  double* rows, double* dRo, double* dRc, double* red) {
+    const int tid = threadIdx.x;
     // entry of the block this thread sums
     int ei = 0, ej = 18;
     if (tid < BA_TRI) {
@@ -301,7 +319,7 @@ __global__ __launch_bounds__(BA_ROWS) void ba_linearize_kernel(const double* __r
             for (int i = 0; i < 3; ++i) { row[6 + i] = gw[i]; row[15 + i] = g[i]; }
             row[18] = e;
             const size_t gr = (size_t)c * n_rows + r;
-            errors[gr] = e;
+            if (errors) errors[gr] = e;
             if (J_obj)
 #pragma unroll
                 for (int i = 0; i < 9; ++i) J_obj[gr * 9 + i] = row[i];
@@ -326,17 +344,36 @@ __global__ __launch_bounds__(BA_ROWS) void ba_linearize_kernel(const double* __r
     if (tid == 0) loss_part[c] = loss_acc;
 }
 
+__global__ __launch_bounds__(BA_ROWS) void ba_linearize_kernel(const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                                               const double* __restrict__ aligned, const double* __restrict__ K,
+                                                               const int* __restrict__ ids, const double* __restrict__ pts, int n_cand,
+                                                               int n_obj, int n_views, int n_mesh, int P, double threshold,
+                                                               double* __restrict__ errors, double* __restrict__ J_obj,
+                                                               double* __restrict__ J_view, double* __restrict__ blk,
+                                                               double* __restrict__ loss_part) {
+    __shared__ double rows[BA_ROWS * BA_W];
+    __shared__ double dRo[6 * 9], dRc[6 * 9];
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    int o, v, m, mo;
+    const bool ok = cand_ids(ids, c, n_cand, n_obj, n_views, n_mesh, o, v, m, mo);
+    ba_linearize_body(TWO_9d, TCW_9d, aligned, K, pts, ok, c, o, v, mo, P, threshold, errors, J_obj, J_view, blk, loss_part, rows, dRo, dRc,
+                      red);
+}
+
 __device__ __forceinline__ int tri_index(int i, int j) {   // i <= j < 18
     return i * 18 - (i * (i - 1)) / 2 + (j - i);
 }
 
-// A (n,n) and b (n), n = 9 (n_obj + n_views), objects first: workgroup (bj, bi) writes the 9x9 block (bi, bj) -- zeros included, so A
-// needs no clearing -- as the sum over the candidates of that block IN CANDIDATE ORDER; column 0's workgroups also write b, workgroup
-// (0,0) the loss.
-__global__ __launch_bounds__(128) void ba_accumulate_kernel(const double* __restrict__ blk, const double* __restrict__ loss_part,
-                                                            const int* __restrict__ ids, int n_cand, int n_obj, int n_views, int P,
-                                                            double* __restrict__ A, double* __restrict__ b, double* __restrict__ loss) {
-    const int bi = blockIdx.y, bj = blockIdx.x, tid = threadIdx.x;
+// A (n,n) and b (n), n = 9 (n_obj + n_views), objects first: the workgroup of block (bi, bj) writes that 9x9 block -- zeros included, so A
+// needs no clearing -- as the sum over the candidates c0 <= c < c1 of that block IN CANDIDATE ORDER; column 0's workgroups also write b,
+// workgroup (0,0) the loss.  A candidate's object / view row is cand_obj[c] - o_base / cand_view[c] - v_base.  Shared by the
+// single-problem and the batched kernel.
+__device__ __forceinline__ void ba_accumulate_body(const double* __restrict__ blk, const double* __restrict__ loss_part,
+                                                   const int* __restrict__ cand_obj, const int* __restrict__ cand_view, int c0, int c1,
+                                                   int o_base, int v_base, int n_obj, int n_views, int P, int bi, int bj,
+                                                   double* __restrict__ A, double* __restrict__ b, double* __restrict__ loss) {
+    const int tid = threadIdx.x;
     const int n = 9 * (n_obj + n_views);
     const bool io = bi < n_obj, jo = bj < n_obj;
     const int r = tid / 9, cc = tid % 9;
@@ -350,8 +387,8 @@ __global__ __launch_bounds__(128) void ba_accumulate_kernel(const double* __rest
             else if (io) { hi = r; hj = 9 + cc; }
             else { hi = cc; hj = 9 + r; }
             const int e = hi <= hj ? tri_index(hi, hj) : tri_index(hj, hi);
-            for (int c = 0; c < n_cand; ++c) {
-                const int o = ids[c], v = ids[n_cand + c];
+            for (int c = c0; c < c1; ++c) {
+                const int o = cand_obj[c] - o_base, v = cand_view[c] - v_base;
                 if ((want_o < 0 || o == want_o) && (want_v < 0 || v == want_v)) acc += blk[(size_t)c * BA_BLK + e];
             }
         }
@@ -360,24 +397,31 @@ __global__ __launch_bounds__(128) void ba_accumulate_kernel(const double* __rest
     if (bj == 0 && tid >= 96 && tid < 105) {
         const int t = tid - 96;
         double acc = 0.;
-        for (int c = 0; c < n_cand; ++c) {
-            const int o = ids[c], v = ids[n_cand + c];
+        for (int c = c0; c < c1; ++c) {
+            const int o = cand_obj[c] - o_base, v = cand_view[c] - v_base;
             if (io ? o == bi : v == bi - n_obj) acc += blk[(size_t)c * BA_BLK + BA_TRI + (io ? t : 9 + t)];
         }
         b[bi * 9 + t] = acc;
     }
     if (bi == 0 && bj == 0 && tid == 127) {
         double acc = 0.;
-        for (int c = 0; c < n_cand; ++c) acc += loss_part[c];
-        *loss = acc / ((double)n_cand * (double)(2 * P));
+        for (int c = c0; c < c1; ++c) acc += loss_part[c];
+        *loss = acc / ((double)(c1 - c0) * (double)(2 * P));
     }
 }
 
+__global__ __launch_bounds__(128) void ba_accumulate_kernel(const double* __restrict__ blk, const double* __restrict__ loss_part,
+                                                            const int* __restrict__ ids, int n_cand, int n_obj, int n_views, int P,
+                                                            double* __restrict__ A, double* __restrict__ b, double* __restrict__ loss) {
+    ba_accumulate_body(blk, loss_part, ids, ids + n_cand, 0, n_cand, 0, 0, n_obj, n_views, P, blockIdx.y, blockIdx.x, A, b, loss);
+}
+
 // h = (A + lambda I)^-1 b: right-looking Cholesky of the lower triangle in `L` (n*n doubles of workspace), then L y = b, L^T h = y.
-// One workgroup; column k and the right-hand side live in LDS.  A non-positive pivot gives NaNs in h (the caller's loss test rejects).
-__global__ __launch_bounds__(BA_SOLVE_THREADS) void ba_solve_kernel(const double* __restrict__ A, const double* __restrict__ b, int n,
-                                                                    double lambda, double* __restrict__ L, double* __restrict__ h) {
-    __shared__ double col[BA_MAX_N], vec[BA_MAX_N], dg[BA_MAX_N];
+// One workgroup of BA_SOLVE_THREADS; column k (col), the right-hand side (vec) and the diagonal (dg) live in LDS, BA_MAX_N doubles
+// each.  h is left in vec, visible to every thread on return.  A non-positive pivot gives NaNs in h (the caller's loss test rejects).
+// Shared by the single-problem and the batched kernel.
+__device__ __forceinline__ void ba_solve_body(const double* __restrict__ A, const double* __restrict__ b, int n, double lambda,
+                                              double* __restrict__ L, double* col, double* vec, double* dg) {
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
     for (int i = ty; i < n; i += 32)
         for (int j = tx; j <= i; j += 32) L[(size_t)i * n + j] = A[(size_t)i * n + j] + (i == j ? lambda : 0.);
@@ -412,7 +456,190 @@ __global__ __launch_bounds__(BA_SOLVE_THREADS) void ba_solve_kernel(const double
         for (int i = tid; i < k; i += BA_SOLVE_THREADS) vec[i] -= L[(size_t)k * n + i] * hk;
         __syncthreads();
     }
-    for (int i = tid; i < n; i += BA_SOLVE_THREADS) h[i] = vec[i];
+}
+
+__global__ __launch_bounds__(BA_SOLVE_THREADS) void ba_solve_kernel(const double* __restrict__ A, const double* __restrict__ b, int n,
+                                                                    double lambda, double* __restrict__ L, double* __restrict__ h) {
+    __shared__ double col[BA_MAX_N], vec[BA_MAX_N], dg[BA_MAX_N];
+    ba_solve_body(A, b, n, lambda, L, col, vec, dg);
+    for (int i = threadIdx.x; i < n; i += BA_SOLVE_THREADS) h[i] = vec[i];
+}
+
+// ---- the batch: G problems through the same launches ------------------------------------------------------------------------------
+// The device table written by cosy_ba_batch_upload: int32 cand_obj | cand_view | cand_mesh | cand_prob (n_cand each; object and view
+// rows are GLOBAL) | obj_mesh (n_obj) | cand_off | obj_off | view_off (G+1 each), then, 8-byte aligned, A_off (G+1) int64.
+struct BaTab {
+    const int *cand_obj, *cand_view, *cand_mesh, *cand_prob, *obj_mesh, *cand_off, *obj_off, *view_off;
+    const long long* A_off;
+};
+
+inline size_t ba_tab_ints(int G, int n_cand, int n_obj) {
+    const size_t n = 4 * (size_t)n_cand + (size_t)n_obj + 3 * ((size_t)G + 1);
+    return (n + 1) & ~(size_t)1;
+}
+
+inline BaTab ba_tab(const void* table, int G, int n_cand, int n_obj) {
+    const int* t = (const int*)table;
+    BaTab r;
+    r.cand_obj = t;
+    r.cand_view = t + (size_t)n_cand;
+    r.cand_mesh = t + 2 * (size_t)n_cand;
+    r.cand_prob = t + 3 * (size_t)n_cand;
+    r.obj_mesh = t + 4 * (size_t)n_cand;
+    r.cand_off = r.obj_mesh + (size_t)n_obj;
+    r.obj_off = r.cand_off + ((size_t)G + 1);
+    r.view_off = r.obj_off + ((size_t)G + 1);
+    r.A_off = (const long long*)(t + ba_tab_ints(G, n_cand, n_obj));
+    return r;
+}
+
+// candidate c of the batch: its object / view row inside ITS problem's rows, its meshes inside the table (cosy_ba_batch_upload checked
+// them; a candidate that is outside nevertheless is skipped as in the single problem)
+__device__ __forceinline__ bool ba_batch_cand_ids(const BaTab& t, int c, int g, int n_mesh, int& o, int& v, int& m, int& mo) {
+    o = t.cand_obj[c]; v = t.cand_view[c]; m = t.cand_mesh[c];
+    if (o < t.obj_off[g] || o >= t.obj_off[g + 1] || v < t.view_off[g] || v >= t.view_off[g + 1] || m < 0 || m >= n_mesh) return false;
+    mo = t.obj_mesh[o];
+    return mo >= 0 && mo < n_mesh;
+}
+
+// does problem g take part in this linearisation?  which = 0: the current state, not needed after an accepted step
+__device__ __forceinline__ bool ba_batch_idle(const cosy_ba_ctrl_t* __restrict__ ctrl, int g, int which) {
+    return ctrl[g].finished || (which == 0 && ctrl[g].prev_update);
+}
+
+__global__ __launch_bounds__(256) void ba_batch_align_kernel(BaTab t, const cosy_ba_ctrl_t* __restrict__ ctrl, int which, int G,
+                                                             const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                                             const double* __restrict__ cand_TCO, const double* __restrict__ K,
+                                                             const double* __restrict__ pts, const double* __restrict__ sym,
+                                                             const int* __restrict__ n_sym, int n_mesh, int P, int S,
+                                                             double* __restrict__ aligned) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    const int g = t.cand_prob[c];
+    if (g < 0 || g >= G || ba_batch_idle(ctrl, g, which)) return;
+    int o, v, m, mo;
+    if (!ba_batch_cand_ids(t, c, g, n_mesh, o, v, m, mo)) return;
+    ba_align_body(TWO_9d, TCW_9d, cand_TCO, K, pts, sym, n_sym, c, o, v, m, P, S, nullptr, nullptr, aligned, red);
+}
+
+__global__ __launch_bounds__(BA_ROWS) void ba_batch_linearize_kernel(BaTab t, const cosy_ba_ctrl_t* __restrict__ ctrl, int which, int G,
+                                                                     const double* __restrict__ TWO_9d, const double* __restrict__ TCW_9d,
+                                                                     const double* __restrict__ aligned, const double* __restrict__ K,
+                                                                     const double* __restrict__ pts, int n_mesh, int P, double threshold,
+                                                                     double* __restrict__ blk, double* __restrict__ loss_part) {
+    __shared__ double rows[BA_ROWS * BA_W];
+    __shared__ double dRo[6 * 9], dRc[6 * 9];
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    const int g = t.cand_prob[c];
+    if (g < 0 || g >= G || ba_batch_idle(ctrl, g, which)) return;
+    int o, v, m, mo;
+    const bool ok = ba_batch_cand_ids(t, c, g, n_mesh, o, v, m, mo);
+    ba_linearize_body(TWO_9d, TCW_9d, aligned, K, pts, ok, c, o, v, mo, P, threshold, nullptr, nullptr, nullptr, blk, loss_part, rows, dRo,
+                      dRc, red);
+}
+
+// grid (max_blocks^2, G): workgroup (x, g) owns block (x / blocks_g, x % blocks_g) of problem g's A
+__global__ __launch_bounds__(128) void ba_batch_accumulate_kernel(BaTab t, cosy_ba_ctrl_t* __restrict__ ctrl, int which,
+                                                                  const double* __restrict__ blk, const double* __restrict__ loss_part,
+                                                                  int P, double* __restrict__ A, double* __restrict__ b) {
+    const int g = blockIdx.y;
+    if (ba_batch_idle(ctrl, g, which)) return;
+    const int o0 = t.obj_off[g], v0 = t.view_off[g];
+    const int no = t.obj_off[g + 1] - o0, nv = t.view_off[g + 1] - v0, nb = no + nv;
+    if ((int)blockIdx.x >= nb * nb) return;
+    const int bi = blockIdx.x / nb, bj = blockIdx.x % nb;
+    ba_accumulate_body(blk, loss_part, t.cand_obj, t.cand_view, t.cand_off[g], t.cand_off[g + 1], o0, v0, no, nv, P, bi, bj,
+                       A + (size_t)t.A_off[g], b + 9 * ((size_t)o0 + (size_t)v0), which ? &ctrl[g].next_loss : &ctrl[g].loss);
+}
+
+__global__ __launch_bounds__(BA_SOLVE_THREADS) void ba_batch_solve_step_kernel(BaTab t, const cosy_ba_ctrl_t* __restrict__ ctrl,
+                                                                               const double* __restrict__ A, const double* __restrict__ b,
+                                                                               double* __restrict__ L, const double* __restrict__ TWO_9d,
+                                                                               const double* __restrict__ TCW_9d,
+                                                                               double* __restrict__ TWO_9d_updated,
+                                                                               double* __restrict__ TCW_9d_updated, int optimize_cameras) {
+    __shared__ double col[BA_MAX_N], vec[BA_MAX_N], dg[BA_MAX_N];
+    const int g = blockIdx.x;
+    if (ctrl[g].finished) return;
+    const int o0 = t.obj_off[g], v0 = t.view_off[g];
+    const int no = t.obj_off[g + 1] - o0, nv = t.view_off[g + 1] - v0;
+    const int n = 9 * (no + nv);
+    if (n > BA_MAX_N) return;
+    const size_t a0 = (size_t)t.A_off[g];
+    ba_solve_body(A + a0, b + 9 * ((size_t)o0 + (size_t)v0), n, ctrl[g].lambda, L + a0, col, vec, dg);
+    const size_t po = 9 * (size_t)o0, pv = 9 * (size_t)v0;
+    for (int i = threadIdx.x; i < n; i += BA_SOLVE_THREADS) {
+        if (i < 9 * no) {
+            TWO_9d_updated[po + i] = TWO_9d[po + i] + vec[i];
+        } else {
+            const int j = i - 9 * no;
+            TCW_9d_updated[pv + j] = optimize_cameras ? TCW_9d[pv + j] + vec[i] : TCW_9d[pv + j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_batch_record_kernel(BaTab t, cosy_ba_ctrl_t* __restrict__ ctrl, int iteration, int n_hist_rows,
+                                                              int n_obj, int n_views, const double* __restrict__ TWO_9d,
+                                                              const double* __restrict__ TCW_9d, int* __restrict__ hist_iteration,
+                                                              double* __restrict__ hist_lambda, double* __restrict__ hist_loss,
+                                                              double* __restrict__ hist_TWO_9d, double* __restrict__ hist_TCW_9d) {
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const cosy_ba_ctrl_t r = ctrl[g];
+    if (r.finished) return;    // uniform: the record is written below, after every thread has read it
+    __syncthreads();
+    const int k = r.n_hist;
+    if (k < 0 || k >= n_hist_rows) return;
+    if (hist_TWO_9d) {
+        const size_t o0 = 9 * (size_t)t.obj_off[g], v0 = 9 * (size_t)t.view_off[g];
+        const int no = 9 * (t.obj_off[g + 1] - t.obj_off[g]), nv = 9 * (t.view_off[g + 1] - t.view_off[g]);
+        double* ho = hist_TWO_9d + (size_t)k * n_obj * 9 + o0;
+        double* hv = hist_TCW_9d + (size_t)k * n_views * 9 + v0;
+        for (int i = tid; i < no; i += 256) ho[i] = TWO_9d[o0 + i];
+        for (int i = tid; i < nv; i += 256) hv[i] = TCW_9d[v0 + i];
+    }
+    if (tid == 0) {
+        const size_t row = (size_t)g * n_hist_rows + k;
+        hist_iteration[row] = iteration;
+        hist_lambda[row] = r.lambda;
+        hist_loss[row] = r.loss;
+        ctrl[g].n_hist = k + 1;
+        if (r.done) ctrl[g].finished = 1;
+    }
+}
+
+// the reference's comparisons in the reference's order (bundle_adjustment.py:263-276 there): a NaN rho fails both and is rejected
+__global__ __launch_bounds__(256) void ba_batch_decide_kernel(BaTab t, cosy_ba_ctrl_t* __restrict__ ctrl, double L_down, double L_up,
+                                                              double eps, double* __restrict__ TWO_9d, double* __restrict__ TCW_9d,
+                                                              const double* __restrict__ TWO_9d_updated,
+                                                              const double* __restrict__ TCW_9d_updated) {
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const cosy_ba_ctrl_t r = ctrl[g];
+    if (r.finished) return;    // uniform, as in the record kernel
+    __syncthreads();
+    const double rho = r.loss - r.next_loss;
+    if (fabs(rho) < eps) {
+        if (tid == 0) ctrl[g].done = 1;
+    } else if (rho > eps) {
+        if (TWO_9d) {
+            const size_t o0 = 9 * (size_t)t.obj_off[g], v0 = 9 * (size_t)t.view_off[g];
+            const int no = 9 * (t.obj_off[g + 1] - t.obj_off[g]), nv = 9 * (t.view_off[g + 1] - t.view_off[g]);
+            for (int i = tid; i < no; i += 256) TWO_9d[o0 + i] = TWO_9d_updated[o0 + i];
+            for (int i = tid; i < nv; i += 256) TCW_9d[v0 + i] = TCW_9d_updated[v0 + i];
+        }
+        if (tid == 0) {
+            const double l = r.lambda / L_down;
+            ctrl[g].loss = r.next_loss;
+            ctrl[g].lambda = 1e-7 > l ? 1e-7 : l;      // max(lambda / L_down, 1e-7)
+            ctrl[g].prev_update = 1;
+        }
+    } else {
+        if (tid == 0) {
+            const double l = r.lambda * L_up;
+            ctrl[g].lambda = 1e7 < l ? 1e7 : l;        // min(lambda * L_up, 1e7)
+            ctrl[g].prev_update = 0;
+        }
+    }
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -530,6 +757,225 @@ int cosy_ba_solve(const double* A, const double* b, int n, double lambda, double
     COSY_REQUIRE(A && b && h && workspace, "cosy_ba_solve: null pointer");
     hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(BA_SOLVE_THREADS), 0, s, A, b, n, lambda, (double*)workspace, h);
     COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+// ---- the batch ----
+namespace {
+
+struct BaBatchWs { double *blk, *loss_part, *aligned, *A, *L, *b; };
+
+inline size_t ba_batch_ws_layout(int n_cand, int n_blocks, long long a_total, char* base, BaBatchWs* ws) {
+    const size_t sizes[6] = {(size_t)n_cand * BA_BLK, (size_t)n_cand, (size_t)n_cand * 16, (size_t)a_total, (size_t)a_total,
+                             (size_t)n_blocks * 9};
+    double** out[6] = {ws ? &ws->blk : nullptr, ws ? &ws->loss_part : nullptr, ws ? &ws->aligned : nullptr, ws ? &ws->A : nullptr,
+                       ws ? &ws->L : nullptr, ws ? &ws->b : nullptr};
+    size_t off = 0;
+    for (int i = 0; i < 6; ++i) {
+        if (ws) *out[i] = (double*)(base + off);
+        off += align256(sizes[i] * sizeof(double));
+    }
+    return off;
+}
+
+int ba_batch_check(const cosy_ba_batch_t* b, const char* name) {
+    COSY_REQUIRE(b, "%s: null batch", name);
+    COSY_REQUIRE(b->G > 0 && b->G <= COSY_MAX_GRID_Y && b->n_cand >= b->G && b->n_obj >= b->G && b->n_views >= b->G,
+                 "%s: G=%d n_cand=%d n_obj=%d n_views=%d (every problem has a candidate, an object and a view; G <= %d)", name, b->G,
+                 b->n_cand, b->n_obj, b->n_views, COSY_MAX_GRID_Y);
+    COSY_REQUIRE(b->n_mesh > 0 && b->P > 0 && b->S > 0 && b->n_hist_rows > 0, "%s: n_mesh=%d P=%d S=%d n_hist_rows=%d", name, b->n_mesh,
+                 b->P, b->S, b->n_hist_rows);
+    if (b->max_blocks > BA_MAX_N / 9) {
+        cosy::set_error("%s: max_blocks = %d > %d", name, b->max_blocks, BA_MAX_N / 9);
+        return COSY_ESIZE;
+    }
+    COSY_REQUIRE(b->max_blocks >= 2 && b->a_total >= 324LL * b->G, "%s: max_blocks=%d a_total=%lld", name, b->max_blocks, b->a_total);
+    COSY_REQUIRE(b->L_down > 0. && b->L_up > 0., "%s: L_down=%g L_up=%g must be positive", name, b->L_down, b->L_up);
+    COSY_REQUIRE(b->table && b->cand_TCO && b->K && b->pts_table && b->sym_table && b->n_sym && b->TWO_9d && b->TCW_9d &&
+                     b->TWO_9d_updated && b->TCW_9d_updated && b->ctrl && b->hist_iteration && b->hist_lambda && b->hist_loss &&
+                     b->workspace,
+                 "%s: null pointer", name);
+    COSY_REQUIRE(!b->hist_TWO_9d == !b->hist_TCW_9d, "%s: hist_TWO_9d and hist_TCW_9d go together", name);
+    return COSY_OK;
+}
+
+int ba_batch_linearize_launch(const cosy_ba_batch_t* b, int which, hipStream_t s) {
+    const BaTab t = ba_tab(b->table, b->G, b->n_cand, b->n_obj);
+    BaBatchWs ws;
+    ba_batch_ws_layout(b->n_cand, b->n_obj + b->n_views, b->a_total, (char*)b->workspace, &ws);
+    const double* TWO = which ? b->TWO_9d_updated : b->TWO_9d;
+    const double* TCW = which ? b->TCW_9d_updated : b->TCW_9d;
+    hipLaunchKernelGGL(ba_batch_align_kernel, dim3(b->n_cand), dim3(256), 0, s, t, b->ctrl, which, b->G, TWO, TCW, b->cand_TCO, b->K,
+                       b->pts_table, b->sym_table, b->n_sym, b->n_mesh, b->P, b->S, ws.aligned);
+    COSY_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ba_batch_linearize_kernel, dim3(b->n_cand), dim3(BA_ROWS), 0, s, t, b->ctrl, which, b->G, TWO, TCW, ws.aligned, b->K,
+                       b->pts_table, b->n_mesh, b->P, b->residuals_threshold, ws.blk, ws.loss_part);
+    COSY_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ba_batch_accumulate_kernel, dim3(b->max_blocks * b->max_blocks, b->G), dim3(128), 0, s, t, b->ctrl, which, ws.blk,
+                       ws.loss_part, b->P, ws.A, ws.b);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int ba_batch_solve_step_launch(const cosy_ba_batch_t* b, hipStream_t s) {
+    const BaTab t = ba_tab(b->table, b->G, b->n_cand, b->n_obj);
+    BaBatchWs ws;
+    ba_batch_ws_layout(b->n_cand, b->n_obj + b->n_views, b->a_total, (char*)b->workspace, &ws);
+    hipLaunchKernelGGL(ba_batch_solve_step_kernel, dim3(b->G), dim3(BA_SOLVE_THREADS), 0, s, t, b->ctrl, ws.A, ws.b, ws.L, b->TWO_9d,
+                       b->TCW_9d, b->TWO_9d_updated, b->TCW_9d_updated, b->optimize_cameras);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+}  // namespace
+
+size_t cosy_ba_batch_table_bytes(int G, int n_cand, int n_obj) {
+    if (G <= 0 || n_cand <= 0 || n_obj <= 0) return 0;
+    return ba_tab_ints(G, n_cand, n_obj) * sizeof(int) + ((size_t)G + 1) * sizeof(long long);
+}
+
+size_t cosy_ba_batch_workspace_bytes(int n_cand, int n_blocks, long long a_total) {
+    if (n_cand <= 0 || n_blocks <= 0 || a_total <= 0) return 0;
+    return ba_batch_ws_layout(n_cand, n_blocks, a_total, nullptr, nullptr);
+}
+
+int cosy_ba_batch_upload(const int* host_cand_obj, const int* host_cand_view, const int* host_cand_mesh, const int* host_obj_mesh,
+                         const int* host_cand_off, const int* host_obj_off, const int* host_view_off, int G, int n_mesh, void* table,
+                         long long* a_total, int* max_blocks, cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    COSY_REQUIRE(G > 0 && G <= COSY_MAX_GRID_Y && n_mesh > 0, "cosy_ba_batch_upload: G=%d (1 .. %d) n_mesh=%d", G, COSY_MAX_GRID_Y, n_mesh);
+    COSY_REQUIRE(host_cand_obj && host_cand_view && host_cand_mesh && host_obj_mesh && host_cand_off && host_obj_off && host_view_off &&
+                     table && a_total && max_blocks,
+                 "cosy_ba_batch_upload: null pointer");
+    COSY_REQUIRE(host_cand_off[0] == 0 && host_obj_off[0] == 0 && host_view_off[0] == 0, "cosy_ba_batch_upload: offsets start at %d, %d, %d",
+                 host_cand_off[0], host_obj_off[0], host_view_off[0]);
+    long long a_sum = 0;
+    int blocks_max = 0;
+    for (int g = 0; g < G; ++g) {
+        const long long nc = (long long)host_cand_off[g + 1] - host_cand_off[g], no = (long long)host_obj_off[g + 1] - host_obj_off[g],
+                        nv = (long long)host_view_off[g + 1] - host_view_off[g];
+        COSY_REQUIRE(nc > 0 && no > 0 && nv > 0, "cosy_ba_batch_upload: problem %d: %lld candidates, %lld objects, %lld views", g, nc, no, nv);
+        if (no + nv > BA_MAX_N / 9) {
+            cosy::set_error("cosy_ba_batch_upload: problem %d: n_obj + n_views = %lld > %d", g, no + nv, BA_MAX_N / 9);
+            return COSY_ESIZE;
+        }
+        a_sum += 81 * (no + nv) * (no + nv);
+        if (no + nv > blocks_max) blocks_max = (int)(no + nv);
+    }
+    const int n_cand = host_cand_off[G], n_obj = host_obj_off[G];
+    for (int g = 0; g < G; ++g)
+        for (int c = host_cand_off[g]; c < host_cand_off[g + 1]; ++c) {
+            COSY_REQUIRE(host_cand_obj[c] >= host_obj_off[g] && host_cand_obj[c] < host_obj_off[g + 1],
+                         "cosy_ba_batch_upload: problem %d, candidate %d: object row %d outside [%d, %d)", g, c, host_cand_obj[c],
+                         host_obj_off[g], host_obj_off[g + 1]);
+            COSY_REQUIRE(host_cand_view[c] >= host_view_off[g] && host_cand_view[c] < host_view_off[g + 1],
+                         "cosy_ba_batch_upload: problem %d, candidate %d: view row %d outside [%d, %d)", g, c, host_cand_view[c],
+                         host_view_off[g], host_view_off[g + 1]);
+            COSY_REQUIRE(host_cand_mesh[c] >= 0 && host_cand_mesh[c] < n_mesh,
+                         "cosy_ba_batch_upload: problem %d, candidate %d: mesh id %d outside [0, %d)", g, c, host_cand_mesh[c], n_mesh);
+        }
+    for (int o = 0; o < n_obj; ++o)
+        COSY_REQUIRE(host_obj_mesh[o] >= 0 && host_obj_mesh[o] < n_mesh, "cosy_ba_batch_upload: object %d: mesh id %d outside [0, %d)", o,
+                     host_obj_mesh[o], n_mesh);
+    // the whole table in one host block, one copy
+    const size_t n_ints = ba_tab_ints(G, n_cand, n_obj), bytes = cosy_ba_batch_table_bytes(G, n_cand, n_obj);
+    int* host = (int*)calloc(1, bytes);
+    COSY_REQUIRE(host, "cosy_ba_batch_upload: out of host memory (%zu bytes)", bytes);
+    int* w = host;
+    memcpy(w, host_cand_obj, (size_t)n_cand * sizeof(int)); w += n_cand;
+    memcpy(w, host_cand_view, (size_t)n_cand * sizeof(int)); w += n_cand;
+    memcpy(w, host_cand_mesh, (size_t)n_cand * sizeof(int)); w += n_cand;
+    for (int g = 0; g < G; ++g)
+        for (int c = host_cand_off[g]; c < host_cand_off[g + 1]; ++c) w[c] = g;
+    w += n_cand;
+    memcpy(w, host_obj_mesh, (size_t)n_obj * sizeof(int)); w += n_obj;
+    memcpy(w, host_cand_off, ((size_t)G + 1) * sizeof(int)); w += G + 1;
+    memcpy(w, host_obj_off, ((size_t)G + 1) * sizeof(int)); w += G + 1;
+    memcpy(w, host_view_off, ((size_t)G + 1) * sizeof(int));
+    long long* a_off = (long long*)(host + n_ints);
+    a_off[0] = 0;
+    for (int g = 0; g < G; ++g) {
+        const long long nb = ((long long)host_obj_off[g + 1] - host_obj_off[g]) + ((long long)host_view_off[g + 1] - host_view_off[g]);
+        a_off[g + 1] = a_off[g] + 81 * nb * nb;
+    }
+    hipError_t e = hipMemcpyAsync(table, host, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);     // `host` is freed below
+    free(host);
+    COSY_CHECK_HIP(e);
+    *a_total = a_sum;
+    *max_blocks = blocks_max;
+    return COSY_OK;
+}
+
+int cosy_ba_batch_linearize(const cosy_ba_batch_t* batch, int which, cosy_stream_t stream) {
+    const int rc = ba_batch_check(batch, "cosy_ba_batch_linearize");
+    if (rc != COSY_OK) return rc;
+    COSY_REQUIRE(which == 0 || which == 1, "cosy_ba_batch_linearize: which=%d", which);
+    return ba_batch_linearize_launch(batch, which, (hipStream_t)stream);
+}
+
+int cosy_ba_batch_solve_step(const cosy_ba_batch_t* batch, cosy_stream_t stream) {
+    const int rc = ba_batch_check(batch, "cosy_ba_batch_solve_step");
+    if (rc != COSY_OK) return rc;
+    return ba_batch_solve_step_launch(batch, (hipStream_t)stream);
+}
+
+int cosy_ba_batch_record(cosy_ba_ctrl_t* ctrl, int G, int iteration, int n_hist_rows, const void* table, int n_cand, int n_obj,
+                         int n_views, const double* TWO_9d, const double* TCW_9d, int* hist_iteration, double* hist_lambda,
+                         double* hist_loss, double* hist_TWO_9d, double* hist_TCW_9d, cosy_stream_t stream) {
+    COSY_REQUIRE(G > 0 && iteration >= 0 && n_hist_rows > 0, "cosy_ba_batch_record: G=%d iteration=%d n_hist_rows=%d", G, iteration,
+                 n_hist_rows);
+    COSY_REQUIRE(ctrl && hist_iteration && hist_lambda && hist_loss, "cosy_ba_batch_record: null pointer");
+    COSY_REQUIRE(!hist_TWO_9d == !hist_TCW_9d, "cosy_ba_batch_record: hist_TWO_9d and hist_TCW_9d go together");
+    BaTab t = {};
+    if (hist_TWO_9d) {
+        COSY_REQUIRE(table && TWO_9d && TCW_9d && n_cand > 0 && n_obj > 0 && n_views > 0,
+                     "cosy_ba_batch_record: a state history needs the table and the states (n_cand=%d n_obj=%d n_views=%d)", n_cand, n_obj,
+                     n_views);
+        t = ba_tab(table, G, n_cand, n_obj);
+    }
+    hipLaunchKernelGGL(ba_batch_record_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, t, ctrl, iteration, n_hist_rows, n_obj, n_views,
+                       TWO_9d, TCW_9d, hist_iteration, hist_lambda, hist_loss, hist_TWO_9d, hist_TCW_9d);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_ba_batch_decide(cosy_ba_ctrl_t* ctrl, int G, double L_down, double L_up, double eps, const void* table, int n_cand, int n_obj,
+                         double* TWO_9d, double* TCW_9d, const double* TWO_9d_updated, const double* TCW_9d_updated,
+                         cosy_stream_t stream) {
+    COSY_REQUIRE(G > 0 && L_down > 0. && L_up > 0., "cosy_ba_batch_decide: G=%d L_down=%g L_up=%g", G, L_down, L_up);
+    COSY_REQUIRE(ctrl, "cosy_ba_batch_decide: null ctrl");
+    BaTab t = {};
+    if (TWO_9d || TCW_9d || TWO_9d_updated || TCW_9d_updated) {
+        COSY_REQUIRE(table && TWO_9d && TCW_9d && TWO_9d_updated && TCW_9d_updated && n_cand > 0 && n_obj > 0,
+                     "cosy_ba_batch_decide: the states go together with the table (n_cand=%d n_obj=%d)", n_cand, n_obj);
+        t = ba_tab(table, G, n_cand, n_obj);
+    }
+    hipLaunchKernelGGL(ba_batch_decide_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, t, ctrl, L_down, L_up, eps, TWO_9d, TCW_9d,
+                       TWO_9d_updated, TCW_9d_updated);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_ba_batch_iterate(const cosy_ba_batch_t* batch, int n_first, int n_count, cosy_stream_t stream) {
+    const int rc = ba_batch_check(batch, "cosy_ba_batch_iterate");
+    if (rc != COSY_OK) return rc;
+    COSY_REQUIRE(n_first >= 0 && n_count >= 0, "cosy_ba_batch_iterate: n_first=%d n_count=%d", n_first, n_count);
+    const cosy_ba_batch_t* b = batch;
+    for (int n = n_first; n < n_first + n_count; ++n) {
+        int r = ba_batch_linearize_launch(b, 0, (hipStream_t)stream);
+        if (r != COSY_OK) return r;
+        r = cosy_ba_batch_record(b->ctrl, b->G, n, b->n_hist_rows, b->table, b->n_cand, b->n_obj, b->n_views, b->TWO_9d, b->TCW_9d,
+                                 b->hist_iteration, b->hist_lambda, b->hist_loss, b->hist_TWO_9d, b->hist_TCW_9d, stream);
+        if (r != COSY_OK) return r;
+        r = ba_batch_solve_step_launch(b, (hipStream_t)stream);
+        if (r != COSY_OK) return r;
+        r = ba_batch_linearize_launch(b, 1, (hipStream_t)stream);
+        if (r != COSY_OK) return r;
+        r = cosy_ba_batch_decide(b->ctrl, b->G, b->L_down, b->L_up, b->eps, b->table, b->n_cand, b->n_obj, b->TWO_9d, b->TCW_9d,
+                                 b->TWO_9d_updated, b->TCW_9d_updated, stream);
+        if (r != COSY_OK) return r;
+    }
     return COSY_OK;
 }
 

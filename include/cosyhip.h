@@ -470,6 +470,66 @@ int cosy_ba_linearize(const double* TWO_9d, const double* TCW_9d, const double* 
                       cosy_stream_t stream);
 int cosy_ba_solve(const double* A, const double* b, int n, double lambda, double* h, void* workspace, cosy_stream_t stream);
 
+/* ---- batched bundle adjustment: G problems per call, the Levenberg-Marquardt loop (bundle_adjustment.py:238-277) on the device ----
+ * A batch is the concatenation of G problems that share the mesh tables: candidates (n_cand), objects (n_obj) and views (n_views) are
+ * TOTALS over the batch, problem g owns the candidate rows cand_off[g] .. cand_off[g+1], the object rows obj_off[g] .. obj_off[g+1] of
+ * TWO_9d (n_obj,9), the view rows view_off[g] .. view_off[g+1] of TCW_9d / K, and candidates name GLOBAL object and view rows.  Its
+ * unknowns are ordered as in the single problem (its objects, then its views; n_g = 9 blocks_g, blocks_g <= 128), its parameter offset
+ * is 9 (obj_off[g] + view_off[g]) and its A lies at the sum of n_k^2 over the problems before it.
+ *
+ * cosy_ba_batch_upload: checks the HOST tables (offsets start at 0 and rise, every problem has a candidate, an object and a view and
+ *   at most 128 blocks -- COSY_ESIZE beyond --, every id inside ITS problem's rows, mesh ids inside [0, n_mesh)) before anything is
+ *   copied, then writes the device `table` (cosy_ba_batch_table_bytes(G, n_cand, n_obj) bytes: the ids, each candidate's problem, the
+ *   offsets, the A offsets) and waits for the copy; a_total receives the sum of n_g^2, max_blocks the largest blocks_g.
+ * cosy_ba_ctrl_t: the control record of one problem.  loss = the loss at the current state, next_loss = at the updated one.
+ * cosy_ba_batch_linearize: align + linearise + accumulate, one launch each over the batch, at the current (which = 0) or the updated
+ *   (which = 1) states -> the problem's A, b (in the workspace) and ctrl.loss / ctrl.next_loss.  Workgroups of a problem that is
+ *   `finished`, or with which = 0 whose last iteration accepted its step (`prev_update`: A, b and the loss are those of the accepted
+ *   state already), leave at once.  The same device code as cosy_ba_align / cosy_ba_linearize: the same bits.
+ * cosy_ba_batch_solve_step: one workgroup per problem: the Cholesky of cosy_ba_solve on A_g + lambda_g I, then updated = current + h
+ *   (the views' part of h dropped when optimize_cameras = 0).
+ * cosy_ba_batch_record: appends (iteration, lambda, loss and, with hist_TWO_9d / hist_TCW_9d given, the current states) as row n_hist
+ *   of the problem's history -- hist_iteration / hist_lambda / hist_loss (G, n_hist_rows), hist_TWO_9d (n_hist_rows, n_obj, 9),
+ *   hist_TCW_9d (n_hist_rows, n_views, 9) -- and marks the problem `finished` if `done` was set: where the reference appends, then
+ *   breaks.  table and the states may be NULL when no state history is asked for.
+ * cosy_ba_batch_decide: rho = loss - next_loss; |rho| < eps: done = 1, nothing else; else rho > eps: current = updated, loss =
+ *   next_loss, lambda = max(lambda / L_down, 1e-7), prev_update = 1; otherwise (a NaN rho too) lambda = min(lambda L_up, 1e7),
+ *   prev_update = 0.  Finished problems are left alone.  table and the states may be NULL: the records alone are then updated.
+ * cosy_ba_batch_iterate: iterations n_first .. n_first + n_count - 1, each = linearize(0), record(n), solve_step, linearize(1), decide.
+ *   Launches on one stream are the only synchronisation; nothing is read back.
+ * workspace: cosy_ba_batch_workspace_bytes(n_cand, n_obj + n_views, a_total) bytes.  Do not share one between streams. */
+typedef struct {
+    double loss, next_loss, lambda;
+    int done, prev_update, finished, n_hist;
+} cosy_ba_ctrl_t;
+typedef struct {
+    int G, n_cand, n_obj, n_views, n_mesh, P, S, max_blocks, n_hist_rows, optimize_cameras;
+    long long a_total;
+    double residuals_threshold, L_down, L_up, eps;
+    const void* table;
+    const double *cand_TCO, *K, *pts_table, *sym_table;
+    const int* n_sym;
+    double *TWO_9d, *TCW_9d, *TWO_9d_updated, *TCW_9d_updated;
+    cosy_ba_ctrl_t* ctrl;
+    int* hist_iteration;
+    double *hist_lambda, *hist_loss, *hist_TWO_9d, *hist_TCW_9d;
+    void* workspace;
+} cosy_ba_batch_t;
+size_t cosy_ba_batch_table_bytes(int G, int n_cand, int n_obj);
+size_t cosy_ba_batch_workspace_bytes(int n_cand, int n_blocks, long long a_total);
+int cosy_ba_batch_upload(const int* host_cand_obj, const int* host_cand_view, const int* host_cand_mesh, const int* host_obj_mesh,
+                         const int* host_cand_off, const int* host_obj_off, const int* host_view_off, int G, int n_mesh, void* table,
+                         long long* a_total, int* max_blocks, cosy_stream_t stream);
+int cosy_ba_batch_linearize(const cosy_ba_batch_t* batch, int which, cosy_stream_t stream);
+int cosy_ba_batch_solve_step(const cosy_ba_batch_t* batch, cosy_stream_t stream);
+int cosy_ba_batch_record(cosy_ba_ctrl_t* ctrl, int G, int iteration, int n_hist_rows, const void* table, int n_cand, int n_obj,
+                         int n_views, const double* TWO_9d, const double* TCW_9d, int* hist_iteration, double* hist_lambda,
+                         double* hist_loss, double* hist_TWO_9d, double* hist_TCW_9d, cosy_stream_t stream);
+int cosy_ba_batch_decide(cosy_ba_ctrl_t* ctrl, int G, double L_down, double L_up, double eps, const void* table, int n_cand, int n_obj,
+                         double* TWO_9d, double* TCW_9d, const double* TWO_9d_updated, const double* TCW_9d_updated,
+                         cosy_stream_t stream);
+int cosy_ba_batch_iterate(const cosy_ba_batch_t* batch, int n_first, int n_count, cosy_stream_t stream);
+
 /* ---- multi-view candidate matching, CosyPose stage 2 (cosypose/multiview/ransac.py:19-88, csrc/cosypose_cext.cpp:107-216), float32 ----
  * The scene: cand_poses (n_cand,4,4) TCO of every candidate, cand_mesh (n_cand) int32 row of its label in pts_table (n_mesh,P,3) /
  * sym_table (n_mesh,S,4,4, identity-padded) / n_sym (n_mesh) int32.  Tentative matches are stored once per ORDERED view pair, not per
