@@ -1397,12 +1397,14 @@ int cosy_wgrad(const float* dY, const float* X, long M, int N, int K, float* dW,
 }
 
 // out (M,N) = A (M,K) . op(W) (+ add): op(W) = W^T for W stored (N,K) (a 1x1 convolution's forward), W for W stored (K,N)
-// (its data gradient: dX = dY . W).  fp32 MFMA through pw_gemm with an identity epilogue; K % 4 == 0 (16-byte rows).
+// (its data gradient: dX = dY . W).  fp32 MFMA through pw_gemm with an identity epilogue; K % 8 == 0 and N % 8 == 0 (launch_pw_gemm's
+// own rule, checked here before the pack kernel is launched).
 int cosy_train_gemm(const float* A, const float* W, int w_is_kn, long M, int K, int N, const float* add, float* out, void* workspace,
                     cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(A && W && out && workspace && M > 0 && K > 0 && N > 0, "train_gemm: bad argument M=%ld K=%d N=%d", M, K, N);
-    COSY_REQUIRE(K % 4 == 0 && N % 4 == 0 && M < (1l << 31), "train_gemm: K=%d and N=%d must be multiples of 4", K, N);
+    COSY_REQUIRE(K % 8 == 0 && N % 8 == 0, "train_gemm: K=%d and N=%d must be multiples of 8", K, N);
+    COSY_REQUIRE(M < (1l << 31), "train_gemm: M=%ld exceeds the 32-bit row index", M);
     const PwCfg cfg = pw_choose_cfg(N);
     const size_t packed = pw_packed_elems(K, N, cfg, COSY_F32);
     const int n_pad = cdiv(N, pw_bn(cfg)) * pw_bn(cfg);
@@ -1427,7 +1429,8 @@ int cosy_train_pack_plan(int n, const float* const* W, const int* K, const int* 
     COSY_REQUIRE(n > 0 && W && K && N && w_is_kn && plan && pool_floats && n_blocks, "train_pack_plan: null argument");
     long long off = PACK_HEAD_FLOATS, blk = PACK_HEAD_BLOCKS;
     for (int e = 0; e < n; ++e) {
-        COSY_REQUIRE(W[e] && K[e] > 0 && N[e] > 0 && K[e] % 4 == 0 && N[e] % 4 == 0, "train_pack_plan: entry %d: K=%d N=%d", e, K[e], N[e]);
+        COSY_REQUIRE(W[e] && K[e] > 0 && N[e] > 0, "train_pack_plan: entry %d: bad argument K=%d N=%d", e, K[e], N[e]);
+        COSY_REQUIRE(K[e] % 8 == 0 && N[e] % 8 == 0, "train_pack_plan: entry %d: K=%d and N=%d must be multiples of 8", e, K[e], N[e]);
         const PwCfg cfg = pw_choose_cfg(N[e]);
         const size_t packed = pw_packed_elems(K[e], N[e], cfg, COSY_F32);
         COSY_REQUIRE(cdiv(N[e], pw_bn(cfg)) * pw_bn(cfg) <= PACK_HEAD_N, "train_pack_plan: N=%d exceeds the shared epilogue arrays", N[e]);
@@ -1451,7 +1454,8 @@ int cosy_train_pack_all(const long long* plan_dev, int n, long long n_blocks, fl
 int cosy_train_gemm_packed(const float* A, const float* pool, long long packed_offset, long M, int K, int N, const float* add, float* out,
                            cosy_stream_t stream) {
     COSY_REQUIRE(A && pool && out && packed_offset >= PACK_HEAD_FLOATS && M > 0 && K > 0 && N > 0, "train_gemm_packed: bad argument M=%ld K=%d N=%d", M, K, N);
-    COSY_REQUIRE(K % 4 == 0 && N % 4 == 0 && M < (1l << 31), "train_gemm_packed: K=%d and N=%d must be multiples of 4", K, N);
+    COSY_REQUIRE(K % 8 == 0 && N % 8 == 0, "train_gemm_packed: K=%d and N=%d must be multiples of 8", K, N);
+    COSY_REQUIRE(M < (1l << 31), "train_gemm_packed: M=%ld exceeds the 32-bit row index", M);
     const PwCfg cfg = pw_choose_cfg(N);
     PwArgs a{};
     a.A = A; a.Wp = pool + packed_offset; a.out = out; a.scale = pool; a.bias = pool + PACK_HEAD_N; a.res = add; a.gate = nullptr;

@@ -206,7 +206,8 @@ def wgrad(dY, X, out=None):
 def gemm(A, W, w_is_kn=False, add=None, packed=None):
     """A (M,K) @ W^T for W (N,K)  [w_is_kn=False: a 1x1 convolution's forward]  or  A (M,K) @ W for W (K,N)  [w_is_kn=True: its
     data gradient], plus `add` (M,N): the library's own fp32 MFMA GEMM (cosy_train_gemm), no rocBLAS.  packed: a PackedWeights holding
-    W in this orientation (packed at the top of the step with every other weight) -- without it the weight is packed by a launch of its own."""
+    W in this orientation (packed at the top of the step with every other weight) -- without it the weight is packed by a launch of its own.
+    K and N must be multiples of 8 (the tile kernel's rule; anything else is refused before a launch); M is free."""
     M, K = A.shape
     N = W.shape[1] if w_is_kn else W.shape[0]
     assert W.shape == ((K, N) if w_is_kn else (N, K)) and A.is_contiguous() and W.is_contiguous()

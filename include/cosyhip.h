@@ -279,7 +279,8 @@ int cosy_dw_train_backward_weight_ex(const float* x, const float* dy, int B, int
 /* 1x1 convolutions of the training step on the library's own fp32 MFMA GEMMs (no rocBLAS on the path):
  *   cosy_train_gemm: out (M,N) = A (M,K) . op(W) (+ add (M,N)); op(W) = W^T for W stored (N,K) [w_is_kn = 0: the forward of
  *                    F.conv2d with a 1x1 kernel, efficientnet.py:81,90,188], W for W stored (K,N) [w_is_kn = 1: the data
- *                    gradient dX = dY . W].  K and N multiples of 4.  The weights are packed on the device per call.
+ *                    gradient dX = dY . W].  K and N multiples of 8 (anything else: COSY_EINVAL before a launch; the same rule
+ *                    holds for cosy_train_pack_plan and cosy_train_gemm_packed).  The weights are packed on the device per call.
  *   cosy_wgrad:      dW (N,K) = dY^T (N,M) . X (M,K), dY (M,N), X (M,K) row-major, any shape; deterministic (fixed-order
  *                    combine of per-slab partial tiles).
  * cosy_wgrad_tall / _supported are round 1's names for the same kernel (kept: every shape is supported now). */

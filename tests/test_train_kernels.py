@@ -1,8 +1,10 @@
 """Kernel-level parity of the training step (csrc/kernels_train.hip) against float64 torch on the CPU.
 
 The end-to-end training tests (test_gpu_parity.py: test_training_step_vs_reference, ..._with_drop_connect, ..._batch64_vs_oracle)
-run one crop size and judge 340 gradient tensors after 26 blocks of error build-up.  Here every training entry of the C ABI is
-held on its own: the reference restates the OPERATION in float64 with stock torch on the CPU (F.conv2d on the statically padded
+run one crop size and judge 340 gradient tensors after 26 blocks of error build-up.  Here the training entries of the C ABI are
+held on their own, except those that run on the matrix instruction, which live in test_train_matrix_kernels.py (cosy_train_gemm,
+cosy_train_gemm_packed with cosy_train_pack_plan / _pack_all, cosy_wgrad, cosy_se_train_forward / _backward, cosy_fc_small_forward /
+_backward, cosy_rows_mean_bn / cosy_rows_dot_bn).  The reference restates the OPERATION in float64 with stock torch on the CPU (F.conv2d on the statically padded
 input, F.batch_norm + x * sigmoid(x) with autograd, clip_grad_norm_ + Adam, TorchRef.disentangled_loss with autograd), from the
 same fp32 inputs the kernel gets, at the network's 14 depthwise shape classes (EfficientNet-B3 at 240x320) and 256x256's 8x8
 maps, plus ragged shapes where the kernels' tails live (Ho % 4 != 0 for the 4-row depthwise threads, Wo % 4 != 0 for the 4-pixel
