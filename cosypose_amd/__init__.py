@@ -61,4 +61,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('mask_instance_stats', 'make_detections_from_segmentation', 'visible_ids', 'instance_masks', 'detection_targets'):
         from . import mask_ops
         return getattr(mask_ops, name)
+    if name in ('gt_info', 'annotate_gt'):
+        from . import gt_annotations
+        return getattr(gt_annotations, name)
     raise AttributeError(name)

@@ -11,6 +11,9 @@ Poses <-> BOP result files.  Contract of cosypose/scripts/run_custom_scenario.py
 `scene_id,im_id,obj_id,score,R,t,time` with R row-major, t in millimetres, both space separated (the writer itself is
 bop_toolkit_lib.inout.save_bop_results, third-party); the reader returns infos [view_id, scene_id, score, label] with
 label 'obj_%06d' and poses in metres.
+
+Ground-truth annotations -> scene_gt_info.json.  Format of the BOP toolkit's calc_gt_info.py (third-party; what
+cosypose/datasets/bop.py:124-126 reads back): per image a list with one dict per annotated instance, in annotation order.
 """
 
 import numpy as np
@@ -72,6 +75,22 @@ def save_bop_results(path, rows):
     body = [f"{r['scene_id']},{r['im_id']},{r['obj_id']},{r['score']},{fmt(r['R'])},{fmt(r['t'])},{r.get('time', -1)}" for r in rows]
     with open(path, 'w') as f:
         f.write('\n'.join([BOP19_HEADER] + body))
+
+
+def scene_gt_info_rows(annotated):
+    """The annotations of gt_annotations.annotate_gt (infos: scene_id, view_id and the count columns; tensors bbox_obj, bbox_visib) as
+    {(scene_id, view_id): [dict(bbox_obj, bbox_visib, px_count_all, px_count_valid, px_count_visib, visib_fract), ...]}, rows in
+    annotation order, plain Python ints and floats: what scene_gt_info.json holds per image."""
+    boxes = torch.stack([annotated.bbox_obj, annotated.bbox_visib], 1).detach().cpu().numpy()      # ONE device -> host copy
+    info = annotated.infos
+    out = {}
+    for i in range(len(info)):
+        key = (int(info['scene_id'].iloc[i]), int(info['view_id'].iloc[i]))
+        out.setdefault(key, []).append(dict(
+            bbox_obj=[int(v) for v in boxes[i, 0]], bbox_visib=[int(v) for v in boxes[i, 1]], px_count_all=int(info['px_count_all'].iloc[i]),
+            px_count_valid=int(info['px_count_valid'].iloc[i]), px_count_visib=int(info['px_count_visib'].iloc[i]),
+            visib_fract=float(info['visib_fract'].iloc[i])))
+    return out
 
 
 def tc_to_csv(predictions, csv_path):

@@ -11,9 +11,10 @@ VALUES are parity-unpinned as there (PyBullet's OpenGL shading is third-party).
 host interface on top of it, `scene_visibility` the companion of MultiviewScenePredictor.reproject_scene: which object is seen in
 which view, and how much of it.
 
-"Visible" here means: the pixel is won by the instance in the rendered scene's z-buffer.  BOP's dataset tool additionally compares
-with the SENSOR depth under a 15 mm tolerance; there is no sensor depth here, so an instance hidden by something that is not part of
-the scene counts as visible.
+"Visible" here means: the pixel is won by the instance in the rendered scene's z-buffer.  BOP's dataset tool compares with the SENSOR
+depth under a 15 mm tolerance instead and counts the part of the silhouette outside the frame: that is cosypose_amd.gt_info /
+annotate_gt (gt_annotations.py), which take a measured depth frame -- or, for a scene without a sensor, this renderer's own
+render(..., render_depth=True)['depth'].
 """
 import ctypes
 

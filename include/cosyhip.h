@@ -632,6 +632,33 @@ int cosy_bop_vsd_counts(const int* est_inst, const int* gt_inst, const int* inst
                         int N, int n_views, int n_tau, int H, int W, int* counts, void* workspace, size_t workspace_bytes,
                         cosy_stream_t stream);
 
+/* ---- BOP ground-truth annotations: what the BOP toolkit's calc_gt_masks.py / calc_gt_info.py write ----
+ * Every instance is drawn alone on a canvas of 3H x 3W whose centre third is the (H,W) frame: the caller forms K' = K with cx + W and
+ * cy + H (one float32 addition each) and calls cosy_bop_instance_boxes and cosy_bop_render_windows with K' and (3H, 3W).
+ * cosy_gt_info then reads boxes (N,4) and win_offset (N) as those two left them, windows = the store of n_pixels floats, inst_view (N)
+ * the row of every instance in depth_test (n_views,H,W) (measured depth in metres, 0 = missing) and in K (n_views,3,3), the UNSHIFTED
+ * intrinsics, and id_in_segm (N) in [1, 255].  With dist() of section 15 in the frame's coordinates (x = x_canvas - W, y = y_canvas - H),
+ * dist_gt of the window depth and t of depth_test:  mask = dist_gt > 0;  V = mask and (dist_gt - t <= delta or t == 0); a NaN in
+ * depth_test fails every comparison.  Written in full for every n < N:
+ *   counts (N,3) int32 = px_count_all (depth > 0 on the whole canvas), px_count_valid (mask and t > 0), px_count_visib (V);
+ *   bbox_obj (N,4) int32 = x, y, w, h of {depth > 0} on the canvas in the frame's coordinates (x, y may be negative, w = max - min);
+ *   bbox_visib (N,4) the same of V; both -1, -1, -1, -1 where px_count_visib = 0.
+ * Accumulated into (the caller zeroes them once, chunks of instances then share them): composite (n_views,H,W) int32 = the largest
+ * id_in_segm whose V holds the pixel; mask, mask_visib (N,H,W) uint8 0 / 1, both optional (null: not written), stored on the part of
+ * the frame the instance's window covers.  cosy_gt_composite_u8 narrows n words of the composite to bytes.
+ * Checked on the host before any launch (COSY_EINVAL, cosy_last_error() names the argument): N, n_pixels >= 0, n_views, H, W > 0 with
+ * 9 H W and N ceil(9 H W / 2048) < 2^31, every pointer that is read or written non-null (windows only when n_pixels > 0), workspace
+ * 16-byte aligned and at least cosy_gt_info_workspace_bytes(N); N = 0 (n = 0) returns COSY_OK at once with null pointers.  Checked on
+ * the device, where the boxes are: an instance whose box is empty or dead (x1 = -2), whose view lies outside [0, n_views), or whose
+ * window does not lie inside the n_pixels of the store as a whole reads nothing and gets zero counts and -1 boxes.  Integer atomics
+ * only: equal inputs give equal bytes, and an instance's rows do not depend on what else is in the call. */
+size_t cosy_gt_info_workspace_bytes(int N);
+int cosy_gt_info(const int* inst_view, const int* id_in_segm, const int* boxes, const long long* win_offset, const float* windows,
+                 long long n_pixels, const float* depth_test, const float* K, float delta, int N, int n_views, int H, int W, int* counts,
+                 int* bbox_obj, int* bbox_visib, int* composite, unsigned char* mask, unsigned char* mask_visib, void* workspace,
+                 size_t workspace_bytes, cosy_stream_t stream);
+int cosy_gt_composite_u8(const int* composite, long long n, unsigned char* out, cosy_stream_t stream);
+
 /* ---- detection side: instance-id masks -> counts, boxes and binary masks; box IoU (cosypose/datasets/utils.py:27-40,
  * datasets/detection_dataset.py:61-80, evaluation/meters/detection_meters.py:31-35) ----
  * masks (B,H,W) of uint8 (COSY_MASK_U8) or int32 (COSY_MASK_I32), contiguous; the base address needs the element's alignment only and
