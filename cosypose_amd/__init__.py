@@ -16,6 +16,12 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == 'BatchedMeshes':
         from .mesh_db import BatchedMeshes
         return BatchedMeshes
+    if name in ('MeshDataBase', 'make_bop_symmetries'):
+        from . import mesh_db
+        return getattr(mesh_db, name)
+    if name == 'model_info':      # the function and its module share the name, as bop_errors: the module is callable
+        import importlib
+        return importlib.import_module('.model_info', __name__)
     if name in ('HipBatchRenderer', 'RenderMeshes'):
         from . import rasterizer
         return getattr(rasterizer, name)

@@ -120,6 +120,8 @@ _SIGNATURES = {
     'cosy_gt_info_workspace_bytes': ([_I], _SZ),
     'cosy_gt_info': ([_P, _P, _P, _P, _P, _c.c_longlong, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P], _I),
     'cosy_gt_composite_u8': ([_P, _c.c_longlong, _P, _P], _I),
+    'cosy_model_info_workspace_bytes': ([_P, _I], _SZ),
+    'cosy_model_info': ([_P, _I, _P, _P, _I, _P, _P, _SZ, _P], _I),
     'cosy_mask_instance_stats': ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
     'cosy_instance_masks': ([_P, _I, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     'cosy_box_iou_pairs': ([_P, _P, _I, _P, _P], _I),

@@ -14,6 +14,10 @@ label 'obj_%06d' and poses in metres.
 
 Ground-truth annotations -> scene_gt_info.json.  Format of the BOP toolkit's calc_gt_info.py (third-party; what
 cosypose/datasets/bop.py:124-126 reads back): per image a list with one dict per annotated instance, in annotation order.
+
+Object models -> models_info.json.  Format of the BOP toolkit's calc_model_info.py (third-party; what
+cosypose/datasets/bop_object_datasets.py:8-29 reads back): per object id a dict with diameter, min_* and size_* in the model's units
+and, where the object has them, symmetries_discrete and symmetries_continuous.
 """
 
 import numpy as np
@@ -90,6 +94,25 @@ def scene_gt_info_rows(annotated):
             bbox_obj=[int(v) for v in boxes[i, 0]], bbox_visib=[int(v) for v in boxes[i, 1]], px_count_all=int(info['px_count_all'].iloc[i]),
             px_count_valid=int(info['px_count_valid'].iloc[i]), px_count_visib=int(info['px_count_visib'].iloc[i]),
             visib_fract=float(info['visib_fract'].iloc[i])))
+    return out
+
+
+def models_info_rows(infos, obj_ids, symmetries_discrete=None, symmetries_continuous=None):
+    """The dicts of model_info.model_info (one per object, in the order of obj_ids) as {str(obj_id): dict(diameter, min_x, min_y, min_z,
+    size_x, size_y, size_z[, symmetries_discrete][, symmetries_continuous])}, plain Python floats and lists: what models_info.json holds
+    (json.dump writes the keys as the strings they are here).  symmetries_discrete / symmetries_continuous: {obj_id: list} of the
+    objects that have them -- 16 numbers per discrete symmetry, dict(axis, offset) per continuous one; an empty list is left out, as the
+    toolkit's files do.  diameter_ids is not part of the file."""
+    assert len(infos) == len(obj_ids) and len(set(int(o) for o in obj_ids)) == len(obj_ids)
+    out = {}
+    for info, obj_id in zip(infos, obj_ids):
+        row = {k: float(info[k]) for k in ('diameter', 'min_x', 'min_y', 'min_z', 'size_x', 'size_y', 'size_z')}
+        for key, table in (('symmetries_discrete', symmetries_discrete), ('symmetries_continuous', symmetries_continuous)):
+            syms = (table or {}).get(int(obj_id), [])
+            if len(syms) > 0:
+                row[key] = [{k: [float(x) for x in v] for k, v in s.items()} if isinstance(s, dict) else [float(x) for x in np.asarray(s).reshape(-1)]
+                            for s in syms]
+        out[str(int(obj_id))] = row
     return out
 
 

@@ -659,6 +659,39 @@ int cosy_gt_info(const int* inst_view, const int* id_in_segm, const int* boxes, 
                  size_t workspace_bytes, cosy_stream_t stream);
 int cosy_gt_composite_u8(const int* composite, long long n, unsigned char* out, cosy_stream_t stream);
 
+/* ---- object models: what the BOP toolkit's calc_model_info.py writes per model -- the diameter (misc.calc_pts_diameter: the largest
+ * distance between two vertices), the axis-aligned box (misc.calc_3d_bbox) -- for a ragged batch of models ----
+ * verts: the vertices of all models one after the other, (sum V, 3) row-major, float32 (elem_bytes = 4) or float64 (elem_bytes = 8), in
+ * the model's own units; offsets (n + 1) int64 on the DEVICE and host_offsets, the same numbers on the HOST (they size the grid and the
+ * workspace and are checked there): model m owns the vertices [offsets[m], offsets[m + 1]), 1 <= V_m < 2^31, and verts holds
+ * host_offsets[n] vertices.  out (n) records, written in full for every model:
+ *   s_max   the largest SQUARED distance over all vertex pairs, float64, computed as ((dx dx + dy dy) + dz dz) with dx = x_i - x_j formed
+ *           in float64 (float32 input is widened first) and every operation rounded on its own: no fused multiply-add, not the form
+ *           |a|^2 + |b|^2 - 2 a.b.  Bit-equal to the square of SciPy's cdist; the diameter is the caller's sqrt(s_max) on the host;
+ *   i, j    i < j: of all pairs that attain s_max the lexicographically smallest, vertex numbers within the model; the same from run to
+ *           run and whatever else is in the call.  V = 1: s_max = 0, i = j = 0.  A pair with a NaN distance never wins;
+ *   min, max  per axis over the model's vertices, float64 (NaN coordinates are skipped); the caller forms size = max - min;
+ *   n_bad   the number of non-finite coordinates (NaN, +-inf) of the model: the caller refuses the model when it is not 0.
+ * Three launches (tile plan, vertex-pair tiles of 512 x 512 over the upper triangle of every model in ONE grid, per-model merge), plain
+ * stores only, no atomics: every tile leaves its winner in the workspace, and a model's tiles are merged under one total order (larger s,
+ * smaller i, smaller j).  workspace: 16-byte aligned, at least cosy_model_info_workspace_bytes(host_offsets, n) = 8 (n + 1) rounded up to
+ * 16, plus 16 bytes per tile; that function returns 0 for n <= 0 and for offsets the call would refuse.
+ * Checked on the host before any launch (COSY_EINVAL, cosy_last_error() names the argument): n >= 0, elem_bytes 4 or 8, non-null
+ * pointers, host_offsets[0] >= 0 and 1 <= V_m < 2^31, verts aligned to its elements, out to 8 bytes, the workspace's size and alignment;
+ * n = 0 returns COSY_OK at once with null pointers.  Checked on the device, where the offsets are read: a model whose device offsets are
+ * not 0 <= offsets[m] <= offsets[m + 1] <= host_offsets[n] reads no vertex and gets s_max = 0, i = j = 0, an empty box (min = +inf,
+ * max = -inf) and n_bad = -1; device offsets that give more tiles than the host's leave the surplus tiles out (no access outside the
+ * workspace), so the two arrays must agree for a meaningful result. */
+typedef struct cosy_model_record {
+    double s_max;
+    double min[3], max[3];
+    int i, j;
+    long long n_bad; /* 72 bytes per model */
+} cosy_model_info_t;
+size_t cosy_model_info_workspace_bytes(const long long* host_offsets, int n);
+int cosy_model_info(const void* verts, int elem_bytes, const long long* offsets, const long long* host_offsets, int n, cosy_model_info_t* out,
+                    void* workspace, size_t workspace_bytes, cosy_stream_t stream);
+
 /* ---- detection side: instance-id masks -> counts, boxes and binary masks; box IoU (cosypose/datasets/utils.py:27-40,
  * datasets/detection_dataset.py:61-80, evaluation/meters/detection_meters.py:31-35) ----
  * masks (B,H,W) of uint8 (COSY_MASK_U8) or int32 (COSY_MASK_I32), contiguous; the base address needs the element's alignment only and
