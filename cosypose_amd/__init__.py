@@ -67,6 +67,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('mask_instance_stats', 'make_detections_from_segmentation', 'visible_ids', 'instance_masks', 'detection_targets'):
         from . import mask_ops
         return getattr(mask_ops, name)
+    if name in ('nms', 'batched_nms', 'postprocess_detections', 'paste_masks', 'detections_from_heads'):
+        from . import detector
+        return getattr(detector, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

@@ -126,6 +126,12 @@ _SIGNATURES = {
     'cosy_instance_masks': ([_P, _I, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     'cosy_box_iou_pairs': ([_P, _P, _I, _P, _P], _I),
     'cosy_box_iou_matrix': ([_P, _P, _I, _I, _P, _P], _I),
+    'cosy_nms_max_candidates': ([], _I),
+    'cosy_det_decode': ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_nms_mask': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P], _I),
+    'cosy_nms_scan': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    'cosy_det_gather': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    'cosy_paste_masks': ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
     'cosy_resize_ksize': ([_I, _I, _I], _I),
     'cosy_resize_coeffs': ([_I, _I, _I, _P, _P, _SZ], _I),
     'cosy_resize_workspace_bytes': ([_I, _I, _I, _I], _SZ),

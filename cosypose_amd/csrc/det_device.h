@@ -1,0 +1,26 @@
+// Box IoU with torchvision.ops.box_iou's float32 arithmetic, shared by kernels_det.hip (box_iou / box_iou_pairs) and kernels_detpost.hip
+// (the suppression matrix of NMS): one definition, so a keep set of NMS is decided by exactly the bits box_iou returns.
+// Every operation is rounded to float32 on its own; both files are compiled with contraction off.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace cosy {
+
+// torch.max / torch.min / clamp(min=0): a NaN operand gives NaN (fmaxf / fminf would drop it)
+__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : b != b ? b : a > b ? a : b; }
+__device__ __forceinline__ float min_nan(float a, float b) { return a != a ? a : b != b ? b : a < b ? a : b; }
+__device__ __forceinline__ float clamp0_nan(float a) { return a != a ? a : a < 0.f ? 0.f : a; }
+
+struct Box { float x1, y1, x2, y2; };
+
+// torchvision.ops.box_iou, every operation rounded to float32 on its own
+__device__ __forceinline__ float box_iou(const Box& a, const Box& b) {
+    const float area_a = __fmul_rn(__fsub_rn(a.x2, a.x1), __fsub_rn(a.y2, a.y1));
+    const float area_b = __fmul_rn(__fsub_rn(b.x2, b.x1), __fsub_rn(b.y2, b.y1));
+    const float w = clamp0_nan(__fsub_rn(min_nan(a.x2, b.x2), max_nan(a.x1, b.x1)));
+    const float h = clamp0_nan(__fsub_rn(min_nan(a.y2, b.y2), max_nan(a.y1, b.y1)));
+    const float inter = __fmul_rn(w, h);
+    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
+}
+
+}  // namespace cosy

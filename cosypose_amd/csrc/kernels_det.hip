@@ -16,6 +16,7 @@
 // one rounding per operation; the file is compiled with contraction off (the pragma below and -ffp-contract=off in build.FILE_FLAGS).
 #include <limits.h>
 #include "cosy_common.h"
+#include "det_device.h"
 
 #pragma clang fp contract(off)
 
@@ -150,13 +151,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_instance_masks_kernel(const T
     *reinterpret_cast<uint4*>(o) = make_uint4(r[0], r[1], r[2], r[3]);
 }
 
-// torch.max / torch.min / clamp(min=0): a NaN operand gives NaN (fmaxf / fminf would drop it)
-__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : b != b ? b : a > b ? a : b; }
-__device__ __forceinline__ float min_nan(float a, float b) { return a != a ? a : b != b ? b : a < b ? a : b; }
-__device__ __forceinline__ float clamp0_nan(float a) { return a != a ? a : a < 0.f ? 0.f : a; }
-
-struct Box { float x1, y1, x2, y2; };
-
+// (Box and box_iou: det_device.h, shared with the NMS of kernels_detpost.hip)
 template <bool ALIGNED>
 __device__ __forceinline__ Box load_box(const float* __restrict__ p, long n) {
     if (ALIGNED) {
@@ -164,16 +159,6 @@ __device__ __forceinline__ Box load_box(const float* __restrict__ p, long n) {
         return {v.x, v.y, v.z, v.w};
     }
     return {p[4 * n], p[4 * n + 1], p[4 * n + 2], p[4 * n + 3]};
-}
-
-// torchvision.ops.box_iou, every operation rounded to float32 on its own
-__device__ __forceinline__ float box_iou(const Box& a, const Box& b) {
-    const float area_a = __fmul_rn(__fsub_rn(a.x2, a.x1), __fsub_rn(a.y2, a.y1));
-    const float area_b = __fmul_rn(__fsub_rn(b.x2, b.x1), __fsub_rn(b.y2, b.y1));
-    const float w = clamp0_nan(__fsub_rn(min_nan(a.x2, b.x2), max_nan(a.x1, b.x1)));
-    const float h = clamp0_nan(__fsub_rn(min_nan(a.y2, b.y2), max_nan(a.y1, b.y1)));
-    const float inter = __fmul_rn(w, h);
-    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
 }
 
 template <bool ALIGNED>

@@ -776,6 +776,53 @@ typedef struct cosy_frame_item {
 int cosy_resize_frames_u8(const cosy_frame_item_t* items, int n, int H, int W, const int* tables, long n_tables, int lut,
                           unsigned char* out_images, unsigned char* out_masks, cosy_stream_t stream);
 
+/* ---- Output side of the detector: the Mask R-CNN heads' raw outputs -> detections (torchvision 0.4.2's roi_heads.postprocess_detections,
+ * ops.batched_nms, GeneralizedRCNNTransform.postprocess, maskrcnn_inference + paste_masks_in_image; cosypose/integrated/detector.py:28-50) ----
+ * DESIGN.md section 21 holds the arithmetic: float32, one rounding per operation.  Every pointer is DEVICE memory.  All functions check on
+ * the host before any launch (COSY_EINVAL, cosy_last_error() names the argument); nothing is allocated.
+ *
+ * Candidates live in a per-image arena of `cap` slots (a multiple of 64 in [64, cosy_nms_max_candidates() = 16384]): slot s of image b is
+ * row b cap + s of cand_boxes (B cap,4), cand_scores, cand_labels (1 .. C-1), cand_src (proposal-in-image (C-1) + label - 1) and cand_keys.
+ *
+ * cosy_det_decode: class_logits (R,C), box_regression (R,4C), proposals (R,4) xyxy of all B images, image b owning rows
+ * [prop_offsets[b], prop_offsets[b+1]) (B+1 int32; a row no image owns is skipped); net_sizes (B,2) float32 = height, width the network
+ * saw.  Softmax, BoxCoder.decode with weights (10,10,5,5) and the log(1000/16) clamp, clip to the image, score > score_thresh, both sides
+ * >= 1e-2.  Survivors take slots in NO particular order; cand_keys (int64) = b << 52 | (0x7fffffff - score bits) << 21 | cand_src, and an
+ * unused slot holds b << 52 | 2^52 - 1: sorting ALL B cap keys ascending lists every image's candidates by descending score, equal scores
+ * by ascending cand_src, and its unused slots after them.  counts (B) = survivors of every image, which MAY EXCEED cap: the ones beyond
+ * it were dropped and the caller must refuse the result.  max_coord (B) = the largest coordinate among an image's candidates (0 without
+ * any).  Limits: 2 <= C <= 4096, B <= 2047, R (C-1) <= 2^21, score_thresh >= 0.  Two launches (initialisation, decode). */
+int cosy_nms_max_candidates(void);
+int cosy_det_decode(const float* class_logits, const float* box_regression, const float* proposals, const int* prop_offsets,
+                    const float* net_sizes, int R, int C, int B, float score_thresh, int cap, float* cand_boxes, float* cand_scores,
+                    int* cand_labels, int* cand_src, long long* cand_keys, int* counts, float* max_coord, cosy_stream_t stream);
+/* Greedy NMS of B segments in one launch each.  Segment b is the rows [seg_start[b], seg_start[b] + min(seg_count[b], cap)) of `order`
+ * (N int64: row -> index into boxes (N,4), labels (N); null = identity), ALREADY sorted by descending score; a segment that does not fit
+ * into [0, N) is treated as empty, an index outside [0, N) as a box that suppresses nothing.  With labels (int32), a box is shifted by
+ * float(label) * (max_coord[b] + 1) before the IoU (batched_nms); without, max_coord may be null.
+ * cosy_nms_mask: mask (B, cap, cap/64) uint64, bit j of word (b, i, c) = "IoU(row i, row 64 c + j) > iou_thresh and 64 c + j > i", written
+ * for the 64 x 64 tiles with c >= i / 64 that hold rows of the segment; the IoU is cosy_box_iou_matrix's, bit for bit.
+ * cosy_nms_scan: walks the rows in order; a row nothing kept before it suppresses is kept, until max_keep are.  kept (B, max_keep) int32
+ * = the kept rows' indices (order[row], or the row) in visiting order, -1 beyond n_kept (B); keep_flags (N uint8, may be null) is zeroed
+ * and set at every kept index. */
+int cosy_nms_mask(const float* boxes, const long long* order, const int* labels, const float* max_coord, const int* seg_start,
+                  const int* seg_count, int B, int N, int cap, float iou_thresh, unsigned long long* mask, cosy_stream_t stream);
+int cosy_nms_scan(const unsigned long long* mask, const long long* order, const int* seg_start, const int* seg_count, int B, int N, int cap,
+                  int max_keep, int* kept, int* n_kept, unsigned char* keep_flags, cosy_stream_t stream);
+/* The kept candidates of an arena (kept, n_kept of cosy_nms_scan with order = the sorted keys' permutation) as B max_keep padded rows:
+ * boxes_net (B max_keep,4) as decoded, boxes_frame = x * ratios[b][0], y * ratios[b][1] (ratios (B,2) float32 = width ratio, height
+ * ratio), src = cand_src; a row past n_kept[b] holds zeros and src -1.  packed (2 B + 2 B max_keep int32) is what the host needs in one
+ * copy: counts (B), n_kept (B), labels (B max_keep, -1 on a padding row), bits of the scores (B max_keep). */
+int cosy_det_gather(const int* kept, const int* n_kept, const int* counts, const float* cand_boxes, const float* cand_scores,
+                    const int* cand_labels, const int* cand_src, const float* ratios, int B, int cap, int max_keep, float* boxes_net,
+                    float* boxes_frame, int* src, int* packed, cosy_stream_t stream);
+/* mask_logits (D,C,M,M), boxes (D,4) xyxy in the frame, labels (D) int32 = channel -> out (D,H,W) uint8 (0 / 1), EVERY byte written:
+ * sigmoid of the label's channel, zero padding of 1, box expanded by (M+2)/M and truncated toward zero, torch's bilinear upsample
+ * (align_corners = False) to the box's integer size, value > mask_th inside the frame, 0 elsewhere and for a label outside [0, C).
+ * 1 <= M <= 62, D <= 65535, H W < 2^30.  One launch. */
+int cosy_paste_masks(const float* mask_logits, const float* boxes, const int* labels, int D, int C, int M, int H, int W, float mask_th,
+                     unsigned char* out, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
