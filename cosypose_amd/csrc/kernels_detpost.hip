@@ -19,7 +19,8 @@
 //                            (x * ratio_w, y * ratio_h), and the small int32 block the host reads (counts, labels, score bits)
 //   paste_masks_kernel<V>    a workgroup owns 16384 consecutive pixels of one detection's (H, W) plane: where they meet the box it stages
 //                            the sigmoid of the label's channel, zero-padded to (M+2)^2, in LDS and writes value > mask_th; everything
-//                            else is written as 0 by the same launch.  V = 16 pixels per 16-byte store where the plane allows it.
+//                            else holds the value 0 and is written as 0 > mask_th by the same launch (false unless mask_th is negative;
+//                            a NaN mask_th makes every pixel false).  V = 16 pixels per 16-byte store where the plane allows it.
 // Integer atomics only (add, max on the bits of non-negative floats): equal inputs give equal bytes.  float32 with one rounding per
 // operation; the file is compiled with contraction off (the pragma below and -ffp-contract=off in build.FILE_FLAGS).
 #include <limits.h>
@@ -97,8 +98,8 @@ __global__ __launch_bounds__(DP_THREADS) void det_decode_kernel(const float* __r
             o.x2 = min_nan(max_nan(__fadd_rn(pcx, hw), 0.f), net_w); o.y2 = min_nan(max_nan(__fadd_rn(pcy, hh), 0.f), net_h);
             emit = score > score_thresh && __fsub_rn(o.x2, o.x1) >= 1e-2f && __fsub_rn(o.y2, o.y1) >= 1e-2f;   // (NaN fails every test)
         }
-        // one atomic per wave and image: the lanes of the leader's image take consecutive slots (a wave spans two images at most
-        // once per boundary, so this loop runs once or twice)
+        // one atomic per wave and image: the lanes of the leader's image take consecutive slots.  The loop runs once per image that has
+        // an emitting lane in this wave: once inside an image, twice across one boundary, up to 64 times where images hold a proposal each
         unsigned long long todo = __ballot(emit);
         while (todo) {
             const int leader = __ffsll((long long)todo) - 1;
@@ -312,6 +313,7 @@ __global__ __launch_bounds__(DP_THREADS) void paste_masks_kernel(const float* __
         __syncthreads();
     }
     const float sx = __fdiv_rn((float)P, (float)bw), sy = __fdiv_rn((float)P, (float)bh);
+    const bool outside = 0.f > mask_th;
     unsigned char* o = out + (size_t)d * plane;
     for (int k = 0; k < PASTE_ITERS; ++k) {
         const long at = chunk0 + ((long)k * DP_THREADS + tid) * V;
@@ -320,13 +322,15 @@ __global__ __launch_bounds__(DP_THREADS) void paste_masks_kernel(const float* __
         unsigned r[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int j = 0; j < V; ++j) {                               // (V = 16 only where plane % 16 == 0: all 16 pixels lie in the plane)
+            bool on = outside;                                      // a pixel the box does not reach holds the value 0
             if (touches && x >= xa && x < xb && y >= ya && y < yb) {
                 const PasteAxis ay = paste_axis(y - by1, sy, P), ax = paste_axis(x - bx1, sx, P);
                 const float top = __fadd_rn(__fmul_rn(ax.l0, sm[ay.i0 * P + ax.i0]), __fmul_rn(ax.l1, sm[ay.i0 * P + ax.i1]));
                 const float bot = __fadd_rn(__fmul_rn(ax.l0, sm[ay.i1 * P + ax.i0]), __fmul_rn(ax.l1, sm[ay.i1 * P + ax.i1]));
                 const float v = __fadd_rn(__fmul_rn(ay.l0, top), __fmul_rn(ay.l1, bot));
-                r[j / 4] |= (unsigned)(v > mask_th) << (8 * (j % 4));
+                on = v > mask_th;
             }
+            r[j / 4] |= (unsigned)on << (8 * (j % 4));
             if (++x == W) { x = 0; ++y; }
         }
         if (V == 16) *reinterpret_cast<uint4*>(o + at) = make_uint4(r[0], r[1], r[2], r[3]);
@@ -357,13 +361,15 @@ int cosy_det_decode(const float* class_logits, const float* box_regression, cons
     COSY_REQUIRE(score_thresh >= 0.f, "cosy_det_decode: score_thresh=%g is negative or NaN", (double)score_thresh);
     if (B == 0) return COSY_OK;
     COSY_REQUIRE_PTR("cosy_det_decode", cand_keys); COSY_REQUIRE_PTR("cosy_det_decode", counts); COSY_REQUIRE_PTR("cosy_det_decode", max_coord);
+    if (R > 0) {                                                   // every check before the first launch: a refused call leaves nothing behind
+        COSY_REQUIRE_PTR("cosy_det_decode", class_logits); COSY_REQUIRE_PTR("cosy_det_decode", box_regression); COSY_REQUIRE_PTR("cosy_det_decode", proposals);
+        COSY_REQUIRE_PTR("cosy_det_decode", prop_offsets); COSY_REQUIRE_PTR("cosy_det_decode", net_sizes);
+        COSY_REQUIRE_PTR("cosy_det_decode", cand_boxes); COSY_REQUIRE_PTR("cosy_det_decode", cand_scores);
+        COSY_REQUIRE_PTR("cosy_det_decode", cand_labels); COSY_REQUIRE_PTR("cosy_det_decode", cand_src);
+    }
     hipLaunchKernelGGL(detpost_init_kernel, dim3(cdiv((long)B * cap, DP_THREADS)), dim3(DP_THREADS), 0, s, cand_keys, counts, (unsigned*)max_coord, B, cap);
     COSY_CHECK_HIP(hipGetLastError());
     if (R == 0) return COSY_OK;
-    COSY_REQUIRE_PTR("cosy_det_decode", class_logits); COSY_REQUIRE_PTR("cosy_det_decode", box_regression); COSY_REQUIRE_PTR("cosy_det_decode", proposals);
-    COSY_REQUIRE_PTR("cosy_det_decode", prop_offsets); COSY_REQUIRE_PTR("cosy_det_decode", net_sizes);
-    COSY_REQUIRE_PTR("cosy_det_decode", cand_boxes); COSY_REQUIRE_PTR("cosy_det_decode", cand_scores);
-    COSY_REQUIRE_PTR("cosy_det_decode", cand_labels); COSY_REQUIRE_PTR("cosy_det_decode", cand_src);
     hipLaunchKernelGGL(det_decode_kernel, dim3(cdiv(R, DP_THREADS)), dim3(DP_THREADS), 0, s, class_logits, box_regression, proposals, prop_offsets,
                        net_sizes, R, C, B, score_thresh, cap, cand_boxes, cand_scores, cand_labels, cand_src, cand_keys, counts, (unsigned*)max_coord);
     COSY_CHECK_HIP(hipGetLastError());

@@ -25,6 +25,9 @@ from . import tensor_collection as tc
 MAX_CANDIDATES = 16384          # cosy_nms_max_candidates()
 DEFAULT_CANDIDATES = 4096
 MAX_MASK_SIDE = 62
+MAX_IMAGES = 2047               # cosy_det_decode's limits: 11 bits of image, 21 bits of candidate index in the sort key
+MAX_CLASSES = 4096
+MAX_CANDIDATE_INDEX = 1 << 21
 
 
 # ---- argument checks: all of them run before the library is loaded -----------------------------------------------------------------
@@ -152,6 +155,13 @@ def _run(class_logits, box_regression, proposals, net_sizes, original_sizes, cou
     C = int(class_logits.shape[1])
     if C < 2:
         raise ValueError(f'class_logits must have a background column and at least one class, got C = {C}')
+    # the sort key's fields (image << 52 | score << 21 | candidate index): refused here, by name, before anything is allocated or launched
+    if B > MAX_IMAGES:
+        raise ValueError(f'{B} images exceed the limit of {MAX_IMAGES} per call')
+    if C > MAX_CLASSES:
+        raise ValueError(f'C = {C} classes exceed the limit of {MAX_CLASSES}')
+    if R * (C - 1) > MAX_CANDIDATE_INDEX:
+        raise ValueError(f'R (C-1) = {R} x {C - 1} = {R * (C - 1)} exceeds the limit of 2^21 = {MAX_CANDIDATE_INDEX} candidate indices per call')
     class_logits = _tensor(class_logits, 'class_logits', (R, C))
     box_regression = _tensor(box_regression, 'box_regression', (R, 4 * C))
     if torch.is_tensor(props) and props.shape[0] != R:
@@ -249,7 +259,9 @@ def postprocess_detections(class_logits, box_regression, proposals, net_sizes, o
 def paste_masks(mask_logits, boxes, labels, frame_size, mask_th=0.8, out=None):
     """maskrcnn_inference + paste_masks_in_image (padding 1) + the threshold: mask_logits (D,C,M,M) float32, boxes (D,4) xyxy float32 in
     the frame, labels (D) int = the channel of every detection (the category id), frame_size (H, W) -> (D,H,W) bool, every pixel
-    written by one launch; the float (D,1,H,W) probabilities are never materialised.  A label outside [0, C) gives an empty mask."""
+    written by one launch; the float (D,1,H,W) probabilities are never materialised.  A pixel outside the box holds the value 0 and is
+    `0 > mask_th` like any other: false for mask_th >= 0, true for a negative one; a NaN mask_th gives all-false masks.  A label outside
+    [0, C) pastes nothing: its whole plane holds 0 (an empty mask for mask_th >= 0)."""
     if not torch.is_tensor(mask_logits) or mask_logits.dim() != 4 or mask_logits.shape[2] != mask_logits.shape[3]:
         raise ValueError(f'mask_logits must be (D,C,M,M), got {tuple(mask_logits.shape) if torch.is_tensor(mask_logits) else type(mask_logits).__name__}')
     D, C, M = int(mask_logits.shape[0]), int(mask_logits.shape[1]), int(mask_logits.shape[2])

@@ -818,7 +818,8 @@ int cosy_det_gather(const int* kept, const int* n_kept, const int* counts, const
                     float* boxes_frame, int* src, int* packed, cosy_stream_t stream);
 /* mask_logits (D,C,M,M), boxes (D,4) xyxy in the frame, labels (D) int32 = channel -> out (D,H,W) uint8 (0 / 1), EVERY byte written:
  * sigmoid of the label's channel, zero padding of 1, box expanded by (M+2)/M and truncated toward zero, torch's bilinear upsample
- * (align_corners = False) to the box's integer size, value > mask_th inside the frame, 0 elsewhere and for a label outside [0, C).
+ * (align_corners = False) to the box's integer size; a pixel the box does not reach, and every pixel of a label outside [0, C), holds the
+ * value 0; out = value > mask_th for all of them (so 0 outside the box unless mask_th is negative; a NaN mask_th gives 0 everywhere).
  * 1 <= M <= 62, D <= 65535, H W < 2^30.  One launch. */
 int cosy_paste_masks(const float* mask_logits, const float* boxes, const int* labels, int D, int C, int M, int H, int W, float mask_th,
                      unsigned char* out, cosy_stream_t stream);

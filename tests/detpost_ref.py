@@ -5,7 +5,12 @@ nothing from cosypose_amd and reads nothing outside tests/.  torchvision itself 
 never been run against it.
 
 float64 variants of the scores (scores64) and of the pasted mask values (paste_values(..., dtype=torch.float64)) exist only to tell
-near-ties: a score next to score_thresh, a mask value next to mask_th."""
+near-ties: a score next to score_thresh, a mask value next to mask_th.
+
+For tests/test_detpost_kernels.py: nms_fast / batched_nms_fast (the same greedy NMS vectorised in numpy float32, so that 16384 boxes take a
+second), decode64 / clip64 (steps 2-3 in float64 with a per-coordinate bound derived from the rounding sequence), paste_value64 (step 8
+evaluated per frame pixel in float64, without F.interpolate: it can state NaN, infinite and clamped boxes), and the seeded inputs of that
+suite, so that test_detector_post_host.py can hold them against their conditions without a device."""
 import math
 
 import numpy as np
@@ -33,7 +38,7 @@ def scores64(class_logits):
 def decode(box_regression, proposals):
     """(R,4C), (R,4) -> (R,C,4), one float32 rounding per operation"""
     rel, p = f32(box_regression), f32(proposals)
-    rel = rel.reshape(p.shape[0], -1, 4)
+    rel = rel.reshape(p.shape[0], rel.shape[-1] // 4, 4)            # (an image without proposals: (0,C,4))
     w, h = p[:, 2] - p[:, 0], p[:, 3] - p[:, 1]
     cx, cy = p[:, 0] + 0.5 * w, p[:, 1] + 0.5 * h
     dx, dy = rel[:, :, 0] / WEIGHTS[0], rel[:, :, 1] / WEIGHTS[1]
@@ -97,6 +102,107 @@ def batched_nms(boxes, scores, idxs, iou_threshold, max_keep=None):
     return nms(boxes + offsets[:, None], scores, iou_threshold, max_keep)
 
 
+def iou_rows_np(a, rest):
+    """box_iou of the float32 box a (4) with every row of rest (K,4) in numpy float32, one rounding per operation: the operations of iou()
+    in the same order (np.minimum / np.maximum propagate NaN as torch.min / torch.max / clamp do)"""
+    area_a = (a[2] - a[0]) * (a[3] - a[1])
+    area_r = (rest[:, 2] - rest[:, 0]) * (rest[:, 3] - rest[:, 1])
+    w = np.maximum(np.minimum(a[2], rest[:, 2]) - np.maximum(a[0], rest[:, 0]), np.float32(0))
+    h = np.maximum(np.minimum(a[3], rest[:, 3]) - np.maximum(a[1], rest[:, 1]), np.float32(0))
+    inter = w * h
+    return inter / ((area_a + area_r) - inter)
+
+
+def nms_fast(boxes, scores, iou_threshold, max_keep=None, trace=False):
+    """nms() vectorised the other way round: every KEPT box marks the later boxes it suppresses, in one numpy float32 pass over them.  The
+    same visiting order, the same float32 operations, the same strict >: exactly nms()'s list, at a cost of (kept x N), not (N x kept)
+    torch calls -- N = 16384 with a few hundred kept takes well under a second.  trace: also, per visiting position, the position of the
+    last kept box that suppresses it (-1: kept, or never reached)."""
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+    order = np.asarray(visiting_order(scores), dtype=np.int64)
+    thr = np.float32(iou_threshold)
+    sorted_boxes = b[order]
+    dead = np.zeros(len(order), bool)
+    last = np.full(len(order), -1, np.int64)                 # per visiting position: the position of the LAST kept box that suppresses it
+    keep = []
+    with np.errstate(all='ignore'):
+        for pos in range(len(order)):
+            if max_keep is not None and len(keep) >= max_keep:
+                break
+            if dead[pos]:
+                continue
+            keep.append(int(order[pos]))
+            if pos + 1 < len(order):
+                hit = iou_rows_np(sorted_boxes[pos], sorted_boxes[pos + 1:]) > thr
+                dead[pos + 1:] |= hit
+                last[pos + 1:][hit] = pos
+    keep = np.asarray(keep, dtype=np.int64)
+    return (keep, last) if trace else keep
+
+
+def shifted_np(boxes, idxs):
+    """batched_nms' shift in numpy float32: boxes + float32(idx) * (max + 1); a NaN anywhere makes max, and every shift, NaN"""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    with np.errstate(all='ignore'):
+        unit = b.max() + np.float32(1)
+        return b + (np.asarray(idxs).astype(np.float32) * unit)[:, None]
+
+
+def batched_nms_fast(boxes, scores, idxs, iou_threshold, max_keep=None):
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    if b.size == 0:
+        return np.zeros(0, np.int64)
+    return nms_fast(shifted_np(b, idxs), scores, iou_threshold, max_keep)
+
+
+# ---- steps 2-3 in float64 and the error of their float32 evaluation ----------------------------------------------------------------------
+U32 = 2.0 ** -24
+
+
+def decode64(box_regression, proposals):
+    """(R,4C), (R,4) float32 values -> boxes (R,C,4) float64 of step 2 evaluated without rounding error to speak of, and bound (R,C,4):
+    what a float32 evaluation with one rounding per operation and an exp within 1 ulp may differ from it by, per coordinate.
+
+    Derivation for x1 = pcx - 0.5 pw (x2, y1, y2 alike), u = 2^-24, every float32 operation off by at most u relative, first order:
+      w   = fl(x2 - x1)            error  u |w|
+      cx  = fl(x1 + 0.5 w)         0.5 w is exact; error  u |cx| + 0.5 u |w|
+      dx  = fl(r0 / 10),  fl(dx w) three roundings on the product (dx, w, the product): error  3 u |dx w|
+      pcx = fl(dx w + cx)          error  u |pcx| + 3 u |dx w| + u |cx| + 0.5 u |w|
+      dw  = min(fl(r2 / 5), L)     error  u |dw|  (the rounding of the quotient, or that of the constant L = log(1000/16) to float32);
+                                   exp turns an absolute error of its argument into a relative one: u |dw|, with |dw| <= 4.14 for dw >= -4.14
+      e   = expf(dw)               1 ulp, the figure of the HIP math API's accuracy table for expf ("Maximum ULP error: 1", HIP documentation,
+                                   "HIP math API", single precision functions); an ulp is at most 2 u relative
+      pw  = fl(e w)                relative error  u (|dw| + 2 + 1 + 1): argument, exp, the rounding of w, the rounding of the product
+      x1  = fl(pcx - 0.5 pw)       0.5 pw is exact; error  u |x1| + error(pcx) + 0.5 (|dw| + 4) u pw
+    Together  |error(x)| <= u (|x| + |pcx| + 3 |dx w| + 0.5 |w| + |cx| + k pw),  k = (|dw| + 4) / 2  (<= 4.07 for |dw| <= 4.14; the test
+    inputs stay there), all magnitudes those of the float64 evaluation; times 1 + 2^-10 for the terms of second order (the largest is the
+    square of the 8 u on pw, far below).  The clip (step 3) is 1-Lipschitz: it cannot widen the error."""
+    reg, p = np.asarray(box_regression, np.float32).astype(np.float64), np.asarray(proposals, np.float32).astype(np.float64)
+    reg = reg.reshape(p.shape[0], -1, 4)
+    w, h = (p[:, 2] - p[:, 0])[:, None], (p[:, 3] - p[:, 1])[:, None]
+    cx, cy = p[:, 0, None] + 0.5 * w, p[:, 1, None] + 0.5 * h
+    dx, dy = reg[:, :, 0] / 10.0, reg[:, :, 1] / 10.0
+    dw, dh = np.minimum(reg[:, :, 2] / 5.0, XFORM_CLIP), np.minimum(reg[:, :, 3] / 5.0, XFORM_CLIP)
+    pcx, pcy = dx * w + cx, dy * h + cy
+    pw, ph = np.exp(dw) * w, np.exp(dh) * h
+    boxes = np.stack([pcx - 0.5 * pw, pcy - 0.5 * ph, pcx + 0.5 * pw, pcy + 0.5 * ph], -1)
+
+    def bound(x, pc, d, size, c, dsize, psize):
+        return U32 * (1 + 2.0 ** -10) * (np.abs(x) + np.abs(pc) + 3 * np.abs(d * size) + 0.5 * np.abs(size) + np.abs(c)
+                                         + 0.5 * (np.abs(dsize) + 4) * np.abs(psize))
+    bx = [bound(boxes[..., i], pcx, dx, w, cx, dw, pw) for i in (0, 2)]
+    by = [bound(boxes[..., i], pcy, dy, h, cy, dh, ph) for i in (1, 3)]
+    return boxes, np.stack([bx[0], by[0], bx[1], by[1]], -1)
+
+
+def clip64(boxes, net_size):
+    net_h, net_w = net_size
+    out = np.array(boxes, dtype=np.float64)
+    out[..., 0::2] = np.clip(out[..., 0::2], 0, net_w)
+    out[..., 1::2] = np.clip(out[..., 1::2], 0, net_h)
+    return out
+
+
 # ---- steps 1-6 of one batch ----------------------------------------------------------------------------------------------------------
 def postprocess(class_logits, box_regression, proposals, net_sizes, original_sizes=None, score_thresh=0.05, nms_thresh=0.5,
                 detections_per_img=100):
@@ -131,21 +237,72 @@ def postprocess(class_logits, box_regression, proposals, net_sizes, original_siz
 
 # ---- step 8 ------------------------------------------------------------------------------------------------------------------------
 def box_pixels(box, M):
-    """the expanded box truncated toward zero -> (bx1, by1, bx2, by2) Python ints"""
-    b = f32(box)
-    scale = torch.tensor(M + 2, dtype=torch.float32) / torch.tensor(M, dtype=torch.float32)
-    xc, yc = (b[2] + b[0]) * 0.5, (b[3] + b[1]) * 0.5
-    wh, hh = (b[2] - b[0]) * 0.5 * scale, (b[3] - b[1]) * 0.5 * scale
-    return tuple(int(v) for v in torch.stack([xc - wh, yc - hh, xc + wh, yc + hh]).to(torch.int64))
+    """the expanded box in float32, truncated toward zero -> (bx1, by1, bx2, by2) Python ints.  As the contract's last sentence of step 8
+    has it for what torch's cast leaves undefined: a NaN gives 0, anything beyond +-2^29 (an infinity included) is clamped there"""
+    b = np.asarray(box, dtype=np.float32).reshape(4)
+    with np.errstate(all='ignore'):
+        scale = np.float32(M + 2) / np.float32(M)
+        xc, yc = (b[2] + b[0]) * np.float32(0.5), (b[3] + b[1]) * np.float32(0.5)
+        wh, hh = (b[2] - b[0]) * np.float32(0.5) * scale, (b[3] - b[1]) * np.float32(0.5) * scale
+        edges = [xc - wh, yc - hh, xc + wh, yc + hh]
+    return tuple(0 if math.isnan(v) else int(min(max(float(v), -float(BOX_PIXEL_LIMIT)), float(BOX_PIXEL_LIMIT))) for v in edges)
+
+
+BOX_PIXEL_LIMIT = 1 << 29
+
+
+def paste_value64(mask_logits, box, label, frame_size):
+    """step 8 for ONE detection, evaluated directly per frame pixel in float64 (no F.interpolate, nothing of size (h, w)): mask_logits
+    (C,M,M), box (4), label -> (H,W) float64 values (0 outside the box) and (H,W) bool `inside`.  Only the integer box comes from float32
+    (box_pixels: the contract rounds there); sigmoid, scales, source coordinates, weights and taps are float64.  A label outside [0, C)
+    pastes nothing."""
+    H, W = frame_size
+    logits = np.asarray(mask_logits, np.float32).astype(np.float64)
+    C, M, _ = logits.shape
+    values, inside = np.zeros((H, W)), np.zeros((H, W), bool)
+    if not 0 <= int(label) < C:
+        return values, inside
+    P = M + 2
+    padded = np.zeros((P, P))
+    padded[1:-1, 1:-1] = 1.0 / (1.0 + np.exp(-logits[int(label)]))
+    bx1, by1, bx2, by2 = box_pixels(box, M)
+    w, h = max(bx2 - bx1 + 1, 1), max(by2 - by1 + 1, 1)
+    x0, x1, y0, y1 = max(bx1, 0), min(bx2 + 1, W), max(by1, 0), min(by2 + 1, H)
+    if x0 >= x1 or y0 >= y1:
+        return values, inside
+
+    def axis(first, last, origin, n):
+        i = np.arange(first, last, dtype=np.int64) - origin
+        s = np.maximum(P / n * (i + 0.5) - 0.5, 0.0)
+        i0 = np.minimum(np.floor(s).astype(np.int64), P - 1)
+        i1 = i0 + (i0 < P - 1)
+        l1 = s - i0
+        return i0, i1, 1.0 - l1, l1
+    yi0, yi1, yl0, yl1 = axis(y0, y1, by1, h)
+    xi0, xi1, xl0, xl1 = axis(x0, x1, bx1, w)
+    top = xl0 * padded[yi0][:, xi0] + xl1 * padded[yi0][:, xi1]
+    bot = xl0 * padded[yi1][:, xi0] + xl1 * padded[yi1][:, xi1]
+    values[y0:y1, x0:x1] = yl0[:, None] * top + yl1[:, None] * bot
+    inside[y0:y1, x0:x1] = True
+    return values, inside
+
+
+def paste_values64(mask_logits, boxes, labels, frame_size):
+    """paste_value64 for D detections -> (D,H,W) float64, (D,H,W) bool"""
+    H, W = frame_size
+    both = [paste_value64(mask_logits[d], boxes[d], labels[d], frame_size) for d in range(len(boxes))]
+    return (np.stack([v for v, _ in both]).reshape(-1, H, W), np.stack([i for _, i in both]).reshape(-1, H, W))
 
 
 def paste_values(mask_logits, boxes, labels, frame_size, dtype=torch.float32):
     """-> (D,H,W) pasted probabilities (0 outside the box) and (D,H,W) bool `inside` (pixels that took an interpolated value)"""
     H, W = frame_size
     logits = f32(mask_logits)
-    D, _, M, _ = logits.shape
+    D, C, M, _ = logits.shape
     values, inside = torch.zeros((D, H, W), dtype=dtype), torch.zeros((D, H, W), dtype=torch.bool)
     for d in range(D):
+        if not 0 <= int(labels[d]) < C:                     # a label outside the channels: the pasted plane is 0 everywhere
+            continue
         prob = torch.sigmoid(logits[d, int(labels[d])].to(dtype))
         padded = F.pad(prob, (1, 1, 1, 1))
         bx1, by1, bx2, by2 = box_pixels(boxes[d], M)
@@ -233,3 +390,102 @@ def head_case(seed, counts, C, net_size, near_thresh=0.05):
         logits[1] = -8; logits[1, 0] = 0
         logits[1, 1] = np.float32(math.log(s * (1 + (C - 2) * math.exp(-8)) / (1 - s)))
     return logits, reg.reshape(R, 4 * C), np.split(props, np.cumsum(counts)[:-1])
+
+
+def nms_clustered_case(N, seed=0, extent=1000.0):
+    """N NON-integer float32 boxes in clusters of heavy overlap: a few hundred are kept, the rest suppressed, many of them by a box visited
+    several row blocks (of 64) earlier.  Scores are distinct but for a handful of planted equal pairs; labels 0 .. 3."""
+    rng = np.random.RandomState(1000 + seed + N)
+    K = max(8, min(300, N // 4))
+    centre = rng.uniform(40, extent - 40, (K, 2))
+    size = rng.uniform(18, 42, (K, 2))
+    which = rng.randint(0, K, N)
+    c = centre[which] + rng.normal(0, 2.5, (N, 2))
+    s = size[which] * rng.uniform(0.85, 1.15, (N, 2))
+    boxes = np.concatenate([c - 0.5 * s, c + 0.5 * s], 1).astype(np.float32)
+    scores = rng.uniform(0.05, 1.0, N).astype(np.float32)
+    if N >= 8:
+        scores[N // 2], scores[N - 1] = scores[3], scores[5]                  # equal scores far apart
+    labels = rng.randint(0, 4, N).astype(np.int64)
+    return boxes, scores, labels
+
+
+def nms_label_case(seed=0, N=600, max_label=4095, extent=1000.0):
+    """fractional boxes with coordinates up to `extent` and labels up to 4095, one label per cluster: the shift float32(label) * (max + 1)
+    reaches 4e6, where float32 steps by 0.25 to 0.5, and ROUNDS twice: the product (max + 1 has a fractional part) and the sum"""
+    rng = np.random.RandomState(2000 + seed)
+    K = N // 6
+    centre = rng.uniform(30, extent - 30, (K, 2))
+    cluster_label = rng.randint(0, max_label + 1, K)
+    cluster_label[0], cluster_label[1] = max_label, 0
+    which = rng.randint(0, K, N)
+    c = centre[which] + rng.normal(0, 4.0, (N, 2))
+    s = rng.uniform(14, 34, (K, 2))[which] * rng.uniform(0.8, 1.25, (N, 2))
+    boxes = np.minimum(np.concatenate([c - 0.5 * s, c + 0.5 * s], 1), extent - 0.5).astype(np.float32)
+    boxes[0, 2] = np.float32(extent - 0.27)                                   # the largest coordinate: max + 1 is no integer, label * (max + 1) rounds
+    return boxes, rng.uniform(0.05, 1.0, N).astype(np.float32), cluster_label[which].astype(np.int64)
+
+
+def nms64_per_label(boxes, scores, labels, iou_threshold):
+    """what the shift stands for, without it: greedy NMS among the boxes of one label only, IoU in float64 on the unshifted boxes -> sorted
+    kept indices"""
+    b = np.asarray(boxes, np.float32).astype(np.float64)
+    labels = np.asarray(labels)
+    keep = []
+    for i in visiting_order(scores):
+        ok = True
+        for k in keep:
+            if labels[k] != labels[i]:
+                continue
+            w = max(min(b[k, 2], b[i, 2]) - max(b[k, 0], b[i, 0]), 0.0)
+            h = max(min(b[k, 3], b[i, 3]) - max(b[k, 1], b[i, 1]), 0.0)
+            union = (b[k, 2] - b[k, 0]) * (b[k, 3] - b[k, 1]) + (b[i, 2] - b[i, 0]) * (b[i, 3] - b[i, 1]) - w * h
+            if w * h / union > iou_threshold:
+                ok = False
+                break
+        if ok:
+            keep.append(i)
+    return sorted(keep)
+
+
+# the standard boxes of the paste tests, for a frame of (37, 53); scaled to other frames by the tests
+PASTE_FOUR = np.array([[10.3, 8.2, 30.7, 25.9], [-5.5, 10, 8, 20], [45, 12, 60.4, 30], [-20, -15, 80, 60]], np.float32)
+NAN, INF = float('nan'), float('inf')
+
+
+def paste_edge_cases():
+    """name -> dict(M, C, frame, boxes (D,4), labels (D), logits (D,C,M,M), mask_ths): the inputs of test_detpost_kernels.py's paste group.
+    Defined here so that test_detector_post_host.py can hold every one of them against the exclusion-band cap without a device."""
+    cases = {}
+
+    def add(name, M, frame, boxes, labels=None, C=3, mask_ths=(0.5,), amplitude=6.0, logits=None):
+        boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+        D = len(boxes)
+        labels = np.arange(D) % C if labels is None else np.asarray(labels)
+        cases[name] = dict(M=M, C=C, frame=frame, boxes=boxes, labels=labels.astype(np.int64), mask_ths=tuple(mask_ths),
+                           logits=smooth_mask_logits(M + D, D, C, M, amplitude) if logits is None else logits)
+    for M in (1, 2, 61, 62):                                                  # the ends of the range of M; one or four taps: plain positive logits
+        add(f'M{M}', M, (37, 53), PASTE_FOUR, logits=np.random.RandomState(M).uniform(1, 4, (4, 3, M, M)).astype(np.float32) if M <= 2 else None)
+    # (260, 128), 16-byte stores: three workgroups, a chunk is exactly rows 0-127, 128-255, 256-259.  With M = 14 (scale 16/14) the y ranges
+    # truncate to rows 128 .. 151 (first row 128), 98 .. 127 (last row 127), 135 .. 204 (inside the middle chunk), 3 .. 275 (all three
+    # chunks), 256 .. 259 (the tail only), and to the single rows 127 (a chunk's last row: row_last == ya) and 128 (a chunk's first: row_first ==
+    # yb - 1).  A one-row box reads the mask's centre rows; the first row of a taller box reads the zero ring and could not tell
+    add('chunks', 14, (260, 128), [[10.3, 130, 100.7, 150], [20.5, 100, 90.2, 126], [-8, 140, 60, 200], [5.5, 20, 140, 258], [30.2, 257, 99.9, 259],
+                                   [40.1, 127.3, 120.3, 127.9], [3.3, 128.2, 70.6, 128.8]])
+    add('one_pixel_frame', 14, (1, 1), [[-3, -3, 4, 4], [0.2, 0.1, 0.7, 0.8], [2, 2, 5, 5]])
+    # (1, 4099): one row, scalar stores, five workgroups of 1024 pixels: a box across four of them, one inside the last, two pixels across a seam
+    add('one_row', 28, (1, 4099), [[1000.5, -2, 3100.2, 3], [4090, -1, 4105, 2], [1023.9, 0, 1024.1, 1], [-50, -50, 5000, 50]])
+    add('one_column_wide', 14, (48, 1), [[-2, 5.5, 3, 40.2], [0, 0, 1, 48], [0.2, 30.5, 0.9, 30.7], [5, 5, 9, 9]])     # 48 % 16 == 0
+    add('one_column_scalar', 14, (40, 1), [[-2, 5.5, 3, 38.2], [0, 0, 1, 40], [0.2, 30.5, 0.9, 30.7], [5, 5, 9, 9]])
+    add('alignment', 14, (24, 40), PASTE_FOUR * np.array([40 / 53, 24 / 37, 40 / 53, 24 / 37], np.float32))
+    add('boxes', 14, (24, 40), [[30, 5, 10, 20], [5, 20, 30, 4], [30, 20, 10, 4],                  # inverted in x, in y, in both
+                                [NAN, 5, 20, 15], [NAN, NAN, NAN, NAN],                            # a NaN coordinate, an all-NaN box
+                                [0, 0, INF, INF], [-INF, 3, 10, 12], [-INF, -INF, INF, INF],       # infinities
+                                [-1e12, -1e12, 1e12, 1e12],                                        # clamped at +-2^29
+                                [0, 0, 40, 24], [7, 9, 7, 9]])                                     # exactly the frame; zero area on integers
+    add('labels', 14, (24, 40), np.tile(PASTE_FOUR[3], (4, 1)), labels=[-1, 3, 1, -7], mask_ths=(0.5, -0.5))
+    # mask_th in {-0.5, 0, 1, NaN}: boxes of fewer than M + 2 pixels a side (no source coordinate clamps to 0: every in-box value is a
+    # positive mix of taps) and flat logits (sigmoid in about [0.1, 0.7]): every in-box value lies in (1e-4, 0.75), far from 0 and from 1
+    add('mask_th', 14, (24, 40), [[3.2, 4.1, 12.4, 15.3], [-4, 10, 6, 20], [30, -5, 41, 6], [70, 50, 80, 60]], mask_ths=(-0.5, 0.0, 1.0, NAN),
+        amplitude=0.1)
+    return cases

@@ -223,6 +223,148 @@ def test_lazy_names():
     assert detector._lib.EXPORTS.count('cosy_paste_masks') == 1
 
 
+# ---- the twin's additions for tests/test_detpost_kernels.py --------------------------------------------------------------------------
+def integer_nms_case(N, seed=0):
+    """test_detector_post.py's nms_case, restated here (that module needs a device to import)"""
+    rng = np.random.RandomState(seed + N)
+    x1, y1 = rng.randint(0, 40, N), rng.randint(0, 40, N)
+    boxes = np.stack([x1, y1, x1 + rng.randint(1, 21, N), y1 + rng.randint(1, 21, N)], 1).astype(np.float32)
+    if N >= 2:
+        boxes[0], boxes[1] = [0, 0, 10, 10], [0, 0, 10, 5]
+    if N >= 65:
+        boxes[63], boxes[64] = [30, 30, 50, 40], [30, 30, 50, 35]
+    return boxes, (rng.randint(1, 17, N) / 16).astype(np.float32), rng.randint(0, 3, N).astype(np.int64)
+
+
+@pytest.mark.parametrize('N', [0, 1, 2, 63, 64, 65, 130])
+def test_vectorised_nms_equals_the_loop_on_the_integer_cases(N):
+    boxes, scores, labels = integer_nms_case(N)
+    for max_keep in (None, 7):
+        assert ref.nms_fast(boxes, scores, 0.5, max_keep).tolist() == ref.nms(boxes, scores, 0.5, max_keep).tolist()
+        assert ref.batched_nms_fast(boxes, scores, labels, 0.5, max_keep).tolist() == ref.batched_nms(boxes, scores, labels, 0.5, max_keep).tolist()
+
+
+@pytest.mark.parametrize('N', [129, 400])
+def test_vectorised_nms_equals_the_loop_on_random_float_boxes(N):
+    boxes, scores, labels = ref.nms_clustered_case(N)
+    for thr in (0.5, 0.3, 0.0, float('nan')):
+        want = ref.nms(boxes, scores, thr)
+        assert ref.nms_fast(boxes, scores, thr).tolist() == want.tolist()
+    assert 0 < len(ref.nms(boxes, scores, 0.5)) < N
+    assert ref.batched_nms_fast(boxes, scores, labels, 0.5).tolist() == ref.batched_nms(boxes, scores, labels, 0.5).tolist()
+    lb, ls, ll = ref.nms_label_case(N=N)                                    # shifts of 4e6: the rounded coordinates
+    assert ref.batched_nms_fast(lb, ls, ll, 0.5).tolist() == ref.batched_nms(lb, ls, ll, 0.5).tolist()
+    lb[N // 3, 1] = np.nan                                                  # one NaN: every shift is NaN
+    assert ref.batched_nms_fast(lb, ls, ll, 0.5).tolist() == ref.batched_nms(lb, ls, ll, 0.5).tolist() == ref.visiting_order(ls)
+
+
+def test_vectorised_nms_at_the_largest_size_takes_seconds():
+    import time
+    boxes, scores, _ = ref.nms_clustered_case(16384)
+    t0 = time.time()
+    keep = ref.nms_fast(boxes, scores, 0.5)
+    took = time.time() - t0
+    print(f'N=16384: kept {len(keep)} in {took:.2f} s')
+    assert 100 < len(keep) < 2000 and took < 20
+
+
+def test_decode64_agrees_with_the_float32_twin_within_its_bound():
+    logits, reg, props = ref.head_case(9, [70, 40], 5, (37, 53))
+    want32 = ref.decode(reg, np.concatenate(props)).numpy().astype(np.float64)
+    got, bound = ref.decode64(reg, np.concatenate(props))
+    frac = np.abs(want32 - got) / bound
+    print(f'float32 twin against decode64: worst {frac.max():.3f} of the bound')
+    assert got.shape == bound.shape == (110, 5, 4) and frac.max() <= 1
+    # the bound is a few units of float32 rounding of the quantities involved, not a loose figure: at most 16 u of their sum
+    reg64 = reg.reshape(110, 5, 4).astype(np.float64)
+    assert (bound <= 16 * ref.U32 * (np.abs(got).max(-1, keepdims=True) + 25 + 1000 * (reg64[..., 2:].max(-1, keepdims=True) >= 20))).all()
+    # by hand: proposal (0, 0, 16, 16), deltas (0, 5, 30, 0): cx 8 +- 500 through the clamp, cy 8 + 0.5 * 16 = 16 +- 8
+    hand = np.zeros((1, 8), np.float32)
+    hand[0, 4:] = [0, 5, 30, 0]
+    box, b = ref.decode64(hand, [[0, 0, 16, 16]])
+    assert np.abs(box[0, 1] - [8 - 500, 8, 8 + 500, 24]).max() < 1e-9 and np.array_equal(box[0, 0], [0, 0, 16, 16])
+    assert np.array_equal(ref.clip64(box, (37, 53))[0, 1], [0, 8, 53, 24])
+    # x: |x| 508 + |pcx| 8 + 0 + 8 + 8 + (4.135 + 4) / 2 * 1000 = 4599.6 units of 2^-24
+    assert abs(b[0, 1, 2] / ref.U32 - (508 + 8 + 8 + 8 + 0.5 * (ref.XFORM_CLIP + 4) * 1000)) < 5
+
+
+def test_paste_value64_equals_the_interpolating_twin_in_float64():
+    boxes = np.array([[10.3, 8.2, 30.7, 25.9], [-5.5, 10, 8, 20], [20, -6.2, 35, 7.5], [45, 12, 60.4, 30], [12, 30, 28, 44.3],
+                      [70, 50, 90, 60], [-30, -30, -10, -5], [3.2, 4.1, 3.4, 4.3], [-20, -15, 80, 60]], np.float32)    # PASTE_BOXES of the GPU suite
+    for M in (14, 28):
+        for frame in ((37, 53), (24, 40), (130, 128)):
+            H, W = frame
+            b = boxes * np.array([W / 53, H / 37, W / 53, H / 37], np.float32)
+            b[7] = boxes[7]
+            logits = ref.smooth_mask_logits(M, len(b), 3, M)
+            labels = np.arange(len(b)) % 3
+            want, want_inside = ref.paste_values(logits, b, labels, frame, torch.float64)
+            got, inside = ref.paste_values64(logits, b, labels, frame)
+            assert np.array_equal(inside, want_inside.numpy())
+            err = np.abs(got - want.numpy()).max()
+            assert err <= 1e-12, (M, frame, err)
+
+
+def test_box_pixels_for_non_finite_huge_and_inverted_boxes():
+    nan, inf = float('nan'), float('inf')
+    assert ref.box_pixels([nan, nan, nan, nan], 14) == (0, 0, 0, 0)
+    assert ref.box_pixels([-1e12, -1e12, 1e12, 1e12], 14) == (-2 ** 29, -2 ** 29, 2 ** 29, 2 ** 29)
+    assert ref.box_pixels([0, 0, inf, inf], 14) == (0, 0, 2 ** 29, 2 ** 29)        # xc = inf, wh = inf: inf - inf = NaN -> 0, inf + inf -> 2^29
+    assert ref.box_pixels([nan, 5, 20, 15], 14)[::2] == (0, 0)
+    # inverted in x: xc 20, wh -10 * 16/14 = -11.43: 31.43 -> 31 and 8.57 -> 8; y as usual: 12.5 -+ 7.5 * 16/14 = 3.93, 21.07
+    assert ref.box_pixels([30, 5, 10, 20], 14) == (31, 3, 8, 21)
+    values, inside = ref.paste_value64(np.full((1, 14, 14), 3.0, np.float32), [30, 5, 10, 20], 0, (24, 40))
+    assert not inside.any() and not values.any()                                   # bx1 > bx2: an empty region
+    assert ref.box_pixels([-6.5, 2, 6, 10], 4) == (-9, 0, 9, 12)                   # finite boxes as before
+    # the all-NaN box: pixel (0, 0) of a (1, 1) upsample: s = 16/1 * 0.5 - 0.5 = 7.5 on both axes, the mean of the four centre taps
+    logits = ref.smooth_mask_logits(3, 1, 1, 14)
+    values, inside = ref.paste_value64(logits[0], [nan] * 4, 0, (24, 40))
+    prob = 1 / (1 + np.exp(-logits[0, 0].astype(np.float64)))
+    assert inside.sum() == 1 and inside[0, 0] and abs(values[0, 0] - prob[6:8, 6:8].mean()) < 1e-15
+    # the clamped box: 2^30 + 1 pixels a side, the frame sits at its centre: one value to 1e-6
+    values, inside = ref.paste_value64(logits[0], [-1e12, -1e12, 1e12, 1e12], 0, (24, 40))
+    assert inside.all() and np.abs(values - prob[6:8, 6:8].mean()).max() < 1e-5 * 14
+
+
+def test_new_paste_inputs_stay_inside_the_exclusion_cap():
+    """at most 0.1 % of a mask's in-box pixels within 1e-5 of mask_th, on the reference alone, for every input of the GPU suite's paste group"""
+    cases = ref.paste_edge_cases()
+    assert set(cases) >= {'M1', 'M2', 'M61', 'M62', 'chunks', 'one_pixel_frame', 'one_row', 'one_column_wide', 'one_column_scalar', 'alignment',
+                          'boxes', 'labels', 'mask_th'}
+    for name, c in cases.items():
+        v64, inside = ref.paste_values64(c['logits'], c['boxes'], c['labels'], c['frame'])
+        in_box = inside.reshape(len(v64), -1).sum(1)
+        for th in c['mask_ths']:
+            close = (np.abs(v64 - th) <= 1e-5) & inside
+            assert (close.reshape(len(v64), -1).sum(1) <= 1e-3 * in_box).all(), (name, th)
+    # the rows the chunk boxes were built for (a workgroup of the (260, 128) frame owns rows 0-127, 128-255, 256-259)
+    c = cases['chunks']
+    rows = [ref.box_pixels(b, 14)[1::2] for b in c['boxes']]
+    assert rows == [(128, 151), (98, 127), (135, 204), (3, 275), (256, 259), (127, 127), (128, 128)]
+    assert [ref.box_pixels(b, 28)[0::2] for b in cases['one_row']['boxes']][2] == (1023, 1024)      # two pixels across a workgroup seam
+    # mask_th group: every in-box value is strictly between 1e-4 and 0.75, the outside is exactly 0
+    c = cases['mask_th']
+    v64, inside = ref.paste_values64(c['logits'], c['boxes'], c['labels'], c['frame'])
+    assert v64[inside].min() > 1e-4 and v64[inside].max() < 0.75 and not v64[~inside].any() and not inside[3].any() and inside[:3].any((1, 2)).all()
+    assert ref.paste_masks(c['logits'], c['boxes'], c['labels'], c['frame'], -0.5).all()            # 0 > -0.5: the outside is true too
+    assert np.array_equal(ref.paste_masks(c['logits'], c['boxes'], c['labels'], c['frame'], 0.0), inside)
+    assert not ref.paste_masks(c['logits'], c['boxes'], c['labels'], c['frame'], float('nan')).any()
+
+
+def test_wrapper_refuses_the_key_limits_before_loading_the_library(no_library):
+    f = lambda *s: torch.empty(*s)
+    with pytest.raises(ValueError, match='2048 images exceed the limit of 2047'):
+        detector.postprocess_detections(f(2048, 2), f(2048, 8), f(2048, 4), [(37, 53)] * 2048, counts=[1] * 2048)
+    with pytest.raises(ValueError, match='C = 4097 classes exceed the limit of 4096'):
+        detector.postprocess_detections(f(1, 4097), f(1, 4 * 4097), [f(1, 4)], [(37, 53)])
+    with pytest.raises(ValueError, match=r'exceeds the limit of 2\^21'):
+        detector.postprocess_detections(f(2 ** 21 + 1, 2), f(2 ** 21 + 1, 8), [f(2 ** 21 + 1, 4)], [(37, 53)])
+    with pytest.raises(ValueError, match=r'exceeds the limit of 2\^21'):
+        detector.postprocess_detections(f(2 ** 19 + 1, 5), f(2 ** 19 + 1, 20), [f(2 ** 19 + 1, 4)], [(37, 53)])
+    with pytest.raises(ValueError, match='ROCm device'):                       # at the limits the call goes on to the next check
+        detector.postprocess_detections(f(2047, 2), f(2047, 8), f(2047, 4), [(37, 53)] * 2047, counts=[1] * 2047)
+
+
 def test_score_key_orders_scores_descending():
     # the sort key of csrc/kernels_detpost.hip: positive float32 bits order as the values do
     s = np.array([0.05000001, 0.0500001, 0.3, 0.99999994, 1.0], np.float32)
