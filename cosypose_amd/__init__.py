@@ -70,6 +70,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('nms', 'batched_nms', 'postprocess_detections', 'paste_masks', 'detections_from_heads'):
         from . import detector
         return getattr(detector, name)
+    if name in ('rpn_anchors', 'rpn_proposals', 'multiscale_roi_align', 'detections_from_features'):
+        from . import detector_rpn
+        return getattr(detector_rpn, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

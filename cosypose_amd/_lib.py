@@ -132,6 +132,10 @@ _SIGNATURES = {
     'cosy_nms_scan': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
     'cosy_det_gather': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     'cosy_paste_masks': ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
+    'cosy_rpn_select': ([_P, _I, _I, _I, _I, _P, _P, _P], _I),
+    'cosy_rpn_decode': ([_P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_rpn_gather': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_msroi_align': ([_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     'cosy_resize_ksize': ([_I, _I, _I], _I),
     'cosy_resize_coeffs': ([_I, _I, _I, _P, _P, _SZ], _I),
     'cosy_resize_workspace_bytes': ([_I, _I, _I, _I], _SZ),
@@ -161,6 +165,18 @@ class BaBatch(ctypes.Structure):       # cosy_ba_batch_t
         ('a_total', _c.c_longlong)] + [(k, _D) for k in ('residuals_threshold', 'L_down', 'L_up', 'eps')] + [
         (k, _P) for k in ('table', 'cand_TCO', 'K', 'pts_table', 'sym_table', 'n_sym', 'TWO_9d', 'TCW_9d', 'TWO_9d_updated', 'TCW_9d_updated',
                           'ctrl', 'hist_iteration', 'hist_lambda', 'hist_loss', 'hist_TWO_9d', 'hist_TCW_9d', 'workspace')]
+
+
+RPN_MAX_LEVELS, RPN_MAX_ANCHORS = 8, 16
+
+
+class RpnLevels(ctypes.Structure):     # cosy_rpn_levels_t
+    _fields_ = [('objectness', _P * RPN_MAX_LEVELS), ('deltas', _P * RPN_MAX_LEVELS), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS),
+                ('stride_h', _F * RPN_MAX_LEVELS), ('stride_w', _F * RPN_MAX_LEVELS), ('base', _F * 4 * RPN_MAX_ANCHORS * RPN_MAX_LEVELS)]
+
+
+class MsroiLevels(ctypes.Structure):   # cosy_msroi_levels_t
+    _fields_ = [('feat', _P * RPN_MAX_LEVELS), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS), ('scale', _F * RPN_MAX_LEVELS)]
 
 
 class ProfRec(ctypes.Structure):

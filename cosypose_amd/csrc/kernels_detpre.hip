@@ -1,0 +1,425 @@
+// Proposal side of the detector: what sits between the trunk's convolutions and the heads' inputs (torchvision 0.4.2 AnchorGenerator,
+// RegionProposalNetwork.filter_proposals, MultiScaleRoIAlign with Mask R-CNN's defaults).  DESIGN.md section 22 states the contract;
+// tests/detpre_ref.py is the CPU twin.  The NMS between decode and gather is kernels_detpost.hip's (cosy_nms_mask / cosy_nms_scan), unchanged.
+//
+//   rpn_select_kernel        ONE workgroup per (image, level): radix select of the k-th largest objectness logit over the order-preserving
+//                            32-bit map of the float (four passes of 8 bits, per-wave LDS histograms, integer atomics), then an ordered
+//                            compaction: the workgroup walks the level in chunks of 1024 anchors in index order and writes every anchor
+//                            strictly above the threshold key, then the lowest-index ties at it.  An anchor whose logit or any delta is NaN
+//                            is absent: never counted, never selected.  -0 counts as +0.
+//   rpn_decode_kernel        ONE thread per arena slot (image, level, rank): the anchor from its index, BoxCoder.decode with weights 1 and the
+//                            log(1000/16) clamp, clip to the image's own size, the small-box test; a survivor leaves box, score, level,
+//                            candidate index and the sort key  image << 52 | (0xffffffff - ordered score) << 20 | candidate index;  every
+//                            other slot leaves the "empty slot of image b" key, which sorts behind all of b's candidates.
+//   rpn_gather_kernel        the kept rows of cosy_nms_scan into (B, max_keep) padded proposals, scores, levels, candidate indices, counts
+//   msroi_align_kernel       a workgroup owns one RoI and a group of channels: level mapper, then the P g tap indices and weights of each axis
+//                            once into LDS (the taps are separable); lanes run over (channel, ph, pw), pw fastest, and write (R, C, P, P).
+// Integer atomics only.  float32 with one rounding per operation: contraction is off (the pragma below and build.FILE_FLAGS).
+#include <math.h>
+#include "cosy_common.h"
+#include "det_device.h"
+
+#pragma clang fp contract(off)
+
+namespace cosy {
+namespace {
+
+constexpr int SEL_THREADS = 1024;
+constexpr int SEL_WAVES = SEL_THREADS / 64;
+constexpr int PRE_THREADS = 256;
+constexpr int RPN_KEY_INDEX_BITS = 20;                           // candidate index = level offset + anchor index < 2^20
+constexpr int RPN_KEY_IMAGE_SHIFT = 52;                          // 32 bits of ordered score above the index, the image above both
+constexpr int RPN_MAX_IMAGES = 2047;
+constexpr float BBOX_XFORM_CLIP = 4.135166556742356f;            // log(1000 / 16)
+constexpr int MS_MAX_TAPS = 128;                                 // P g per axis
+
+typedef cosy_rpn_levels_t RpnLevels;
+typedef cosy_msroi_levels_t MsLevels;
+
+__device__ __forceinline__ long long empty_key(int b) { return ((long long)b << RPN_KEY_IMAGE_SHIFT) | ((1LL << RPN_KEY_IMAGE_SHIFT) - 1); }
+
+// larger float <=> larger key: all bits of a negative value flipped, the sign bit of any other; -0 is +0 first
+__device__ __forceinline__ unsigned ordered_key(float v) {
+    const unsigned u = v == 0.f ? 0u : __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// anchor i of a level = (cell, a) with a fastest; the head's NCHW planes are read in place
+__device__ __forceinline__ float rpn_logit(const float* __restrict__ obj, int A, int HW, int i) {
+    const int pos = i / A, a = i - pos * A;
+    return obj[(size_t)a * HW + pos];
+}
+__device__ __forceinline__ bool rpn_deltas_finite(const float* __restrict__ del, int A, int HW, int i, float* d) {
+    const int pos = i / A, a = i - pos * A;
+    bool ok = true;
+    for (int c = 0; c < 4; ++c) {
+        d[c] = del[(size_t)(4 * a + c) * HW + pos];
+        ok = ok && d[c] == d[c];
+    }
+    return ok;
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(RpnLevels lv, int L, int A, int pre, int* __restrict__ sel_idx,
+                                                                 int* __restrict__ sel_count) {
+    __shared__ unsigned hist[SEL_WAVES][256];
+    __shared__ unsigned wave_above[SEL_WAVES], wave_tie[SEL_WAVES];
+    __shared__ unsigned s_prefix, s_need;
+    __shared__ int s_k;
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int HW = lv.H[l] * lv.W[l], n = A * HW;
+    const float* obj = lv.objectness[l] + (size_t)b * A * HW;
+    const float* del = lv.deltas[l] + (size_t)b * 4 * A * HW;
+    float d[4];
+    unsigned prefix = 0u, need = 0u;
+    int k = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int i = tid; i < SEL_WAVES * 256; i += SEL_THREADS) (&hist[0][0])[i] = 0u;
+        __syncthreads();
+        for (int i = tid; i < n; i += SEL_THREADS) {
+            const float v = rpn_logit(obj, A, HW, i);
+            if (v != v) continue;
+            const unsigned key = ordered_key(v);
+            if (pass > 0 && (key >> (shift + 8)) != prefix) continue;
+            if (!rpn_deltas_finite(del, A, HW, i, d)) continue;
+            atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned t = 0u;
+            for (int w = 0; w < SEL_WAVES; ++w) t += hist[w][tid];
+            hist[0][tid] = t;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            if (pass == 0) {                                       // every present anchor is in the first histogram
+                unsigned total = 0u;
+                for (int q = 0; q < 256; ++q) total += hist[0][q];
+                s_k = (int)(total < (unsigned)pre ? total : (unsigned)pre);
+                s_need = (unsigned)s_k;
+            }
+            unsigned cum = 0u, want = s_need;
+            int digit = 0;
+            for (int q = 255; q >= 0; --q) {
+                const unsigned c = hist[0][q];
+                if (cum + c >= want) { digit = q; break; }
+                cum += c;
+            }
+            s_need = want - cum;                                   // how many of the keys with this prefix are still wanted
+            s_prefix = (prefix << 8) | (unsigned)digit;
+        }
+        __syncthreads();
+        prefix = s_prefix; need = s_need; k = s_k;
+        if (k == 0) break;                                         // (uniform)
+    }
+    if (tid == 0) sel_count[b * L + l] = k;
+    if (k == 0) return;
+    // `prefix` is the k-th largest key: all keys above it are taken, and the `need` lowest-index anchors at it
+    const unsigned n_above = (unsigned)k - need;
+    int* out = sel_idx + ((size_t)b * L + l) * pre;
+    unsigned base_above = 0u, base_tie = 0u;
+    for (int start = 0; start < n; start += SEL_THREADS) {
+        const int i = start + tid;
+        bool above = false, tie = false;
+        if (i < n) {
+            const float v = rpn_logit(obj, A, HW, i);
+            if (v == v) {
+                const unsigned key = ordered_key(v);
+                if (key >= prefix && rpn_deltas_finite(del, A, HW, i, d)) { above = key > prefix; tie = key == prefix; }
+            }
+        }
+        const unsigned long long ba = __ballot(above), bt = __ballot(tie);
+        if (lane == 0) { wave_above[wave] = (unsigned)__popcll(ba); wave_tie[wave] = (unsigned)__popcll(bt); }
+        __syncthreads();
+        unsigned oa = 0u, ot = 0u, ta = 0u, tt = 0u;
+        for (int w = 0; w < SEL_WAVES; ++w) {
+            const unsigned ca = wave_above[w], ct = wave_tie[w];
+            if (w < wave) { oa += ca; ot += ct; }
+            ta += ca; tt += ct;
+        }
+        const unsigned long long below = (1ULL << lane) - 1ULL;
+        if (above) {
+            const unsigned p = base_above + oa + (unsigned)__popcll(ba & below);
+            if (p < n_above) out[p] = i;
+        }
+        if (tie) {
+            const unsigned p = base_tie + ot + (unsigned)__popcll(bt & below);
+            if (p < need) out[n_above + p] = i;
+        }
+        base_above += ta; base_tie += tt;
+        __syncthreads();
+        if (base_above >= n_above && base_tie >= need) break;      // (uniform)
+    }
+}
+
+__global__ __launch_bounds__(PRE_THREADS) void rpn_decode_kernel(RpnLevels lv, int L, int A, int B, int pre, const int* __restrict__ sel_idx,
+                                                                 const int* __restrict__ sel_count, const float* __restrict__ net_sizes,
+                                                                 float min_size, int cap, float* __restrict__ cand_boxes,
+                                                                 float* __restrict__ cand_scores, int* __restrict__ cand_level,
+                                                                 int* __restrict__ cand_src, long long* __restrict__ cand_keys,
+                                                                 int* __restrict__ counts, unsigned* __restrict__ max_coord) {
+    const long at = (long)blockIdx.x * PRE_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    if (at >= (long)B * cap) return;                               // (B cap is a multiple of 64: a wave is inside or outside as a whole)
+    const int b = (int)(at / cap), s = (int)(at - (long)b * cap);  // one image per wave, for the same reason
+    const int l = s / pre, j = s - l * pre;
+    bool emit = false;
+    Box o = {0.f, 0.f, 0.f, 0.f};
+    float score = 0.f;
+    int cand = 0;
+    if (l < L) {
+        int cnt = sel_count[b * L + l];
+        cnt = cnt < pre ? cnt : pre;
+        const int H = lv.H[l], W = lv.W[l], HW = H * W;
+        const int idx = j < cnt ? sel_idx[((size_t)b * L + l) * pre + j] : -1;
+        if (idx >= 0 && idx < A * HW) {                            // an index read from memory: checked before it addresses anything
+            float d[4];
+            const float v = rpn_logit(lv.objectness[l] + (size_t)b * A * HW, A, HW, idx);
+            const bool fin = rpn_deltas_finite(lv.deltas[l] + (size_t)b * 4 * A * HW, A, HW, idx, d);
+            const int pos = idx / A, a = idx - pos * A, y = pos / W, x = pos - y * W;
+            const float sx = __fmul_rn((float)x, lv.stride_w[l]), sy = __fmul_rn((float)y, lv.stride_h[l]);
+            const float ax1 = __fadd_rn(lv.base[l][a][0], sx), ay1 = __fadd_rn(lv.base[l][a][1], sy);
+            const float ax2 = __fadd_rn(lv.base[l][a][2], sx), ay2 = __fadd_rn(lv.base[l][a][3], sy);
+            const float w = __fsub_rn(ax2, ax1), h = __fsub_rn(ay2, ay1);
+            const float cx = __fadd_rn(ax1, __fmul_rn(0.5f, w)), cy = __fadd_rn(ay1, __fmul_rn(0.5f, h));
+            const float dw = min_nan(d[2], BBOX_XFORM_CLIP), dh = min_nan(d[3], BBOX_XFORM_CLIP);
+            const float pcx = __fadd_rn(__fmul_rn(d[0], w), cx), pcy = __fadd_rn(__fmul_rn(d[1], h), cy);
+            const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
+            const float hw = __fmul_rn(0.5f, pw), hh = __fmul_rn(0.5f, ph);
+            const float net_h = net_sizes[2 * b], net_w = net_sizes[2 * b + 1];
+            o.x1 = min_nan(max_nan(__fsub_rn(pcx, hw), 0.f), net_w); o.y1 = min_nan(max_nan(__fsub_rn(pcy, hh), 0.f), net_h);
+            o.x2 = min_nan(max_nan(__fadd_rn(pcx, hw), 0.f), net_w); o.y2 = min_nan(max_nan(__fadd_rn(pcy, hh), 0.f), net_h);
+            score = v == 0.f ? 0.f : v;
+            int first = 0;
+            for (int m = 0; m < l; ++m) first += A * lv.H[m] * lv.W[m];
+            cand = first + idx;
+            emit = fin && v == v && __fsub_rn(o.x2, o.x1) >= min_size && __fsub_rn(o.y2, o.y1) >= min_size;   // (NaN fails every test)
+        }
+    }
+    long long key = empty_key(b);
+    if (emit) {
+        cand_boxes[4 * at] = o.x1; cand_boxes[4 * at + 1] = o.y1; cand_boxes[4 * at + 2] = o.x2; cand_boxes[4 * at + 3] = o.y2;
+        cand_scores[at] = score; cand_level[at] = l; cand_src[at] = cand;
+        key = ((long long)b << RPN_KEY_IMAGE_SHIFT) | ((long long)(0xffffffffu - ordered_key(score)) << RPN_KEY_INDEX_BITS) | (long long)cand;
+        const unsigned big = __float_as_uint(o.x2 > o.y2 ? o.x2 : o.y2);       // clipped coordinates are >= +0: bits order as values
+        if (big > __hip_atomic_load(&max_coord[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&max_coord[b], big);
+    }
+    cand_keys[at] = key;
+    const unsigned long long grp = __ballot(emit);                 // one integer atomic per wave
+    if (grp && lane == __ffsll((long long)grp) - 1) atomicAdd(&counts[b], __popcll(grp));
+}
+
+__global__ __launch_bounds__(PRE_THREADS) void rpn_gather_kernel(const int* __restrict__ kept, const int* __restrict__ n_kept,
+                                                                 const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores,
+                                                                 const int* __restrict__ cand_level, const int* __restrict__ cand_src, int B,
+                                                                 int cap, int max_keep, float* __restrict__ proposals,
+                                                                 float* __restrict__ scores, int* __restrict__ levels, int* __restrict__ src,
+                                                                 int* __restrict__ counts) {
+    const long at = (long)blockIdx.x * PRE_THREADS + threadIdx.x;
+    if (at < B) { const int n = n_kept[at]; counts[at] = n < 0 ? 0 : n < max_keep ? n : max_keep; }
+    if (at >= (long)B * max_keep) return;
+    const int b = (int)(at / max_keep), j = (int)(at - (long)b * max_keep);
+    const long idx = kept[at];
+    const bool ok = j < n_kept[b] && idx >= (long)b * cap && idx < (long)(b + 1) * cap;
+    Box v = {0.f, 0.f, 0.f, 0.f};
+    float sc = 0.f;
+    int lvl = -1, s = -1;
+    if (ok) {
+        v = {cand_boxes[4 * idx], cand_boxes[4 * idx + 1], cand_boxes[4 * idx + 2], cand_boxes[4 * idx + 3]};
+        sc = cand_scores[idx]; lvl = cand_level[idx]; s = cand_src[idx];
+    }
+    proposals[4 * at] = v.x1; proposals[4 * at + 1] = v.y1; proposals[4 * at + 2] = v.x2; proposals[4 * at + 3] = v.y2;
+    scores[at] = sc; levels[at] = lvl; src[at] = s;
+}
+
+// one tap line of roi_align along one axis (kernels_geom.hip roi_pixel's rules): lo < 0 marks a sample outside [-1, size], which adds nothing
+struct Tap { int lo, hi; float wl, wh; };
+
+__device__ __forceinline__ Tap msroi_tap(float start, float bin, int p, int i, int g, int size) {
+    float v = __fadd_rn(__fadd_rn(start, __fmul_rn((float)p, bin)), __fdiv_rn(__fmul_rn(__fadd_rn((float)i, .5f), bin), (float)g));
+    Tap t = {-1, -1, 0.f, 0.f};
+    if (!(v >= -1.0f && v <= (float)size)) return t;               // (a NaN sample is outside too)
+    if (v <= 0.f) v = 0.f;
+    int lo = (int)v, hi;
+    if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else hi = lo + 1;
+    t.lo = lo; t.hi = hi;
+    t.wl = __fsub_rn(v, (float)lo);                                // weight of the high tap
+    t.wh = __fsub_rn(1.f, t.wl);                                   // weight of the low tap
+    return t;
+}
+
+__global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, int L, int B, int C, const float* __restrict__ boxes,
+                                                                  const int* __restrict__ im_id, const int* __restrict__ counts,
+                                                                  int rows_per_image, int P, int g, int cg, int k_min, int k_max,
+                                                                  float* __restrict__ out, int* __restrict__ levels_out) {
+    __shared__ int s_lo[2][MS_MAX_TAPS], s_hi[2][MS_MAX_TAPS];
+    __shared__ float s_wl[2][MS_MAX_TAPS], s_wh[2][MS_MAX_TAPS];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int c0 = blockIdx.y * cg, c1 = c0 + cg < C ? c0 + cg : C;
+    const int PP = P * P, n_out = (c1 - c0) * PP;
+    float* dst = out + ((size_t)r * C + c0) * PP;
+    // everything below up to the tap tables is uniform over the workgroup
+    int img = im_id ? im_id[r] : r / rows_per_image;
+    bool row = img >= 0 && img < B;
+    if (row && counts) row = r - img * rows_per_image < counts[img];
+    const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
+    // LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max]; a NaN (negative area) takes k_min
+    const float sz = sqrtf(__fmul_rn(__fsub_rn(x2, x1), __fsub_rn(y2, y1)));
+    const float t = floorf(__fadd_rn(4.f, log2f(__fadd_rn(__fdiv_rn(sz, 224.f), 1e-6f))));
+    int lvl = !(t >= (float)k_min) ? k_min : t > (float)k_max ? k_max : (int)t;
+    lvl -= k_min;
+    if (lvl < 0 || lvl >= L) row = false;                          // (the entry point refuses k_max - k_min >= L: never taken)
+    if (blockIdx.y == 0 && tid == 0 && levels_out) levels_out[r] = row ? lvl : -1;
+    if (!row) {                                                    // a row no image owns: zeros
+        for (int o = tid; o < n_out; o += PRE_THREADS) dst[o] = 0.f;
+        return;
+    }
+    const int H = lv.H[lvl], W = lv.W[lvl];
+    const float scale = lv.scale[lvl];
+    const int taps = P * g;
+    for (int q = tid; q < 2 * taps; q += PRE_THREADS) {
+        const int axis = q / taps, m = q - axis * taps, p = m / g, i = m - p * g;
+        const float lo = __fmul_rn(axis ? x1 : y1, scale), hi = __fmul_rn(axis ? x2 : y2, scale);
+        const float ext = __fsub_rn(hi, lo);
+        const float size = ext > 1.f ? ext : 1.f;                  // max(extent, 1); a NaN extent gives 1
+        const Tap tp = msroi_tap(lo, __fdiv_rn(size, (float)P), p, i, g, axis ? W : H);
+        s_lo[axis][m] = tp.lo; s_hi[axis][m] = tp.hi; s_wl[axis][m] = tp.wl; s_wh[axis][m] = tp.wh;
+    }
+    __syncthreads();
+    const size_t plane = (size_t)H * W;
+    const float* feat = lv.feat[lvl] + ((size_t)img * C + c0) * plane;
+    const float count = (float)(g * g);
+    for (int o = tid; o < n_out; o += PRE_THREADS) {
+        const int c = o / PP, rem = o - c * PP, ph = rem / P, pw = rem - ph * P;
+        const float* p = feat + (size_t)c * plane;
+        float acc = 0.f;
+        for (int iy = 0; iy < g; ++iy) {
+            const int ty = ph * g + iy, yl = s_lo[0][ty], yh = s_hi[0][ty];
+            if (yl < 0) continue;
+            const float ly = s_wl[0][ty], hy = s_wh[0][ty];
+            for (int ix = 0; ix < g; ++ix) {
+                const int tx = pw * g + ix, xl = s_lo[1][tx], xh = s_hi[1][tx];
+                if (xl < 0) continue;
+                const float lx = s_wl[1][tx], hx = s_wh[1][tx];
+                const float w1 = __fmul_rn(hy, hx), w2 = __fmul_rn(hy, lx), w3 = __fmul_rn(ly, hx), w4 = __fmul_rn(ly, lx);
+                float v = __fmul_rn(w1, p[yl * W + xl]);
+                v = __fadd_rn(v, __fmul_rn(w2, p[yl * W + xh]));
+                v = __fadd_rn(v, __fmul_rn(w3, p[yh * W + xl]));
+                v = __fadd_rn(v, __fmul_rn(w4, p[yh * W + xh]));
+                acc = __fadd_rn(acc, v);
+            }
+        }
+        dst[o] = __fdiv_rn(acc, count);
+    }
+}
+
+int rpn_level_args(const char* fn, const cosy_rpn_levels_t* lv, int L, int A, int B, int pre) {
+    COSY_REQUIRE(lv != nullptr, "%s: null levels", fn);
+    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "%s: L=%d outside [1, %d] levels", fn, L, COSY_RPN_MAX_LEVELS);
+    COSY_REQUIRE(A >= 1 && A <= COSY_RPN_MAX_ANCHORS, "%s: A=%d outside [1, %d] anchors per cell", fn, A, COSY_RPN_MAX_ANCHORS);
+    COSY_REQUIRE(B >= 0 && B <= RPN_MAX_IMAGES, "%s: B=%d outside [0, %d] images per call", fn, B, RPN_MAX_IMAGES);
+    COSY_REQUIRE(pre >= 1, "%s: pre_nms_top_n=%d", fn, pre);
+    COSY_REQUIRE((long)pre * L <= (long)cosy_nms_max_candidates(), "%s: pre_nms_top_n L = %ld exceeds cosy_nms_max_candidates() = %d", fn, (long)pre * L,
+                 cosy_nms_max_candidates());
+    long total = 0;
+    for (int l = 0; l < L; ++l) {
+        COSY_REQUIRE(lv->H[l] >= 1 && lv->W[l] >= 1, "%s: level %d is %d x %d cells", fn, l, lv->H[l], lv->W[l]);
+        total += (long)A * lv->H[l] * lv->W[l];
+        COSY_REQUIRE(total <= (1L << RPN_KEY_INDEX_BITS), "%s: more than 2^%d anchors per image (levels 0 .. %d)", fn, RPN_KEY_INDEX_BITS, l);
+        COSY_REQUIRE(B == 0 || (lv->objectness[l] != nullptr && lv->deltas[l] != nullptr), "%s: null objectness / deltas of level %d", fn, l);
+    }
+    return COSY_OK;
+}
+
+}  // namespace
+}  // namespace cosy
+
+using namespace cosy;
+
+extern "C" {
+
+int cosy_rpn_select(const cosy_rpn_levels_t* levels, int L, int A, int B, int pre_nms_top_n, int* sel_idx, int* sel_count, cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = rpn_level_args("cosy_rpn_select", levels, L, A, B, pre_nms_top_n)) return rc;
+    if (B == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("cosy_rpn_select", sel_idx); COSY_REQUIRE_PTR("cosy_rpn_select", sel_count);
+    hipLaunchKernelGGL(rpn_select_kernel, dim3(L, B), dim3(SEL_THREADS), 0, s, *levels, L, A, pre_nms_top_n, sel_idx, sel_count);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_rpn_decode(const cosy_rpn_levels_t* levels, int L, int A, int B, int pre_nms_top_n, const int* sel_idx, const int* sel_count,
+                    const float* net_sizes, float min_size, int cap, float* cand_boxes, float* cand_scores, int* cand_level, int* cand_src,
+                    long long* cand_keys, int* counts, float* max_coord, cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = rpn_level_args("cosy_rpn_decode", levels, L, A, B, pre_nms_top_n)) return rc;
+    COSY_REQUIRE(cap >= 64 && cap <= cosy_nms_max_candidates() && cap % 64 == 0, "cosy_rpn_decode: cap=%d is no multiple of 64 in [64, %d]", cap,
+                 cosy_nms_max_candidates());
+    COSY_REQUIRE((long)pre_nms_top_n * L <= cap, "cosy_rpn_decode: cap=%d holds fewer than pre_nms_top_n L = %ld slots", cap, (long)pre_nms_top_n * L);
+    COSY_REQUIRE(min_size >= 0.f, "cosy_rpn_decode: min_size=%g is negative or NaN", (double)min_size);
+    if (B == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("cosy_rpn_decode", sel_idx); COSY_REQUIRE_PTR("cosy_rpn_decode", sel_count); COSY_REQUIRE_PTR("cosy_rpn_decode", net_sizes);
+    COSY_REQUIRE_PTR("cosy_rpn_decode", cand_boxes); COSY_REQUIRE_PTR("cosy_rpn_decode", cand_scores); COSY_REQUIRE_PTR("cosy_rpn_decode", cand_level);
+    COSY_REQUIRE_PTR("cosy_rpn_decode", cand_src); COSY_REQUIRE_PTR("cosy_rpn_decode", cand_keys); COSY_REQUIRE_PTR("cosy_rpn_decode", counts);
+    COSY_REQUIRE_PTR("cosy_rpn_decode", max_coord);
+    COSY_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B, s));
+    COSY_CHECK_HIP(hipMemsetAsync(max_coord, 0, sizeof(float) * (size_t)B, s));
+    hipLaunchKernelGGL(rpn_decode_kernel, dim3(cdiv((long)B * cap, PRE_THREADS)), dim3(PRE_THREADS), 0, s, *levels, L, A, B, pre_nms_top_n, sel_idx,
+                       sel_count, net_sizes, min_size, cap, cand_boxes, cand_scores, cand_level, cand_src, cand_keys, counts, (unsigned*)max_coord);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_rpn_gather(const int* kept, const int* n_kept, const float* cand_boxes, const float* cand_scores, const int* cand_level,
+                    const int* cand_src, int B, int cap, int max_keep, float* proposals, float* scores, int* levels, int* src, int* counts,
+                    cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    COSY_REQUIRE(B >= 0 && B <= RPN_MAX_IMAGES && max_keep >= 0, "cosy_rpn_gather: B=%d max_keep=%d", B, max_keep);
+    COSY_REQUIRE(cap >= 64 && cap <= cosy_nms_max_candidates(), "cosy_rpn_gather: cap=%d outside [64, %d]", cap, cosy_nms_max_candidates());
+    COSY_REQUIRE((long)B * max_keep < (1L << 30), "cosy_rpn_gather: %d x %d rows are too many", B, max_keep);
+    if (B == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("cosy_rpn_gather", n_kept); COSY_REQUIRE_PTR("cosy_rpn_gather", counts);
+    if (max_keep > 0) {
+        COSY_REQUIRE_PTR("cosy_rpn_gather", kept); COSY_REQUIRE_PTR("cosy_rpn_gather", cand_boxes); COSY_REQUIRE_PTR("cosy_rpn_gather", cand_scores);
+        COSY_REQUIRE_PTR("cosy_rpn_gather", cand_level); COSY_REQUIRE_PTR("cosy_rpn_gather", cand_src); COSY_REQUIRE_PTR("cosy_rpn_gather", proposals);
+        COSY_REQUIRE_PTR("cosy_rpn_gather", scores); COSY_REQUIRE_PTR("cosy_rpn_gather", levels); COSY_REQUIRE_PTR("cosy_rpn_gather", src);
+    }
+    const long threads = (long)B * max_keep > B ? (long)B * max_keep : B;
+    hipLaunchKernelGGL(rpn_gather_kernel, dim3(cdiv(threads, PRE_THREADS)), dim3(PRE_THREADS), 0, s, kept, n_kept, cand_boxes, cand_scores, cand_level,
+                       cand_src, B, cap, max_keep, proposals, scores, levels, src, counts);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, const float* boxes, const int* im_id, const int* counts,
+                     int rows_per_image, int R, int P, int sampling_ratio, int k_min, int k_max, float* out, int* levels_out,
+                     cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    COSY_REQUIRE(levels != nullptr, "cosy_msroi_align: null levels");
+    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "cosy_msroi_align: L=%d outside [1, %d] levels", L, COSY_RPN_MAX_LEVELS);
+    COSY_REQUIRE(B >= 0 && R >= 0 && C >= 1, "cosy_msroi_align: B=%d R=%d C=%d", B, R, C);
+    COSY_REQUIRE(sampling_ratio > 0, "cosy_msroi_align: sampling_ratio=%d must be > 0", sampling_ratio);
+    COSY_REQUIRE(P >= 1 && (long)P * sampling_ratio <= MS_MAX_TAPS, "cosy_msroi_align: P=%d with sampling_ratio=%d exceeds %d taps per axis", P, sampling_ratio,
+                 MS_MAX_TAPS);
+    COSY_REQUIRE(k_min <= k_max && k_max - k_min < L, "cosy_msroi_align: k_min=%d k_max=%d do not index %d levels", k_min, k_max, L);
+    COSY_REQUIRE(R == 0 || (im_id != nullptr) != (rows_per_image >= 1), "cosy_msroi_align: exactly one of im_id and rows_per_image=%d >= 1 names the images", rows_per_image);
+    COSY_REQUIRE(counts == nullptr || im_id == nullptr, "cosy_msroi_align: counts go with rows_per_image, not with im_id");
+    COSY_REQUIRE(B >= 1 || R == 0, "cosy_msroi_align: R=%d rows without an image", R);
+    for (int l = 0; l < L; ++l) {
+        COSY_REQUIRE(levels->H[l] >= 1 && levels->W[l] >= 1 && (long)levels->H[l] * levels->W[l] < (1L << 30), "cosy_msroi_align: level %d is %d x %d cells", l,
+                     levels->H[l], levels->W[l]);
+        COSY_REQUIRE(levels->scale[l] > 0.f, "cosy_msroi_align: scale of level %d is %g", l, (double)levels->scale[l]);
+        COSY_REQUIRE(R == 0 || levels->feat[l] != nullptr, "cosy_msroi_align: null features of level %d", l);
+    }
+    if (R == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("cosy_msroi_align", boxes); COSY_REQUIRE_PTR("cosy_msroi_align", out);
+    int cg = 1;                                                    // channels per workgroup: the largest power of two with cg P^2 <= 4096
+    while (cg * 2 * P * P <= 4096 && cg * 2 <= C) cg *= 2;
+    COSY_REQUIRE(cdiv(C, cg) <= COSY_MAX_GRID_Y, "cosy_msroi_align: C=%d needs more than %d channel groups", C, COSY_MAX_GRID_Y);
+    hipLaunchKernelGGL(msroi_align_kernel, dim3(R, cdiv(C, cg)), dim3(PRE_THREADS), 0, s, *levels, L, B, C, boxes, im_id, counts, rows_per_image, P,
+                       sampling_ratio, cg, k_min, k_max, out, levels_out);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+}  // extern "C"

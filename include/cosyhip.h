@@ -824,6 +824,60 @@ int cosy_det_gather(const int* kept, const int* n_kept, const int* counts, const
 int cosy_paste_masks(const float* mask_logits, const float* boxes, const int* labels, int D, int C, int M, int H, int W, float mask_th,
                      unsigned char* out, cosy_stream_t stream);
 
+/* ---- Proposal side of the detector: the RPN head's raw outputs -> proposals, and FPN features + boxes -> RoI features (torchvision 0.4.2's
+ * AnchorGenerator, RegionProposalNetwork.filter_proposals, MultiScaleRoIAlign with Mask R-CNN's defaults) ----
+ * DESIGN.md section 22 holds the arithmetic: float32, one rounding per operation.  The level tables are HOST structs, passed to the kernels by
+ * value; every pointer inside them and every other pointer is DEVICE memory.  All functions check on the host before any launch (COSY_EINVAL,
+ * cosy_last_error() names the argument); nothing is allocated.
+ *
+ * cosy_rpn_levels_t: level l has H[l] x W[l] cells of A anchors; objectness[l] (B,A,H,W) and deltas[l] (B,4A,H,W) are the head's NCHW float32
+ * outputs, read in place; anchor i of a level = (y W + x) A + a has the box base[l][a] + (x stride_w[l], y stride_h[l]) on both corners; an
+ * image's candidate index is i plus the anchors of the levels before l.  Limits: L <= 8, A <= 16, B <= 2047, at most 2^20 anchors per image,
+ * pre_nms_top_n L <= cosy_nms_max_candidates().
+ *
+ * cosy_rpn_select: per image and level the k = min(pre_nms_top_n, present anchors) largest objectness LOGITS (no sigmoid; -0 counts as +0);
+ * an anchor whose logit or any of its four deltas is NaN is absent.  sel_idx (B,L,pre_nms_top_n) int32 takes the anchors strictly above the
+ * k-th value in ascending index order, then the lowest-index anchors AT it; sel_count (B,L) = k; rows past k are not written.  One launch.
+ * cosy_rpn_decode: one slot of the arena (B cap; cap a multiple of 64 with pre_nms_top_n L <= cap <= cosy_nms_max_candidates()) per selected
+ * anchor, slot = l pre_nms_top_n + rank: BoxCoder.decode with weights 1 and the log(1000/16) clamp, x clipped to [0, net_sizes[b][1]], y to
+ * [0, net_sizes[b][0]] (net_sizes (B,2) float32 = height, width of the image itself), kept when both sides >= min_size.  A kept slot holds
+ * cand_boxes, cand_scores (the logit), cand_level, cand_src (candidate index) and cand_keys (int64) = b << 52 | (0xffffffff - ordered score)
+ * << 20 | cand_src; every other slot holds the key b << 52 | 2^52 - 1 only: sorting ALL B cap keys ascending lists every image's candidates by
+ * descending score, equal scores by ascending candidate index.  counts (B) = kept slots, max_coord (B) = their largest coordinate (0 without
+ * any): what cosy_nms_mask / cosy_nms_scan take as seg_count and max_coord with labels = cand_level.  Two memsets and one launch.
+ * cosy_rpn_gather: kept / n_kept of cosy_nms_scan -> proposals (B max_keep,4), scores, levels, src (candidate index), padded with zeros
+ * (level and src -1) past counts[b] = n_kept[b]. */
+#define COSY_RPN_MAX_LEVELS 8
+#define COSY_RPN_MAX_ANCHORS 16
+typedef struct cosy_rpn_levels {
+    const float* objectness[COSY_RPN_MAX_LEVELS];
+    const float* deltas[COSY_RPN_MAX_LEVELS];
+    int H[COSY_RPN_MAX_LEVELS], W[COSY_RPN_MAX_LEVELS];
+    float stride_h[COSY_RPN_MAX_LEVELS], stride_w[COSY_RPN_MAX_LEVELS];
+    float base[COSY_RPN_MAX_LEVELS][COSY_RPN_MAX_ANCHORS][4]; /* x1, y1, x2, y2 */
+} cosy_rpn_levels_t;
+int cosy_rpn_select(const cosy_rpn_levels_t* levels, int L, int A, int B, int pre_nms_top_n, int* sel_idx, int* sel_count, cosy_stream_t stream);
+int cosy_rpn_decode(const cosy_rpn_levels_t* levels, int L, int A, int B, int pre_nms_top_n, const int* sel_idx, const int* sel_count,
+                    const float* net_sizes, float min_size, int cap, float* cand_boxes, float* cand_scores, int* cand_level, int* cand_src,
+                    long long* cand_keys, int* counts, float* max_coord, cosy_stream_t stream);
+int cosy_rpn_gather(const int* kept, const int* n_kept, const float* cand_boxes, const float* cand_scores, const int* cand_level,
+                    const int* cand_src, int B, int cap, int max_keep, float* proposals, float* scores, int* levels, int* src, int* counts,
+                    cosy_stream_t stream);
+/* MultiScaleRoIAlign in one launch: boxes (R,4) xyxy at the network's scale; row r belongs to image im_id[r] (R int32), or, with im_id null, to
+ * image r / rows_per_image, and then counts (B int32, may be null) makes the rows r % rows_per_image >= counts[image] padding.  Level of a box
+ * = clamp(floor(4 + log2(sqrt(area) / 224 + 1e-6)), k_min, k_max) - k_min (NaN: 0), which must index the L levels (k_max - k_min < L);
+ * feat[l] is (B,C,H[l],W[l]) float32.  roi_align as torchvision 0.4.2 (no `aligned`): start x1 scale, size max(x2 scale - x1 scale, 1), P x P
+ * bins of sampling_ratio^2 samples, a sample outside [-1, size] (or NaN) adds 0.  out (R,C,P,P) is written in full: a padding row, or one
+ * whose image is outside [0, B), holds zeros and level -1.  levels_out (R int32) may be null.  P sampling_ratio <= 128, sampling_ratio >= 1. */
+typedef struct cosy_msroi_levels {
+    const float* feat[COSY_RPN_MAX_LEVELS];
+    int H[COSY_RPN_MAX_LEVELS], W[COSY_RPN_MAX_LEVELS];
+    float scale[COSY_RPN_MAX_LEVELS];
+} cosy_msroi_levels_t;
+int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, const float* boxes, const int* im_id, const int* counts,
+                     int rows_per_image, int R, int P, int sampling_ratio, int k_min, int k_max, float* out, int* levels_out,
+                     cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
