@@ -73,6 +73,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('rpn_anchors', 'rpn_proposals', 'multiscale_roi_align', 'detections_from_features'):
         from . import detector_rpn
         return getattr(detector_rpn, name)
+    if name in ('match_boxes', 'sample_balanced', 'encode_boxes', 'rpn_loss', 'roi_training_samples', 'fastrcnn_loss', 'mask_targets',
+                'maskrcnn_loss', 'detector_losses', 'AnchorGrid'):
+        from . import detector_train
+        return getattr(detector_train, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

@@ -136,6 +136,14 @@ _SIGNATURES = {
     'cosy_rpn_decode': ([_P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     'cosy_rpn_gather': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     'cosy_msroi_align': ([_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    'cosy_dt_match': ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P], _I),
+    'cosy_dt_sample': ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    'cosy_dt_encode': ([_P, _P, _L, _F, _F, _F, _F, _P, _P], _I),
+    'cosy_dt_rpn_loss': ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_dt_roi_candidates': ([_P, _P, _I, _P, _P, _I, _I, _P, _P, _P], _I),
+    'cosy_dt_roi_gather': ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_dt_fastrcnn_loss': ([_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    'cosy_dt_mask_loss': ([_P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P], _I),
     'cosy_resize_ksize': ([_I, _I, _I], _I),
     'cosy_resize_coeffs': ([_I, _I, _I, _P, _P, _SZ], _I),
     'cosy_resize_workspace_bytes': ([_I, _I, _I, _I], _SZ),

@@ -23,4 +23,21 @@ __device__ __forceinline__ float box_iou(const Box& a, const Box& b) {
     return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
 }
 
+// one tap line of roi_align along one axis (kernels_geom.hip roi_pixel's rules), shared by kernels_detpre.hip (multi-scale RoIAlign) and
+// kernels_dettrain.hip (mask targets): lo < 0 marks a sample outside [-1, size], which adds nothing
+struct Tap { int lo, hi; float wl, wh; };
+
+__device__ __forceinline__ Tap msroi_tap(float start, float bin, int p, int i, int g, int size) {
+    float v = __fadd_rn(__fadd_rn(start, __fmul_rn((float)p, bin)), __fdiv_rn(__fmul_rn(__fadd_rn((float)i, .5f), bin), (float)g));
+    Tap t = {-1, -1, 0.f, 0.f};
+    if (!(v >= -1.0f && v <= (float)size)) return t;               // (a NaN sample is outside too)
+    if (v <= 0.f) v = 0.f;
+    int lo = (int)v, hi;
+    if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else hi = lo + 1;
+    t.lo = lo; t.hi = hi;
+    t.wl = __fsub_rn(v, (float)lo);                                // weight of the high tap
+    t.wh = __fsub_rn(1.f, t.wl);                                   // weight of the low tap
+    return t;
+}
+
 }  // namespace cosy

@@ -232,22 +232,7 @@ __global__ __launch_bounds__(PRE_THREADS) void rpn_gather_kernel(const int* __re
     scores[at] = sc; levels[at] = lvl; src[at] = s;
 }
 
-// one tap line of roi_align along one axis (kernels_geom.hip roi_pixel's rules): lo < 0 marks a sample outside [-1, size], which adds nothing
-struct Tap { int lo, hi; float wl, wh; };
-
-__device__ __forceinline__ Tap msroi_tap(float start, float bin, int p, int i, int g, int size) {
-    float v = __fadd_rn(__fadd_rn(start, __fmul_rn((float)p, bin)), __fdiv_rn(__fmul_rn(__fadd_rn((float)i, .5f), bin), (float)g));
-    Tap t = {-1, -1, 0.f, 0.f};
-    if (!(v >= -1.0f && v <= (float)size)) return t;               // (a NaN sample is outside too)
-    if (v <= 0.f) v = 0.f;
-    int lo = (int)v, hi;
-    if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else hi = lo + 1;
-    t.lo = lo; t.hi = hi;
-    t.wl = __fsub_rn(v, (float)lo);                                // weight of the high tap
-    t.wh = __fsub_rn(1.f, t.wl);                                   // weight of the low tap
-    return t;
-}
-
+// (Tap / msroi_tap, one tap line of roi_align along one axis, live in det_device.h: the mask targets of kernels_dettrain.hip use them too)
 __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, int L, int B, int C, const float* __restrict__ boxes,
                                                                   const int* __restrict__ im_id, const int* __restrict__ counts,
                                                                   int rows_per_image, int P, int g, int cg, int k_min, int k_max,

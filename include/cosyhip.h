@@ -878,6 +878,64 @@ int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, con
                      int rows_per_image, int R, int P, int sampling_ratio, int k_min, int k_max, float* out, int* levels_out,
                      cosy_stream_t stream);
 
+/* ---- Training side of the detector: the heads' raw outputs + targets -> Mask R-CNN's five losses and their gradients (torchvision 0.4.2's
+ * Matcher, BalancedPositiveNegativeSampler, BoxCoder.encode, RPN compute_loss, select_training_samples, fastrcnn_loss, maskrcnn_loss) ----
+ * DESIGN.md section 23 holds the arithmetic: float32, one rounding per operation; loss sums in float64 in a fixed order, rounded once.  Every
+ * pointer is DEVICE memory except the level tables (host structs passed by value).  All functions check on the host before any launch
+ * (COSY_EINVAL, cosy_last_error() names the argument); nothing is allocated; integer atomics only.
+ * Ground truths of all images are concatenated: gt_boxes (G_total,4) xyxy, gt_off (B+1) int32 offsets, at most COSY_DT_MAX_GT per image.
+ *
+ * cosy_dt_match: Matcher(high, low, allow_low_quality) over box_iou(gt, candidates) for N candidates per image: anchors formed from their
+ * index (cand_boxes null; levels as for cosy_rpn_select, the head pointers unused; N = the levels' anchors) or rows of cand_boxes (B N,4), of
+ * which only the first cand_counts[b] (null: all) are candidates.  A NaN or negative IoU counts as 0; equal IoUs go to the lowest ground truth.
+ * matched (B,N) int32: the ground truth's index, -1 below low, -2 between, -3 on a padding row; matched_iou (B,N); labels (B,N, may be null):
+ * gt_labels[matched] (1 without gt_labels) / 0 for -1 / -1 otherwise.  best_ws: G_total uint32 of scratch for allow_low_quality.
+ * cosy_dt_sample: BalancedPositiveNegativeSampler over labels (B,N) with int32 keys (B,N) read as unsigned: the min(max_positives, P) positives
+ * (label >= 1) and the min(batch_size_per_image - that, N) negatives (label 0) with the smallest keys, equal keys lower index first.  samp_idx
+ * (B, batch_size_per_image): all sampled indices ascending, samp_count (B); pos_idx (B, max_positives) / pos_count (B): the positives.  Rows past
+ * the counts are not written.  One launch, one workgroup per image.
+ * cosy_dt_encode: BoxCoder.encode_single(reference_boxes, boxes) with the four weights, n rows.
+ * cosy_dt_rpn_loss: levels hold the head's outputs, grads (same layout) the gradient tensors, which the caller has ZEROED: the sampled anchors'
+ * entries are written.  losses[0] = mean BCE-with-logits over the sampled anchors, losses[1] = sum |d - t| over the sampled positives / the
+ * sampled.  terms_ws: 2 B batch_size_per_image doubles.
+ * cosy_dt_roi_candidates: cand_boxes (B (rows_per_image + G_max), 4) = the first counts[b] proposals of image b, its ground truths, zeros;
+ * cand_counts (B).
+ * cosy_dt_roi_gather: the sampled rows of cosy_dt_sample over N candidates per image -> boxes, labels (-1: padding), the CLAMPED matched index
+ * and the regression targets (B batch_size_per_image rows), and the positives' boxes, labels, matched index (B max_positives rows).
+ * cosy_dt_fastrcnn_loss: rows with a label outside [0, C) are padding.  losses[0] = mean cross-entropy over the N real rows, losses[1] = sum of
+ * smooth-L1(beta 1) over the rows with label > 0 / N; grad_logits (R,C) and grad_box (R,4C) are written in full.  n_real_ws: 1 int, terms_ws:
+ * 2 R doubles.
+ * cosy_dt_mask_loss: one positive RoI per row, B rows_per_image rows, of which image b's first pos_count[b] (null: all) are real.  mask_ptr (B)
+ * int64 addresses of the images' uint8 masks (G,H,W), mask_dims (B,3) int32 = G, H, W with H W < 2^30 (a row whose image says otherwise, or whose
+ * matched index lies outside [0, G), is written as zeros).  Targets: roi_align with the adaptive grid g =
+ * min(ceil(max(extent, 1) / M), COSY_DT_MAX_GRID) per axis.  With mask_logits (R,C,M,M): loss = mean BCE-with-logits(mask_logits[r, labels[r]],
+ * target) over the real rows, grad (R,C,M,M) written in full, partial_ws R doubles.  targets_out (R,M,M) may be null. */
+#define COSY_DT_MAX_GT 1024
+#define COSY_DT_MAX_BATCH 4096
+#define COSY_DT_MAX_CLASSES 4096
+#define COSY_DT_MAX_M 128
+#define COSY_DT_MAX_GRID 4096
+int cosy_dt_match(const cosy_rpn_levels_t* levels, int L, int A, const float* cand_boxes, const int* cand_counts, int N, int B, const float* gt_boxes,
+                  const int* gt_off, const int* gt_labels, int G_max, int G_total, float high, float low, int allow_low_quality, unsigned* best_ws,
+                  int* matched, float* matched_iou, int* labels, cosy_stream_t stream);
+int cosy_dt_sample(const int* labels, const int* keys, int N, int B, int batch_size_per_image, int max_positives, int* samp_idx, int* samp_count,
+                   int* pos_idx, int* pos_count, cosy_stream_t stream);
+int cosy_dt_encode(const float* reference_boxes, const float* boxes, long n, float wx, float wy, float ww, float wh, float* out, cosy_stream_t stream);
+int cosy_dt_rpn_loss(const cosy_rpn_levels_t* levels, const cosy_rpn_levels_t* grads, int L, int A, int B, int batch_size_per_image, const int* samp_idx,
+                     const int* samp_count, const int* matched, const float* gt_boxes, const int* gt_off, double* terms_ws, float* losses,
+                     cosy_stream_t stream);
+int cosy_dt_roi_candidates(const float* proposals, const int* counts, int rows_per_image, const float* gt_boxes, const int* gt_off, int B, int G_max,
+                           float* cand_boxes, int* cand_counts, cosy_stream_t stream);
+int cosy_dt_roi_gather(const float* cand_boxes, int N, const int* matched, const int* labels, const int* samp_idx, const int* samp_count,
+                       const int* pos_idx, const int* pos_count, const float* gt_boxes, const int* gt_off, int B, int batch_size_per_image,
+                       int max_positives, float wx, float wy, float ww, float wh, float* boxes, int* out_labels, int* out_matched, float* targets,
+                       float* pos_boxes, int* pos_labels, int* pos_matched, cosy_stream_t stream);
+int cosy_dt_fastrcnn_loss(const float* class_logits, const float* box_regression, const int* labels, const float* regression_targets, int R, int C,
+                          int* n_real_ws, double* terms_ws, float* grad_logits, float* grad_box, float* losses, cosy_stream_t stream);
+int cosy_dt_mask_loss(const long long* mask_ptr, const int* mask_dims, int B, const float* boxes, const int* labels, const int* matched,
+                      const int* pos_count, int rows_per_image, const float* mask_logits, int C, int M, double* partial_ws, float* grad, float* targets_out,
+                      float* loss, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
