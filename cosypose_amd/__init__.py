@@ -70,7 +70,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('nms', 'batched_nms', 'postprocess_detections', 'paste_masks', 'detections_from_heads'):
         from . import detector
         return getattr(detector, name)
-    if name in ('rpn_anchors', 'rpn_proposals', 'multiscale_roi_align', 'detections_from_features'):
+    if name in ('rpn_anchors', 'rpn_proposals', 'multiscale_roi_align', 'roi_align', 'detections_from_features'):
         from . import detector_rpn
         return getattr(detector_rpn, name)
     if name in ('match_boxes', 'sample_balanced', 'encode_boxes', 'rpn_loss', 'roi_training_samples', 'fastrcnn_loss', 'mask_targets',

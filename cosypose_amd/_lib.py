@@ -136,6 +136,7 @@ _SIGNATURES = {
     'cosy_rpn_decode': ([_P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     'cosy_rpn_gather': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     'cosy_msroi_align': ([_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    'cosy_msroi_align_backward': ([_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     'cosy_dt_match': ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P], _I),
     'cosy_dt_sample': ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     'cosy_dt_encode': ([_P, _P, _L, _F, _F, _F, _F, _P, _P], _I),

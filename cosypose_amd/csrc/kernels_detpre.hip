@@ -14,6 +14,10 @@
 //   rpn_gather_kernel        the kept rows of cosy_nms_scan into (B, max_keep) padded proposals, scores, levels, candidate indices, counts
 //   msroi_align_kernel       a workgroup owns one RoI and a group of channels: level mapper, then the P g tap indices and weights of each axis
 //                            once into LDS (the taps are separable); lanes run over (channel, ph, pw), pw fastest, and write (R, C, P, P).
+//   msroi_rows_kernel, msroi_align_backward_kernel   the adjoint of msroi_align_kernel into the feature maps, as a gather (DESIGN.md section
+//                            24; tests/detbwd_ref.py is its twin): one thread per row notes image, level and touched cells; then a workgroup
+//                            owns 16 x 16 cells of one (image, level) and 32 channels, lists the rows that meet its tile in ascending index
+//                            and adds their terms to registers in a fixed order.  Every cell is stored once; no memset, no float atomic.
 // Integer atomics only.  float32 with one rounding per operation: contraction is off (the pragma below and build.FILE_FLAGS).
 #include <math.h>
 #include "cosy_common.h"
@@ -233,6 +237,23 @@ __global__ __launch_bounds__(PRE_THREADS) void rpn_gather_kernel(const int* __re
 }
 
 // (Tap / msroi_tap, one tap line of roi_align along one axis, live in det_device.h: the mask targets of kernels_dettrain.hip use them too)
+// The two pieces of a row that msroi_align_kernel and its adjoint must agree on to the bit: one definition each.
+// LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min; a NaN (negative area) takes k_min
+__device__ __forceinline__ int msroi_level(float x1, float y1, float x2, float y2, int k_min, int k_max) {
+    const float sz = sqrtf(__fmul_rn(__fsub_rn(x2, x1), __fsub_rn(y2, y1)));
+    const float t = floorf(__fadd_rn(4.f, log2f(__fadd_rn(__fdiv_rn(sz, 224.f), 1e-6f))));
+    const int lvl = !(t >= (float)k_min) ? k_min : t > (float)k_max ? k_max : (int)t;
+    return lvl - k_min;
+}
+// tap m = p g + i of one axis of a box [c1, c2] at a level of `size` cells
+__device__ __forceinline__ Tap msroi_axis_tap(float c1, float c2, float scale, int P, int g, int m, int size) {
+    const int p = m / g, i = m - p * g;
+    const float lo = __fmul_rn(c1, scale), hi = __fmul_rn(c2, scale);
+    const float ext = __fsub_rn(hi, lo);
+    const float extent = ext > 1.f ? ext : 1.f;                    // max(extent, 1); a NaN extent gives 1
+    return msroi_tap(lo, __fdiv_rn(extent, (float)P), p, i, g, size);
+}
+
 __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, int L, int B, int C, const float* __restrict__ boxes,
                                                                   const int* __restrict__ im_id, const int* __restrict__ counts,
                                                                   int rows_per_image, int P, int g, int cg, int k_min, int k_max,
@@ -248,11 +269,7 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, i
     bool row = img >= 0 && img < B;
     if (row && counts) row = r - img * rows_per_image < counts[img];
     const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
-    // LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max]; a NaN (negative area) takes k_min
-    const float sz = sqrtf(__fmul_rn(__fsub_rn(x2, x1), __fsub_rn(y2, y1)));
-    const float t = floorf(__fadd_rn(4.f, log2f(__fadd_rn(__fdiv_rn(sz, 224.f), 1e-6f))));
-    int lvl = !(t >= (float)k_min) ? k_min : t > (float)k_max ? k_max : (int)t;
-    lvl -= k_min;
+    const int lvl = msroi_level(x1, y1, x2, y2, k_min, k_max);
     if (lvl < 0 || lvl >= L) row = false;                          // (the entry point refuses k_max - k_min >= L: never taken)
     if (blockIdx.y == 0 && tid == 0 && levels_out) levels_out[r] = row ? lvl : -1;
     if (!row) {                                                    // a row no image owns: zeros
@@ -263,11 +280,8 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, i
     const float scale = lv.scale[lvl];
     const int taps = P * g;
     for (int q = tid; q < 2 * taps; q += PRE_THREADS) {
-        const int axis = q / taps, m = q - axis * taps, p = m / g, i = m - p * g;
-        const float lo = __fmul_rn(axis ? x1 : y1, scale), hi = __fmul_rn(axis ? x2 : y2, scale);
-        const float ext = __fsub_rn(hi, lo);
-        const float size = ext > 1.f ? ext : 1.f;                  // max(extent, 1); a NaN extent gives 1
-        const Tap tp = msroi_tap(lo, __fdiv_rn(size, (float)P), p, i, g, axis ? W : H);
+        const int axis = q / taps, m = q - axis * taps;
+        const Tap tp = msroi_axis_tap(axis ? x1 : y1, axis ? x2 : y2, scale, P, g, m, axis ? W : H);
         s_lo[axis][m] = tp.lo; s_hi[axis][m] = tp.hi; s_wl[axis][m] = tp.wl; s_wh[axis][m] = tp.wh;
     }
     __syncthreads();
@@ -298,7 +312,154 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, i
     }
 }
 
-int rpn_level_args(const char* fn, const cosy_rpn_levels_t* lv, int L, int A, int B, int pre) {
+// ---- the adjoint of msroi_align_kernel: a gather, DESIGN.md section 24 ----------------------------------------------------------------
+constexpr int BWD_TILE = 16;                                     // a workgroup owns 16 x 16 cells of one (image, level): one cell per thread
+constexpr int BWD_CG = 32;                                       // ... and up to 32 channels, one accumulator register each
+constexpr int BWD_SLOTS = 4;                                     // listed rows staged at a time, one per wave
+constexpr int BWD_WS = 8;                                        // ints per row of the workspace: image (-1: adds nothing), level, y lo, y hi, x lo, x hi
+constexpr int BWD_ENTRIES = 2 * MS_MAX_TAPS;                     // a tap puts its low and its high weight on one cell each
+
+struct BwdPlan {
+    float* grad[COSY_RPN_MAX_LEVELS];
+    int first[COSY_RPN_MAX_LEVELS + 1];                            // blocks [first[l], first[l+1]) are level l's B x tiles; none for a level not asked for
+    int tiles_x[COSY_RPN_MAX_LEVELS], tiles[COSY_RPN_MAX_LEVELS];
+};
+
+// one thread per row: what the forward decides once per row (image, padding, level) and the cells its valid taps touch
+__global__ __launch_bounds__(PRE_THREADS) void msroi_rows_kernel(MsLevels lv, int L, int B, const float* __restrict__ boxes,
+                                                                 const int* __restrict__ im_id, const int* __restrict__ counts,
+                                                                 int rows_per_image, int R, int P, int g, int k_min, int k_max,
+                                                                 int* __restrict__ ws) {
+    const long r = (long)blockIdx.x * PRE_THREADS + threadIdx.x;
+    if (r >= R) return;
+    const int img = im_id ? im_id[r] : (int)(r / rows_per_image);
+    bool row = img >= 0 && img < B;
+    if (row && counts) row = r - (long)img * rows_per_image < counts[img];
+    const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
+    const int lvl = msroi_level(x1, y1, x2, y2, k_min, k_max);
+    if (lvl < 0 || lvl >= L) row = false;
+    int lo[2] = {0x7fffffff, 0x7fffffff}, hi[2] = {-1, -1};
+    if (row) {
+        const float scale = lv.scale[lvl];
+        for (int axis = 0; axis < 2; ++axis)
+            for (int m = 0; m < P * g; ++m) {
+                const Tap t = msroi_axis_tap(axis ? x1 : y1, axis ? x2 : y2, scale, P, g, m, axis ? lv.W[lvl] : lv.H[lvl]);
+                if (t.lo < 0) continue;
+                lo[axis] = t.lo < lo[axis] ? t.lo : lo[axis];
+                hi[axis] = t.hi > hi[axis] ? t.hi : hi[axis];
+            }
+        row = hi[0] >= 0 && hi[1] >= 0;                            // no valid sample on an axis: every value of the row was 0
+    }
+    int* w = ws + BWD_WS * (size_t)r;
+    w[0] = row ? img : -1; w[1] = lvl; w[2] = lo[0]; w[3] = hi[0]; w[4] = lo[1]; w[5] = hi[1]; w[6] = 0; w[7] = 0;
+}
+
+// A workgroup owns a tile of one (image, level) and a group of channels.  It walks the image's rows in ascending index, 256 at a time, and
+// lists (ballot-ordered, so still ascending) those of its level whose taps meet the tile.  Wave w then stages listed row i + w: per axis its
+// taps' weights bucketed by the tile's 16 coordinates, inside a bucket by ascending tap, of one tap the low weight first.  Every thread adds
+// rows in list order, y entries outer, x entries inner: acc = fl(acc + fl(fl(wy wx) g)), and stores fl(acc / g^2) once.
+__global__ __launch_bounds__(PRE_THREADS) void msroi_align_backward_kernel(MsLevels lv, BwdPlan plan, int L, int B, int C,
+                                                                           const float* __restrict__ grad_out,
+                                                                           const float* __restrict__ boxes, const int* __restrict__ ws,
+                                                                           int rows_per_image, int R, int P, int g) {
+    __shared__ int s_list[PRE_THREADS];
+    __shared__ int s_wave[PRE_THREADS / 64];
+    __shared__ int s_start[BWD_SLOTS][2][BWD_TILE + 1];
+    __shared__ unsigned char s_bin[BWD_SLOTS][2][BWD_ENTRIES];     // p of the entry's tap
+    __shared__ float s_w[BWD_SLOTS][2][BWD_ENTRIES];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int l = 0;
+    while (l + 1 < L && (int)blockIdx.x >= plan.first[l + 1]) ++l;  // (uniform)
+    const int within = (int)blockIdx.x - plan.first[l];
+    const int b = within / plan.tiles[l], t = within - b * plan.tiles[l];
+    const int tile_y = t / plan.tiles_x[l], tile_x = t - tile_y * plan.tiles_x[l];
+    const int H = lv.H[l], W = lv.W[l];
+    const float scale = lv.scale[l];
+    const int y0 = tile_y * BWD_TILE, x0 = tile_x * BWD_TILE, ly = tid >> 4, lx = tid & 15;
+    const int c0 = blockIdx.y * BWD_CG, nc = C - c0 < BWD_CG ? C - c0 : BWD_CG;
+    const int PP = P * P, taps = P * g;
+    const long r_first = rows_per_image ? (long)b * rows_per_image : 0, r_last = rows_per_image ? r_first + rows_per_image : R;
+    const int r_begin = (int)(r_first < R ? r_first : R), r_end = (int)(r_last < R ? r_last : R);
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    float acc[BWD_CG];
+#pragma unroll
+    for (int c = 0; c < BWD_CG; ++c) acc[c] = 0.f;
+    for (int chunk = r_begin; chunk < r_end; chunk += PRE_THREADS) {
+        const int r = chunk + tid;
+        bool take = false;
+        if (r < r_end) {
+            const int* w = ws + BWD_WS * (size_t)r;
+            take = w[0] == b && w[1] == l && w[2] < y0 + BWD_TILE && w[3] >= y0 && w[4] < x0 + BWD_TILE && w[5] >= x0;
+        }
+        const unsigned long long mine = __ballot(take);
+        if (lane == 0) s_wave[wave] = __popcll(mine);
+        __syncthreads();
+        int before = 0, n = 0;
+        for (int w = 0; w < PRE_THREADS / 64; ++w) { const int c = s_wave[w]; before += w < wave ? c : 0; n += c; }
+        if (take) s_list[before + __popcll(mine & below)] = r;
+        __syncthreads();
+        for (int i0 = 0; i0 < n; i0 += BWD_SLOTS) {
+            if (i0 + wave < n) {                                   // (uniform over the wave) stage one row per wave
+                const int rr = s_list[i0 + wave];
+                for (int axis = 0; axis < 2; ++axis) {
+                    const float a1 = boxes[4 * (size_t)rr + 1 - axis], a2 = boxes[4 * (size_t)rr + 3 - axis];
+                    const int size = axis ? W : H, first = axis ? x0 : y0;
+                    Tap tp[2];                                     // taps lane and lane + 64 (MS_MAX_TAPS = 128)
+#pragma unroll
+                    for (int pass = 0; pass < 2; ++pass) {
+                        tp[pass] = Tap{-1, -1, 0.f, 0.f};
+                        if (lane + 64 * pass < taps) tp[pass] = msroi_axis_tap(a1, a2, scale, P, g, lane + 64 * pass, size);
+                    }
+                    int cnt = 0;                                   // (uniform) at most 2 taps entries over the 16 buckets
+                    for (int k = 0; k < BWD_TILE; ++k) {
+                        if (lane == 0) s_start[wave][axis][k] = cnt;
+#pragma unroll
+                        for (int pass = 0; pass < 2; ++pass) {
+                            if (pass * 64 >= taps) continue;       // (uniform)
+                            const Tap q = tp[pass];
+                            const bool on_lo = q.lo == first + k, on_hi = q.hi == first + k;   // (an invalid tap has lo = hi = -1)
+                            const unsigned long long blo = __ballot(on_lo), bhi = __ballot(on_hi);
+                            const int pos = cnt + __popcll(blo & below) + __popcll(bhi & below);
+                            const unsigned char bin = (unsigned char)((lane + 64 * pass) / g);
+                            if (on_lo) { s_bin[wave][axis][pos] = bin; s_w[wave][axis][pos] = q.wh; }                 // wh: the low tap's weight
+                            if (on_hi) { s_bin[wave][axis][pos + (on_lo ? 1 : 0)] = bin; s_w[wave][axis][pos + (on_lo ? 1 : 0)] = q.wl; }
+                            cnt += __popcll(blo) + __popcll(bhi);
+                        }
+                    }
+                    if (lane == 0) s_start[wave][axis][BWD_TILE] = cnt;
+                }
+            }
+            __syncthreads();
+            for (int s = 0; s < BWD_SLOTS && i0 + s < n; ++s) {
+                const int ys = s_start[s][0][ly], ye = s_start[s][0][ly + 1], xs = s_start[s][1][lx], xe = s_start[s][1][lx + 1];
+                if (ys == ye || xs == xe) continue;
+                const float* gr = grad_out + ((size_t)s_list[i0 + s] * C + c0) * PP;
+                for (int ey = ys; ey < ye; ++ey) {
+                    const float wy = s_w[s][0][ey];
+                    const float* gy = gr + (int)s_bin[s][0][ey] * P;
+                    for (int ex = xs; ex < xe; ++ex) {
+                        const float w = __fmul_rn(wy, s_w[s][1][ex]);
+                        const float* gp = gy + (int)s_bin[s][1][ex];
+#pragma unroll
+                        for (int c = 0; c < BWD_CG; ++c)
+                            if (c < nc) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, gp[(size_t)c * PP]));
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        __syncthreads();                                           // s_wave and s_list are rewritten by the next chunk
+    }
+    const int y = y0 + ly, x = x0 + lx;
+    if (y >= H || x >= W) return;
+    const float count = (float)(g * g);
+    float* dst = plan.grad[l] + (((size_t)b * C + c0) * H + y) * W + x;
+#pragma unroll
+    for (int c = 0; c < BWD_CG; ++c)
+        if (c < nc) dst[(size_t)c * H * W] = __fdiv_rn(acc[c], count);
+}
+
+int rpn_level_args(const char* fn,const cosy_rpn_levels_t* lv, int L, int A, int B, int pre) {
     COSY_REQUIRE(lv != nullptr, "%s: null levels", fn);
     COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "%s: L=%d outside [1, %d] levels", fn, L, COSY_RPN_MAX_LEVELS);
     COSY_REQUIRE(A >= 1 && A <= COSY_RPN_MAX_ANCHORS, "%s: A=%d outside [1, %d] anchors per cell", fn, A, COSY_RPN_MAX_ANCHORS);
@@ -312,6 +473,28 @@ int rpn_level_args(const char* fn, const cosy_rpn_levels_t* lv, int L, int A, in
         total += (long)A * lv->H[l] * lv->W[l];
         COSY_REQUIRE(total <= (1L << RPN_KEY_INDEX_BITS), "%s: more than 2^%d anchors per image (levels 0 .. %d)", fn, RPN_KEY_INDEX_BITS, l);
         COSY_REQUIRE(B == 0 || (lv->objectness[l] != nullptr && lv->deltas[l] != nullptr), "%s: null objectness / deltas of level %d", fn, l);
+    }
+    return COSY_OK;
+}
+
+// what cosy_msroi_align and its backward refuse alike
+int msroi_args(const char* fn, const cosy_msroi_levels_t* levels, int L, int B, int C, const int* im_id, const int* counts, int rows_per_image,
+               int R, int P, int sampling_ratio, int k_min, int k_max) {
+    COSY_REQUIRE(levels != nullptr, "%s: null levels", fn);
+    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "%s: L=%d outside [1, %d] levels", fn, L, COSY_RPN_MAX_LEVELS);
+    COSY_REQUIRE(B >= 0 && R >= 0 && C >= 1, "%s: B=%d R=%d C=%d", fn, B, R, C);
+    COSY_REQUIRE(sampling_ratio > 0, "%s: sampling_ratio=%d must be > 0", fn, sampling_ratio);
+    COSY_REQUIRE(P >= 1 && (long)P * sampling_ratio <= MS_MAX_TAPS, "%s: P=%d with sampling_ratio=%d exceeds %d taps per axis", fn, P, sampling_ratio,
+                 MS_MAX_TAPS);
+    COSY_REQUIRE(k_min <= k_max && k_max - k_min < L, "%s: k_min=%d k_max=%d do not index %d levels", fn, k_min, k_max, L);
+    COSY_REQUIRE(R == 0 || (im_id != nullptr) != (rows_per_image >= 1), "%s: exactly one of im_id and rows_per_image=%d >= 1 names the images", fn,
+                 rows_per_image);
+    COSY_REQUIRE(counts == nullptr || im_id == nullptr, "%s: counts go with rows_per_image, not with im_id", fn);
+    COSY_REQUIRE(B >= 1 || R == 0, "%s: R=%d rows without an image", fn, R);
+    for (int l = 0; l < L; ++l) {
+        COSY_REQUIRE(levels->H[l] >= 1 && levels->W[l] >= 1 && (long)levels->H[l] * levels->W[l] < (1L << 30), "%s: level %d is %d x %d cells", fn, l,
+                     levels->H[l], levels->W[l]);
+        COSY_REQUIRE(levels->scale[l] > 0.f, "%s: scale of level %d is %g", fn, l, (double)levels->scale[l]);
     }
     return COSY_OK;
 }
@@ -380,22 +563,8 @@ int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, con
                      int rows_per_image, int R, int P, int sampling_ratio, int k_min, int k_max, float* out, int* levels_out,
                      cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    COSY_REQUIRE(levels != nullptr, "cosy_msroi_align: null levels");
-    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "cosy_msroi_align: L=%d outside [1, %d] levels", L, COSY_RPN_MAX_LEVELS);
-    COSY_REQUIRE(B >= 0 && R >= 0 && C >= 1, "cosy_msroi_align: B=%d R=%d C=%d", B, R, C);
-    COSY_REQUIRE(sampling_ratio > 0, "cosy_msroi_align: sampling_ratio=%d must be > 0", sampling_ratio);
-    COSY_REQUIRE(P >= 1 && (long)P * sampling_ratio <= MS_MAX_TAPS, "cosy_msroi_align: P=%d with sampling_ratio=%d exceeds %d taps per axis", P, sampling_ratio,
-                 MS_MAX_TAPS);
-    COSY_REQUIRE(k_min <= k_max && k_max - k_min < L, "cosy_msroi_align: k_min=%d k_max=%d do not index %d levels", k_min, k_max, L);
-    COSY_REQUIRE(R == 0 || (im_id != nullptr) != (rows_per_image >= 1), "cosy_msroi_align: exactly one of im_id and rows_per_image=%d >= 1 names the images", rows_per_image);
-    COSY_REQUIRE(counts == nullptr || im_id == nullptr, "cosy_msroi_align: counts go with rows_per_image, not with im_id");
-    COSY_REQUIRE(B >= 1 || R == 0, "cosy_msroi_align: R=%d rows without an image", R);
-    for (int l = 0; l < L; ++l) {
-        COSY_REQUIRE(levels->H[l] >= 1 && levels->W[l] >= 1 && (long)levels->H[l] * levels->W[l] < (1L << 30), "cosy_msroi_align: level %d is %d x %d cells", l,
-                     levels->H[l], levels->W[l]);
-        COSY_REQUIRE(levels->scale[l] > 0.f, "cosy_msroi_align: scale of level %d is %g", l, (double)levels->scale[l]);
-        COSY_REQUIRE(R == 0 || levels->feat[l] != nullptr, "cosy_msroi_align: null features of level %d", l);
-    }
+    if (int rc = msroi_args("cosy_msroi_align", levels, L, B, C, im_id, counts, rows_per_image, R, P, sampling_ratio, k_min, k_max)) return rc;
+    for (int l = 0; l < L; ++l) COSY_REQUIRE(R == 0 || levels->feat[l] != nullptr, "cosy_msroi_align: null features of level %d", l);
     if (R == 0) return COSY_OK;
     COSY_REQUIRE_PTR("cosy_msroi_align", boxes); COSY_REQUIRE_PTR("cosy_msroi_align", out);
     int cg = 1;                                                    // channels per workgroup: the largest power of two with cg P^2 <= 4096
@@ -403,6 +572,42 @@ int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, con
     COSY_REQUIRE(cdiv(C, cg) <= COSY_MAX_GRID_Y, "cosy_msroi_align: C=%d needs more than %d channel groups", C, COSY_MAX_GRID_Y);
     hipLaunchKernelGGL(msroi_align_kernel, dim3(R, cdiv(C, cg)), dim3(PRE_THREADS), 0, s, *levels, L, B, C, boxes, im_id, counts, rows_per_image, P,
                        sampling_ratio, cg, k_min, k_max, out, levels_out);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int cosy_msroi_align_backward(const cosy_msroi_levels_t* levels, float* const* grad_feat, int L, int B, int C, const float* grad_out,
+                              const float* boxes, const int* im_id, const int* counts, int rows_per_image, int R, int P, int sampling_ratio,
+                              int k_min, int k_max, int* row_ws, cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = msroi_args("cosy_msroi_align_backward", levels, L, B, C, im_id, counts, rows_per_image, R, P, sampling_ratio, k_min, k_max)) return rc;
+    COSY_REQUIRE_PTR("cosy_msroi_align_backward", grad_feat);
+    COSY_REQUIRE(R <= (1 << 30), "cosy_msroi_align_backward: R=%d rows exceed 2^30", R);
+    COSY_REQUIRE(cdiv(C, BWD_CG) <= COSY_MAX_GRID_Y, "cosy_msroi_align_backward: C=%d needs more than %d channel groups", C, COSY_MAX_GRID_Y);
+    BwdPlan plan;
+    long blocks = 0;
+    for (int l = 0; l < COSY_RPN_MAX_LEVELS; ++l) {
+        plan.grad[l] = l < L ? grad_feat[l] : nullptr;
+        plan.first[l] = (int)blocks;
+        plan.tiles_x[l] = plan.tiles[l] = 1;
+        if (!plan.grad[l]) continue;                               // a level whose gradient nobody needs
+        plan.tiles_x[l] = cdiv(levels->W[l], BWD_TILE);
+        plan.tiles[l] = plan.tiles_x[l] * cdiv(levels->H[l], BWD_TILE);
+        blocks += (long)B * plan.tiles[l];
+        COSY_REQUIRE(blocks <= 0x7fffffffL, "cosy_msroi_align_backward: B=%d images of levels 0 .. %d need more than 2^31 - 1 tiles", B, l);
+    }
+    plan.first[COSY_RPN_MAX_LEVELS] = (int)blocks;
+    if (blocks == 0) return COSY_OK;
+    if (R > 0) {
+        COSY_REQUIRE_PTR("cosy_msroi_align_backward", grad_out); COSY_REQUIRE_PTR("cosy_msroi_align_backward", boxes);
+        COSY_REQUIRE_PTR("cosy_msroi_align_backward", row_ws);
+        hipLaunchKernelGGL(msroi_rows_kernel, dim3(cdiv(R, PRE_THREADS)), dim3(PRE_THREADS), 0, s, *levels, L, B, boxes, im_id, counts, rows_per_image, R,
+                           P, sampling_ratio, k_min, k_max, row_ws);
+        COSY_CHECK_HIP(hipGetLastError());
+    }
+    // without a row every requested cell still gets its +0
+    hipLaunchKernelGGL(msroi_align_backward_kernel, dim3((unsigned)blocks, cdiv(C, BWD_CG)), dim3(PRE_THREADS), 0, s, *levels, plan, L, B, C, grad_out,
+                       boxes, row_ws, im_id ? 0 : rows_per_image, R, P, sampling_ratio);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }

@@ -6,7 +6,8 @@ section 22 states the contract; HIP: csrc/kernels_detpre.hip; the NMS is detecto
 What runs where
   * device, our kernels: the per-level top-k of the objectness logits (cosy_rpn_select), anchors + decode + clip + small-box test into
     per-image candidate arenas (cosy_rpn_decode), the suppression matrix and the greedy walk (cosy_nms_mask, cosy_nms_scan), the kept rows
-    (cosy_rpn_gather), level mapper + RoIAlign of all boxes of all images and levels in one launch (cosy_msroi_align);
+    (cosy_rpn_gather), level mapper + RoIAlign of all boxes of all images and levels in one launch (cosy_msroi_align), and its backward
+    into the feature maps as a gather without floating-point atomics (cosy_msroi_align_backward, DESIGN.md section 24);
   * device, torch as plumbing: ONE sort of the candidates' 64-bit keys;
   * host: the base anchors, strides and scales of at most 8 levels (a few dozen numbers).  No device-to-host copy, except the counts for
     rpn_proposals(as_list=True).
@@ -248,7 +249,8 @@ def multiscale_roi_align(features, boxes, net_sizes, output_size, sampling_ratio
       the list form of boxes.
     scales: spatial scale of every level; None: inferred from net_sizes as torchvision does.  Level = clamp(floor(4 + log2(sqrt(area) / 224
     + 1e-6)), k_min, k_max) - k_min with k = -log2(scale) of the first and last level, rounded to an integer.
-    -> (R,C,P,P) float32[, levels (R) int32] on the device, P = output_size."""
+    -> (R,C,P,P) float32[, levels (R) int32] on the device, P = output_size.  With autograd enabled and a feature map that requires grad the
+    result carries a backward into those feature maps (none into the boxes); otherwise the code path is the plain launch."""
     features = _levels(features, 'features')
     L = len(features)
     if not torch.is_tensor(features[0]) or features[0].dim() != 4:
@@ -298,17 +300,76 @@ def multiscale_roi_align(features, boxes, net_sizes, output_size, sampling_ratio
     dev = features[0].device
     if parts is not None:
         boxes = torch.cat(parts) if parts else torch.empty((0, 4), dtype=torch.float32, device=dev)
-    out = torch.empty((R, C, P, P), dtype=torch.float32, device=dev)
-    levels = torch.empty(R, dtype=torch.int32, device=dev) if return_levels else None
-    if R:
-        if im_id is None and rows is None:
-            im_id = _lib.ints_to_device(np.repeat(np.arange(B), counts), dev)
-        lv = _lib.MsroiLevels()
-        for l, f in enumerate(features):
-            lv.feat[l], lv.H[l], lv.W[l], lv.scale[l] = f.data_ptr(), f.shape[2], f.shape[3], scales[l]
-        _lib.check(_lib.lib().cosy_msroi_align(ctypes.byref(lv), L, B, C, _lib.ptr(boxes), _lib.ptr(im_id), _lib.ptr(dev_counts), rows or 0, R, P, g,
-                                               k_min, k_max, _lib.ptr(out), _lib.ptr(levels), _lib.stream()))
+    if R and im_id is None and rows is None:
+        im_id = _lib.ints_to_device(np.repeat(np.arange(B), counts), dev)
+    call = dict(L=L, B=B, C=C, R=R, P=P, g=g, k_min=k_min, k_max=k_max, rows=rows or 0, scales=scales, boxes=boxes, im_id=im_id, counts=dev_counts,
+                return_levels=return_levels)
+    if torch.is_grad_enabled() and any(f.requires_grad for f in features):
+        out, levels = _MsroiAlignFn.apply(call, *features)          # the same launch, with a backward into the feature maps
+    else:
+        out, levels = _msroi_forward(call, features)
     return (out, levels) if return_levels else out
+
+
+def _msroi_table(call, maps):
+    lv = _lib.MsroiLevels()
+    for l, (H, W) in enumerate(maps):
+        lv.H[l], lv.W[l], lv.scale[l] = H, W, call['scales'][l]
+    return lv
+
+
+def _msroi_forward(call, features):
+    R, C, P = call['R'], call['C'], call['P']
+    dev = features[0].device
+    out = torch.empty((R, C, P, P), dtype=torch.float32, device=dev)
+    levels = torch.empty(R, dtype=torch.int32, device=dev) if call['return_levels'] else None
+    if R:
+        lv = _msroi_table(call, [f.shape[2:] for f in features])
+        for l, f in enumerate(features):
+            lv.feat[l] = f.data_ptr()
+        _lib.check(_lib.lib().cosy_msroi_align(ctypes.byref(lv), call['L'], call['B'], C, _lib.ptr(call['boxes']), _lib.ptr(call['im_id']),
+                                               _lib.ptr(call['counts']), call['rows'], R, P, call['g'], call['k_min'], call['k_max'], _lib.ptr(out),
+                                               _lib.ptr(levels), _lib.stream()))
+    return out, levels
+
+
+class _MsroiAlignFn(torch.autograd.Function):
+    """multiscale_roi_align with a gradient for the feature maps (cosy_msroi_align_backward); none for the boxes"""
+
+    @staticmethod
+    def forward(ctx, call, *features):
+        out, levels = _msroi_forward(call, [f.detach() for f in features])
+        ctx.call, ctx.maps = call, [tuple(int(v) for v in f.shape[2:]) for f in features]
+        if levels is not None:
+            ctx.mark_non_differentiable(levels)
+        return out, levels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_levels=None):
+        call, L = ctx.call, ctx.call['L']
+        grad_out = grad_out.to(torch.float32).contiguous()
+        dev = grad_out.device
+        grads = [torch.empty((call['B'], call['C'], H, W), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1 + l] else None
+                 for l, (H, W) in enumerate(ctx.maps)]
+        ptrs = (ctypes.c_void_p * _lib.RPN_MAX_LEVELS)(*[_lib.ptr(t) for t in grads])
+        ws = torch.empty(8 * call['R'], dtype=torch.int32, device=dev)
+        lv = _msroi_table(call, ctx.maps)
+        _lib.check(_lib.lib().cosy_msroi_align_backward(ctypes.byref(lv), ptrs, L, call['B'], call['C'], _lib.ptr(grad_out), _lib.ptr(call['boxes']),
+                                                        _lib.ptr(call['im_id']), _lib.ptr(call['counts']), call['rows'], call['R'], call['P'],
+                                                        call['g'], call['k_min'], call['k_max'], _lib.ptr(ws), _lib.stream()))
+        return (None, *grads)
+
+
+def roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=2):
+    """torchvision.ops.roi_align (0.4.2: no `aligned`) of one feature map: input (B,C,H,W) float32, contiguous, on the device; boxes (K,5)
+    float32 with the image index in column 0, or a list of (K_i,4), one per image.  multiscale_roi_align with one level, so differentiable
+    with respect to input; sampling_ratio <= 0 (the adaptive grid) is refused.  -> (K,C,P,P), P = output_size."""
+    if torch.is_tensor(boxes):
+        boxes = detector._tensor(boxes, 'boxes', (None, 5))
+        return multiscale_roi_align([input], boxes[:, 1:].contiguous(), None, output_size, sampling_ratio, batch_im_id=boxes[:, 0].to(torch.int32),
+                                    scales=[spatial_scale])
+    return multiscale_roi_align([input], boxes, None, output_size, sampling_ratio, scales=[spatial_scale])
 
 
 # ---- features -> detections ----------------------------------------------------------------------------------------------------------

@@ -469,8 +469,9 @@ def detector_losses(features, rpn_head, box_head, mask_head, targets, net_sizes,
     'rpn' (B, anchors per image) and 'roi' (B, post_nms_top_n + max G) int32 keys for the two samplers.  Chains rpn_loss, rpn_proposals on the
     DETACHED RPN outputs with torchvision's training values (2000 / 2000), roi_training_samples, multiscale_roi_align(7) + box_head +
     fastrcnn_loss, multiscale_roi_align(14) of the positives + mask_head + maskrcnn_loss.
-    -> the reference's loss_dict: loss_objectness, loss_rpn_box_reg, loss_classifier, loss_box_reg, loss_mask (scalars with autograd history up
-    to the heads' parameters).  The heads see padded rows: B x 512 for the box head, B x 128 for the mask head."""
+    -> the reference's loss_dict: loss_objectness, loss_rpn_box_reg, loss_classifier, loss_box_reg, loss_mask: scalars with autograd history
+    through the heads and, for feature maps that require grad, through both RoIAligns into the feature maps (cosy_msroi_align_backward), as
+    torchvision's Mask R-CNN has it; the proposals carry no gradient.  The heads see padded rows: B x 512 for the box head, B x 128 for the mask head."""
     features = detector_rpn._levels(features, 'features')
     keys = keys or {}
     objectness, deltas = rpn_head(features)
@@ -479,7 +480,7 @@ def detector_losses(features, rpn_head, box_head, mask_head, targets, net_sizes,
     proposals, counts, _ = detector_rpn.rpn_proposals([o.detach() for o in objectness], [d.detach() for d in deltas], net_sizes, padded_size, sizes,
                                                       aspect_ratios, pre_nms_top_n, post_nms_top_n, rpn_nms_thresh, min_size)
     smp = roi_training_samples(proposals, counts, targets, keys.get('roi'), generator)
-    roi_maps = [f.detach() for f in features[:int(n_roi_levels)]]
+    roi_maps = features[:int(n_roi_levels)]                             # not detached: RoIAlign has a backward into them
     class_logits, box_regression = box_head(detector_rpn.multiscale_roi_align(roi_maps, smp['boxes'], net_sizes, box_output_size, sampling_ratio,
                                                                               counts=smp['counts']))
     loss_classifier, loss_box_reg = fastrcnn_loss(class_logits, box_regression, smp['labels'], smp['regression_targets'])

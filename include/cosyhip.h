@@ -877,6 +877,17 @@ typedef struct cosy_msroi_levels {
 int cosy_msroi_align(const cosy_msroi_levels_t* levels, int L, int B, int C, const float* boxes, const int* im_id, const int* counts,
                      int rows_per_image, int R, int P, int sampling_ratio, int k_min, int k_max, float* out, int* levels_out,
                      cosy_stream_t stream);
+/* The adjoint of cosy_msroi_align with respect to the feature maps: grad_out (R,C,P,P) float32 -> grad_feat[l] (B,C,H[l],W[l]) float32 for
+ * every level l < L whose pointer in the HOST array grad_feat is not null (a null level is skipped; levels->feat is not read).  boxes, im_id,
+ * counts, rows_per_image, P, sampling_ratio, k_min, k_max as in the forward call: the same level, the same taps and weights, the same 1/g^2;
+ * a row the forward writes as zeros adds nothing.  A gather: every cell of every requested level is written exactly once with a plain store
+ * (+0 where nothing arrives: no memset needed), no floating-point atomic, equal bits on every call.  Per cell the terms fl(fl(wy wx) g) are
+ * added in float32 by ascending row; inside a row by ascending y tap (of one tap the low cell's weight first), inside that by ascending x tap
+ * (low first); the sum is divided by g^2 once.  row_ws: 8 R int32 of scratch.  Two launches.  Limits: the forward's,
+ * R <= 2^30, C <= 32 x 65535, and B x (the 16 x 16 tiles of the requested levels) < 2^31. */
+int cosy_msroi_align_backward(const cosy_msroi_levels_t* levels, float* const* grad_feat, int L, int B, int C, const float* grad_out,
+                              const float* boxes, const int* im_id, const int* counts, int rows_per_image, int R, int P, int sampling_ratio,
+                              int k_min, int k_max, int* row_ws, cosy_stream_t stream);
 
 /* ---- Training side of the detector: the heads' raw outputs + targets -> Mask R-CNN's five losses and their gradients (torchvision 0.4.2's
  * Matcher, BalancedPositiveNegativeSampler, BoxCoder.encode, RPN compute_loss, select_training_samples, fastrcnn_loss, maskrcnn_loss) ----
