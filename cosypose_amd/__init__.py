@@ -77,6 +77,12 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
                 'maskrcnn_loss', 'detector_losses', 'AnchorGrid'):
         from . import detector_train
         return getattr(detector_train, name)
+    if name == 'detector_input':  # the function and its module share the name, as model_info: the module is callable
+        import importlib
+        return importlib.import_module('.detector_input', __name__)
+    if name in ('detections_from_frames', 'detector_losses_from_frames', 'DetectorInput'):
+        from . import detector_input
+        return getattr(detector_input, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

@@ -150,6 +150,7 @@ _SIGNATURES = {
     'cosy_resize_workspace_bytes': ([_I, _I, _I, _I], _SZ),
     'cosy_resize_u8': ([_P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _SZ, _P], _I),
     'cosy_resize_frames_u8': ([_P, _I, _I, _I, _P, _L, _I, _P, _P, _P], _I),
+    'cosy_detector_input': ([_P, _P, _I, _I, _I, _P, _L, _I, _I, _I, _P, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libcosyhip.so')
-SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
+SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
            'kernels_dw.hip', 'kernels_wave.hip', 'kernels_stem.hip', 'kernels_smx.hip', 'effnet.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # No packed-fp32 arithmetic (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) anywhere in the library.  Round 4: a wave's packed-fp32 results were WRONG while
@@ -37,7 +37,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-u
 # kernels_dettrain.hip: the same for the matcher's IoU, the encode, the loss terms and the mask targets, which hold the CPU twin's bits: DESIGN section 23.
 # kernels_resize.hip: the same for its HOST routine, which computes Pillow's resampling coefficients in double (its kernels are integer only).
 # kernels_frames.hip: its kernel writes the fused operations of DESIGN section 18 as fmaf and must round every other product on its own.
-FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['-ffp-contract=off'], 'kernels_frames.hip': ['-ffp-contract=off'],'kernels_bop.hip': ['-ffp-contract=off'], 'kernels_gt.hip': ['-ffp-contract=off'], 'kernels_models.hip': ['-ffp-contract=off'], 'kernels_det.hip': ['-ffp-contract=off'], 'kernels_detpost.hip': ['-ffp-contract=off'], 'kernels_detpre.hip': ['-ffp-contract=off'], 'kernels_dettrain.hip': ['-ffp-contract=off'], 'kernels_wave.hip': ['-fno-slp-vectorize'], 'kernels_dw.hip': ['-fno-slp-vectorize'], 'kernels_stem.hip': ['-fno-slp-vectorize'], 'kernels_smx.hip': ['-fno-slp-vectorize']}   # kernels_dw.hip: see its header
+# kernels_detin.hip: the same for the fused operations of DESIGN section 25 and the one product of a box coordinate.
+FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['-ffp-contract=off'], 'kernels_frames.hip': ['-ffp-contract=off'], 'kernels_detin.hip': ['-ffp-contract=off'], 'kernels_bop.hip': ['-ffp-contract=off'], 'kernels_gt.hip': ['-ffp-contract=off'], 'kernels_models.hip': ['-ffp-contract=off'], 'kernels_det.hip': ['-ffp-contract=off'], 'kernels_detpost.hip': ['-ffp-contract=off'], 'kernels_detpre.hip': ['-ffp-contract=off'], 'kernels_dettrain.hip': ['-ffp-contract=off'], 'kernels_wave.hip': ['-fno-slp-vectorize'], 'kernels_dw.hip': ['-fno-slp-vectorize'], 'kernels_stem.hip': ['-fno-slp-vectorize'], 'kernels_smx.hip': ['-fno-slp-vectorize']}   # kernels_dw.hip: see its header
 
 
 def _headers():

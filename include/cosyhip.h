@@ -947,6 +947,51 @@ int cosy_dt_mask_loss(const long long* mask_ptr, const int* mask_dims, int B, co
                       const int* pos_count, int rows_per_image, const float* mask_logits, int C, int M, double* partial_ws, float* grad, float* targets_out,
                       float* loss, cosy_stream_t stream);
 
+/* ---- Input side of the detector: torchvision 0.4.2's GeneralizedRCNNTransform (normalise, resize, pad into one batch; boxes and masks
+ * of the targets to the network's size) for uint8 frames ----
+ * DESIGN.md section 25 holds the arithmetic: float32, one rounding per operation.  Everything that divides is computed by the CALLER and
+ * handed over in `tables` (n_tables int32 of DEVICE memory, 16-byte aligned): at offset `lut` the bits of the 3 x 256 floats
+ * p_c(u) = ((float32(u) / 255f) - mean_c) / std_c, channel-major; for an axis n_in -> n_out a tap table (n_out,4) = i0, i1, bits of l0,
+ * bits of l1 (offset a multiple of 4 ints) and a nearest table (n_out) = source index, as cosy_resize_frames_u8 reads them; and at offset
+ * `units` n_units pairs (item, mask plane), one per mask plane of the call.
+ *
+ * cosy_detector_input: n frames of any sizes in ONE launch.  Frame i is read in place: byte (c, y, x) lies at frame + c sc + y sy + x sx
+ * (strides in bytes, >= 0; CHW, HWC and views of them alike).  out_images (n,3,Hp,Wp) float32: EVERY element is written exactly once;
+ * inside (nh_i, nw_i) of image i
+ *   top = fma(lx0, p00, lx1 * p01), bot = fma(lx0, p10, lx1 * p11), v = fma(ly0, top, ly1 * bot)      (xb / yb: the tap tables)
+ * with every product rounded once, and outside it +0.0.  An item with COSY_DETIN_ONE_TAP set and nh == h, nw == w stores p00 and its tap
+ * offsets are not read: the same bits where no table entry is -0.0, infinite or NaN, which is the caller's to know.  Where n_masks > 0,
+ * masks (n_masks,h,w) uint8 contiguous go through nearest (xn / yn: the nearest tables) to masks_out (n_masks,nh,nw) uint8 contiguous, not
+ * padded.  Where n_boxes > 0, boxes (n_boxes,4) float32 xyxy go to boxes_out as x * rw, y * rh, one product each.  Equal inputs give
+ * equal bits.  out_images must be 4-byte aligned; rows that are 16-byte aligned are stored as 16-byte vectors.
+ * Checked on the host before the launch (COSY_EINVAL, cosy_last_error() names the argument): 0 <= n, n_units >= 0, n + n_units <= 65535,
+ * 1 <= Hp <= 524280, Wp >= 1, 3 Hp Wp < 2^31, lut + 768 <= n_tables, units + 2 n_units <= n_tables, non-null items_host / items / tables /
+ * out_images and their alignment, and EVERY item of items_host -- the caller's host copy of the descriptors: a null frame, a size < 1,
+ * nh > Hp or nw > Wp, a negative stride or count, a table offset outside [0, n_tables) or misaligned, or a null pointer beside a count > 0
+ * refuses the whole call and nothing is written.  n = 0 returns COSY_OK at once.  The kernel reads the DEVICE copy `items` and applies
+ * the same test again: an item that fails it there leaves its outputs UNTOUCHED and nothing is read through it; a unit whose item or plane
+ * does not exist is skipped; a tap or nearest index outside its line is clamped into it.
+ * Why two copies: the descriptors must be in device memory for the kernel, and the caller has just written them on the host to upload
+ * them, so handing over that host copy lets a bad item refuse the call BEFORE anything is written, without a device-to-host copy or a
+ * synchronisation.  Nothing is trusted because of it: the host test decides only the return value, and the kernel's own test of the bytes
+ * it actually reads is what keeps an item that differs between the copies from reading or writing outside its buffers. */
+enum { COSY_DETIN_ONE_TAP = 1 };
+typedef struct cosy_detin_item {
+    const unsigned char* frame;
+    long long sc, sy, sx;           /* byte strides of channel, row, pixel */
+    const unsigned char* masks;
+    unsigned char* masks_out;
+    const float* boxes;
+    float* boxes_out;
+    int h, w, nh, nw;
+    int xb, yb, xn, yn;
+    int n_masks, n_boxes;
+    float rw, rh;
+    int flags, reserved[3];         /* 128 bytes per item */
+} cosy_detin_item_t;
+int cosy_detector_input(const cosy_detin_item_t* items_host, const cosy_detin_item_t* items, int n, int Hp, int Wp, const int* tables,
+                        long n_tables, int lut, int units, int n_units, float* out_images, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
