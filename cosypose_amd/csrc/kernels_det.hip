@@ -158,7 +158,7 @@ __device__ __forceinline__ Box load_box(const float* __restrict__ p, long n) {
         const float4 v = reinterpret_cast<const float4*>(p)[n];
         return {v.x, v.y, v.z, v.w};
     }
-    return {p[4 * n], p[4 * n + 1], p[4 * n + 2], p[4 * n + 3]};
+    return cosy::load_box(p, (size_t)n);                           // the scalar form of det_device.h
 }
 
 template <bool ALIGNED>

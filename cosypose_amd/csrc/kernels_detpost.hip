@@ -4,9 +4,9 @@
 // the torch-CPU twin.
 //
 //   detpost_init_kernel      keys <- "empty slot of image b" (sorts behind every candidate of b), counts <- 0, max coordinate <- 0
-//   det_decode_kernel        ONE thread per proposal: softmax over the C logits, then per foreground class decode, clip, score threshold
-//                            and small-box test; a survivor takes a slot of its image's arena through a wave-aggregated integer atomic
-//                            and leaves box, score, label, source index and its 64-bit sort key
+//   det_decode_kernel        ONE thread per proposal: softmax over the C logits, then per foreground class decode and clip (det_device.h's
+//                            box_decode, the RPN side's too), score threshold and small-box test; a survivor takes a slot of its image's
+//                            arena through a wave-aggregated integer atomic and leaves box, score, label, source index and its 64-bit sort key
 //                            (image << 52 | (0x7fffffff - score bits) << 21 | candidate index): sorting the keys ascending gives image,
 //                            then descending score, then ascending candidate index, whatever order the atomics handed the slots out in.
 //   nms_mask_kernel          one wave per 64 x 64 tile (column block >= row block) of an image's suppression matrix: lane l holds box
@@ -36,14 +36,9 @@ namespace {
 constexpr int DP_THREADS = 256;
 constexpr int NMS_MAX_CAP = 16384;                               // candidates per image (segment): 32 MiB of matrix per image at the cap
 constexpr int NMS_MAX_BLOCKS = NMS_MAX_CAP / 64;
-constexpr int DP_KEY_INDEX_BITS = 21;                            // candidate index = proposal * (C-1) + (label-1) < 2^21
-constexpr int DP_KEY_IMAGE_SHIFT = 52;                           // 31 bits of score above the index, the image above both
-constexpr int DP_MAX_IMAGES = 2047;
+constexpr int DP_KEY_INDEX_BITS = 21;                            // candidate index = proposal * (C-1) + (label-1) < 2^21; 31 bits of score above
 constexpr int PASTE_MAX_M = 62;                                  // (M+2)^2 floats of LDS: 16 KiB at the cap
 constexpr int PASTE_ITERS = 4;                                   // 16-byte stores per thread: 16384 pixels per workgroup
-constexpr float BBOX_XFORM_CLIP = 4.135166556742356f;            // log(1000 / 16)
-
-__device__ __forceinline__ long long empty_key(int b) { return ((long long)b << DP_KEY_IMAGE_SHIFT) | ((1LL << DP_KEY_IMAGE_SHIFT) - 1); }
 
 __global__ __launch_bounds__(DP_THREADS) void detpost_init_kernel(long long* __restrict__ keys, int* __restrict__ counts,
                                                                   unsigned* __restrict__ max_coord, int B, int cap) {
@@ -70,7 +65,8 @@ __global__ __launch_bounds__(DP_THREADS) void det_decode_kernel(const float* __r
         }
     }
     const bool valid = img >= 0;
-    float m = 0.f, sum = 1.f, net_h = 0.f, net_w = 0.f, w = 0.f, h = 0.f, cx = 0.f, cy = 0.f;
+    float m = 0.f, sum = 1.f, net_h = 0.f, net_w = 0.f;
+    Box p = {0.f, 0.f, 0.f, 0.f};
     const float* x = logits + (size_t)(valid ? r : 0) * C;
     if (valid) {
         m = x[0];
@@ -78,9 +74,7 @@ __global__ __launch_bounds__(DP_THREADS) void det_decode_kernel(const float* __r
         sum = 0.f;
         for (int j = 0; j < C; ++j) sum = __fadd_rn(sum, expf(__fsub_rn(x[j], m)));
         net_h = net_sizes[2 * img]; net_w = net_sizes[2 * img + 1];
-        const float4 p = make_float4(proposals[4 * (size_t)r], proposals[4 * (size_t)r + 1], proposals[4 * (size_t)r + 2], proposals[4 * (size_t)r + 3]);
-        w = __fsub_rn(p.z, p.x); h = __fsub_rn(p.w, p.y);
-        cx = __fadd_rn(p.x, __fmul_rn(0.5f, w)); cy = __fadd_rn(p.y, __fmul_rn(0.5f, h));
+        p = load_box(proposals, r);
     }
     for (int j = 1; j < C; ++j) {                                  // (uniform trip count: the ballots below need every lane)
         bool emit = false;
@@ -89,13 +83,8 @@ __global__ __launch_bounds__(DP_THREADS) void det_decode_kernel(const float* __r
         if (valid) {
             score = __fdiv_rn(expf(__fsub_rn(x[j], m)), sum);
             const float* d = reg + ((size_t)r * C + j) * 4;
-            const float dx = __fdiv_rn(d[0], 10.f), dy = __fdiv_rn(d[1], 10.f);
-            const float dw = min_nan(__fdiv_rn(d[2], 5.f), BBOX_XFORM_CLIP), dh = min_nan(__fdiv_rn(d[3], 5.f), BBOX_XFORM_CLIP);
-            const float pcx = __fadd_rn(__fmul_rn(dx, w), cx), pcy = __fadd_rn(__fmul_rn(dy, h), cy);
-            const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-            const float hw = __fmul_rn(0.5f, pw), hh = __fmul_rn(0.5f, ph);
-            o.x1 = min_nan(max_nan(__fsub_rn(pcx, hw), 0.f), net_w); o.y1 = min_nan(max_nan(__fsub_rn(pcy, hh), 0.f), net_h);
-            o.x2 = min_nan(max_nan(__fadd_rn(pcx, hw), 0.f), net_w); o.y2 = min_nan(max_nan(__fadd_rn(pcy, hh), 0.f), net_h);
+            const float dd[4] = {__fdiv_rn(d[0], 10.f), __fdiv_rn(d[1], 10.f), __fdiv_rn(d[2], 5.f), __fdiv_rn(d[3], 5.f)};   // weights (10, 10, 5, 5)
+            o = box_decode(p, dd, net_h, net_w);                   // (the proposal's centre and extent do not depend on j: computed once)
             emit = score > score_thresh && __fsub_rn(o.x2, o.x1) >= 1e-2f && __fsub_rn(o.y2, o.y1) >= 1e-2f;   // (NaN fails every test)
         }
         // one atomic per wave and image: the lanes of the leader's image take consecutive slots.  The loop runs once per image that has
@@ -114,10 +103,10 @@ __global__ __launch_bounds__(DP_THREADS) void det_decode_kernel(const float* __r
                 if (slot >= 0 && slot < cap) {                     // past the cap nothing is written; counts[] says so to the host
                     const size_t at = (size_t)img * cap + slot;
                     const int src = (r - first) * (C - 1) + (j - 1);
-                    cand_boxes[4 * at] = o.x1; cand_boxes[4 * at + 1] = o.y1; cand_boxes[4 * at + 2] = o.x2; cand_boxes[4 * at + 3] = o.y2;
+                    store_box(cand_boxes, at, o);
                     cand_scores[at] = score; cand_labels[at] = j; cand_src[at] = src;
                     const long long sbits = 0x7fffffffLL - (long long)(__float_as_uint(score) & 0x7fffffffu);
-                    cand_keys[at] = ((long long)img << DP_KEY_IMAGE_SHIFT) | (sbits << DP_KEY_INDEX_BITS) | (long long)src;
+                    cand_keys[at] = ((long long)img << ARENA_KEY_IMAGE_SHIFT) | (sbits << DP_KEY_INDEX_BITS) | (long long)src;
                     const unsigned big = __float_as_uint(o.x2 > o.y2 ? o.x2 : o.y2);   // clipped coordinates are >= +0: bits order as values
                     if (big > __hip_atomic_load(&max_coord[img], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&max_coord[img], big);
                 }
@@ -135,7 +124,7 @@ __device__ __forceinline__ Box nms_box(const float* __restrict__ boxes, const lo
     if (i >= n) return nan_box();
     const long long idx = order ? order[start + i] : (long long)(start + i);
     if (idx < 0 || idx >= N) return nan_box();
-    Box v = {boxes[4 * idx], boxes[4 * idx + 1], boxes[4 * idx + 2], boxes[4 * idx + 3]};
+    Box v = load_box(boxes, idx);
     if (labels) {
         const float off = __fmul_rn((float)labels[idx], shift_unit);
         v.x1 = __fadd_rn(v.x1, off); v.y1 = __fadd_rn(v.y1, off); v.x2 = __fadd_rn(v.x2, off); v.y2 = __fadd_rn(v.y2, off);
@@ -246,13 +235,12 @@ __global__ __launch_bounds__(DP_THREADS) void det_gather_kernel(const int* __res
     int label = -1, s = -1;
     unsigned sbits = 0u;
     if (ok) {
-        v = {cand_boxes[4 * idx], cand_boxes[4 * idx + 1], cand_boxes[4 * idx + 2], cand_boxes[4 * idx + 3]};
+        v = load_box(cand_boxes, idx);
         label = cand_labels[idx]; s = cand_src[idx]; sbits = __float_as_uint(cand_scores[idx]);
     }
     const float rw = ratios[2 * b], rh = ratios[2 * b + 1];
-    boxes_net[4 * at] = v.x1; boxes_net[4 * at + 1] = v.y1; boxes_net[4 * at + 2] = v.x2; boxes_net[4 * at + 3] = v.y2;
-    boxes_frame[4 * at] = __fmul_rn(v.x1, rw); boxes_frame[4 * at + 1] = __fmul_rn(v.y1, rh);
-    boxes_frame[4 * at + 2] = __fmul_rn(v.x2, rw); boxes_frame[4 * at + 3] = __fmul_rn(v.y2, rh);
+    store_box(boxes_net, at, v);
+    store_box(boxes_frame, at, {__fmul_rn(v.x1, rw), __fmul_rn(v.y1, rh), __fmul_rn(v.x2, rw), __fmul_rn(v.y2, rh)});
     src[at] = s;
     packed[2 * B + at] = label;
     packed[2 * B + rows + at] = (int)sbits;
@@ -290,10 +278,10 @@ __global__ __launch_bounds__(DP_THREADS) void paste_masks_kernel(const float* __
     const long chunk0 = (long)blockIdx.x * (DP_THREADS * PASTE_ITERS * V);
     const long chunk1 = chunk0 + DP_THREADS * PASTE_ITERS * V < plane ? chunk0 + DP_THREADS * PASTE_ITERS * V : plane;
     // the box, expanded by the padding's share and truncated toward zero (expand_boxes + .to(int64))
-    const float x1 = boxes[4 * (size_t)d], y1 = boxes[4 * (size_t)d + 1], x2 = boxes[4 * (size_t)d + 2], y2 = boxes[4 * (size_t)d + 3];
+    const Box roi = load_box(boxes, d);
     const float scale = __fdiv_rn((float)P, (float)M);
-    const float xc = __fmul_rn(__fadd_rn(x2, x1), 0.5f), yc = __fmul_rn(__fadd_rn(y2, y1), 0.5f);
-    const float wh = __fmul_rn(__fmul_rn(__fsub_rn(x2, x1), 0.5f), scale), hh = __fmul_rn(__fmul_rn(__fsub_rn(y2, y1), 0.5f), scale);
+    const float xc = __fmul_rn(__fadd_rn(roi.x2, roi.x1), 0.5f), yc = __fmul_rn(__fadd_rn(roi.y2, roi.y1), 0.5f);
+    const float wh = __fmul_rn(__fmul_rn(__fsub_rn(roi.x2, roi.x1), 0.5f), scale), hh = __fmul_rn(__fmul_rn(__fsub_rn(roi.y2, roi.y1), 0.5f), scale);
     const int bx1 = trunc_box(__fsub_rn(xc, wh)), by1 = trunc_box(__fsub_rn(yc, hh));
     const int bx2 = trunc_box(__fadd_rn(xc, wh)), by2 = trunc_box(__fadd_rn(yc, hh));
     const int bw = bx2 - bx1 + 1 > 1 ? bx2 - bx1 + 1 : 1, bh = by2 - by1 + 1 > 1 ? by2 - by1 + 1 : 1;
@@ -355,8 +343,8 @@ int cosy_det_decode(const float* class_logits, const float* box_regression, cons
     hipStream_t s = (hipStream_t)stream;
     COSY_REQUIRE(R >= 0 && B >= 0, "cosy_det_decode: R=%d B=%d", R, B);
     COSY_REQUIRE(C >= 2 && C <= 4096, "cosy_det_decode: C=%d outside [2, 4096] (background + at least one class)", C);
-    COSY_REQUIRE(B <= DP_MAX_IMAGES, "cosy_det_decode: B=%d exceeds %d images per call", B, DP_MAX_IMAGES);
-    COSY_REQUIRE(cap >= 64 && cap <= NMS_MAX_CAP && cap % 64 == 0, "cosy_det_decode: cap=%d is no multiple of 64 in [64, %d]", cap, NMS_MAX_CAP);
+    COSY_REQUIRE(B <= ARENA_MAX_IMAGES, "cosy_det_decode: B=%d exceeds %d images per call", B, ARENA_MAX_IMAGES);
+    if (int rc = arena_cap_args("cosy_det_decode", cap)) return rc;
     COSY_REQUIRE((long)R * (C - 1) <= (1L << DP_KEY_INDEX_BITS), "cosy_det_decode: R (C-1) = %ld exceeds 2^%d candidates per call", (long)R * (C - 1), DP_KEY_INDEX_BITS);
     COSY_REQUIRE(score_thresh >= 0.f, "cosy_det_decode: score_thresh=%g is negative or NaN", (double)score_thresh);
     if (B == 0) return COSY_OK;
@@ -379,7 +367,7 @@ int cosy_det_decode(const float* class_logits, const float* box_regression, cons
 static int nms_args(const char* fn, int B, int N, int cap, const void* seg_start, const void* seg_count) {
     COSY_REQUIRE(B >= 0 && N >= 0, "%s: B=%d N=%d", fn, B, N);
     COSY_REQUIRE(B <= COSY_MAX_GRID_Y, "%s: B=%d exceeds %d segments per call", fn, B, COSY_MAX_GRID_Y);
-    COSY_REQUIRE(cap >= 64 && cap <= NMS_MAX_CAP && cap % 64 == 0, "%s: cap=%d is no multiple of 64 in [64, %d]", fn, cap, NMS_MAX_CAP);
+    if (int rc = arena_cap_args(fn, cap)) return rc;
     COSY_REQUIRE(B == 0 || (seg_start != nullptr && seg_count != nullptr), "%s: null seg_start / seg_count", fn);
     return COSY_OK;
 }
@@ -418,8 +406,8 @@ int cosy_det_gather(const int* kept, const int* n_kept, const int* counts, const
                     const int* cand_labels, const int* cand_src, const float* ratios, int B, int cap, int max_keep, float* boxes_net,
                     float* boxes_frame, int* src, int* packed, cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    COSY_REQUIRE(B >= 0 && B <= DP_MAX_IMAGES && max_keep >= 0, "cosy_det_gather: B=%d max_keep=%d", B, max_keep);
-    COSY_REQUIRE(cap >= 64 && cap <= NMS_MAX_CAP, "cosy_det_gather: cap=%d outside [64, %d]", cap, NMS_MAX_CAP);
+    COSY_REQUIRE(B >= 0 && B <= ARENA_MAX_IMAGES && max_keep >= 0, "cosy_det_gather: B=%d max_keep=%d", B, max_keep);
+    if (int rc = arena_cap_args("cosy_det_gather", cap, false)) return rc;
     COSY_REQUIRE((long)B * max_keep < (1L << 30), "cosy_det_gather: %d x %d rows are too many", B, max_keep);
     if (B == 0) return COSY_OK;
     COSY_REQUIRE_PTR("cosy_det_gather", n_kept); COSY_REQUIRE_PTR("cosy_det_gather", counts); COSY_REQUIRE_PTR("cosy_det_gather", packed);

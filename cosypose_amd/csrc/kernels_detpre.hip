@@ -7,8 +7,8 @@
 //                            compaction: the workgroup walks the level in chunks of 1024 anchors in index order and writes every anchor
 //                            strictly above the threshold key, then the lowest-index ties at it.  An anchor whose logit or any delta is NaN
 //                            is absent: never counted, never selected.  -0 counts as +0.
-//   rpn_decode_kernel        ONE thread per arena slot (image, level, rank): the anchor from its index, BoxCoder.decode with weights 1 and the
-//                            log(1000/16) clamp, clip to the image's own size, the small-box test; a survivor leaves box, score, level,
+//   rpn_decode_kernel        ONE thread per arena slot (image, level, rank): the anchor from its index (anchor_box), BoxCoder.decode with weights 1,
+//                            the log(1000/16) clamp and the clip to the image's own size (box_decode, both in det_device.h), the small-box test; a survivor leaves box, score, level,
 //                            candidate index and the sort key  image << 52 | (0xffffffff - ordered score) << 20 | candidate index;  every
 //                            other slot leaves the "empty slot of image b" key, which sorts behind all of b's candidates.
 //   rpn_gather_kernel        the kept rows of cosy_nms_scan into (B, max_keep) padded proposals, scores, levels, candidate indices, counts
@@ -31,16 +31,10 @@ namespace {
 constexpr int SEL_THREADS = 1024;
 constexpr int SEL_WAVES = SEL_THREADS / 64;
 constexpr int PRE_THREADS = 256;
-constexpr int RPN_KEY_INDEX_BITS = 20;                           // candidate index = level offset + anchor index < 2^20
-constexpr int RPN_KEY_IMAGE_SHIFT = 52;                          // 32 bits of ordered score above the index, the image above both
-constexpr int RPN_MAX_IMAGES = 2047;
-constexpr float BBOX_XFORM_CLIP = 4.135166556742356f;            // log(1000 / 16)
+constexpr int RPN_KEY_INDEX_BITS = 20;                           // candidate index = level offset + anchor index < 2^20; 32 bits of score above
 constexpr int MS_MAX_TAPS = 128;                                 // P g per axis
 
-typedef cosy_rpn_levels_t RpnLevels;
 typedef cosy_msroi_levels_t MsLevels;
-
-__device__ __forceinline__ long long empty_key(int b) { return ((long long)b << RPN_KEY_IMAGE_SHIFT) | ((1LL << RPN_KEY_IMAGE_SHIFT) - 1); }
 
 // larger float <=> larger key: all bits of a negative value flipped, the sign bit of any other; -0 is +0 first
 __device__ __forceinline__ unsigned ordered_key(float v) {
@@ -174,25 +168,13 @@ __global__ __launch_bounds__(PRE_THREADS) void rpn_decode_kernel(RpnLevels lv, i
     if (l < L) {
         int cnt = sel_count[b * L + l];
         cnt = cnt < pre ? cnt : pre;
-        const int H = lv.H[l], W = lv.W[l], HW = H * W;
+        const int HW = lv.H[l] * lv.W[l];
         const int idx = j < cnt ? sel_idx[((size_t)b * L + l) * pre + j] : -1;
         if (idx >= 0 && idx < A * HW) {                            // an index read from memory: checked before it addresses anything
             float d[4];
             const float v = rpn_logit(lv.objectness[l] + (size_t)b * A * HW, A, HW, idx);
             const bool fin = rpn_deltas_finite(lv.deltas[l] + (size_t)b * 4 * A * HW, A, HW, idx, d);
-            const int pos = idx / A, a = idx - pos * A, y = pos / W, x = pos - y * W;
-            const float sx = __fmul_rn((float)x, lv.stride_w[l]), sy = __fmul_rn((float)y, lv.stride_h[l]);
-            const float ax1 = __fadd_rn(lv.base[l][a][0], sx), ay1 = __fadd_rn(lv.base[l][a][1], sy);
-            const float ax2 = __fadd_rn(lv.base[l][a][2], sx), ay2 = __fadd_rn(lv.base[l][a][3], sy);
-            const float w = __fsub_rn(ax2, ax1), h = __fsub_rn(ay2, ay1);
-            const float cx = __fadd_rn(ax1, __fmul_rn(0.5f, w)), cy = __fadd_rn(ay1, __fmul_rn(0.5f, h));
-            const float dw = min_nan(d[2], BBOX_XFORM_CLIP), dh = min_nan(d[3], BBOX_XFORM_CLIP);
-            const float pcx = __fadd_rn(__fmul_rn(d[0], w), cx), pcy = __fadd_rn(__fmul_rn(d[1], h), cy);
-            const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-            const float hw = __fmul_rn(0.5f, pw), hh = __fmul_rn(0.5f, ph);
-            const float net_h = net_sizes[2 * b], net_w = net_sizes[2 * b + 1];
-            o.x1 = min_nan(max_nan(__fsub_rn(pcx, hw), 0.f), net_w); o.y1 = min_nan(max_nan(__fsub_rn(pcy, hh), 0.f), net_h);
-            o.x2 = min_nan(max_nan(__fadd_rn(pcx, hw), 0.f), net_w); o.y2 = min_nan(max_nan(__fadd_rn(pcy, hh), 0.f), net_h);
+            o = box_decode(anchor_box(lv, l, idx, A), d, net_sizes[2 * b], net_sizes[2 * b + 1]);   // (weights 1: the deltas as they are)
             score = v == 0.f ? 0.f : v;
             int first = 0;
             for (int m = 0; m < l; ++m) first += A * lv.H[m] * lv.W[m];
@@ -202,9 +184,9 @@ __global__ __launch_bounds__(PRE_THREADS) void rpn_decode_kernel(RpnLevels lv, i
     }
     long long key = empty_key(b);
     if (emit) {
-        cand_boxes[4 * at] = o.x1; cand_boxes[4 * at + 1] = o.y1; cand_boxes[4 * at + 2] = o.x2; cand_boxes[4 * at + 3] = o.y2;
+        store_box(cand_boxes, at, o);
         cand_scores[at] = score; cand_level[at] = l; cand_src[at] = cand;
-        key = ((long long)b << RPN_KEY_IMAGE_SHIFT) | ((long long)(0xffffffffu - ordered_key(score)) << RPN_KEY_INDEX_BITS) | (long long)cand;
+        key = ((long long)b << ARENA_KEY_IMAGE_SHIFT) | ((long long)(0xffffffffu - ordered_key(score)) << RPN_KEY_INDEX_BITS) | (long long)cand;
         const unsigned big = __float_as_uint(o.x2 > o.y2 ? o.x2 : o.y2);       // clipped coordinates are >= +0: bits order as values
         if (big > __hip_atomic_load(&max_coord[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&max_coord[b], big);
     }
@@ -229,18 +211,18 @@ __global__ __launch_bounds__(PRE_THREADS) void rpn_gather_kernel(const int* __re
     float sc = 0.f;
     int lvl = -1, s = -1;
     if (ok) {
-        v = {cand_boxes[4 * idx], cand_boxes[4 * idx + 1], cand_boxes[4 * idx + 2], cand_boxes[4 * idx + 3]};
+        v = load_box(cand_boxes, idx);
         sc = cand_scores[idx]; lvl = cand_level[idx]; s = cand_src[idx];
     }
-    proposals[4 * at] = v.x1; proposals[4 * at + 1] = v.y1; proposals[4 * at + 2] = v.x2; proposals[4 * at + 3] = v.y2;
+    store_box(proposals, at, v);
     scores[at] = sc; levels[at] = lvl; src[at] = s;
 }
 
-// (Tap / msroi_tap, one tap line of roi_align along one axis, live in det_device.h: the mask targets of kernels_dettrain.hip use them too)
+// (Tap / msroi_tap, one tap line of roi_align along one axis, live in det_device.h, as do anchor_box, box_decode and the arena's key layout above)
 // The two pieces of a row that msroi_align_kernel and its adjoint must agree on to the bit: one definition each.
 // LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min; a NaN (negative area) takes k_min
-__device__ __forceinline__ int msroi_level(float x1, float y1, float x2, float y2, int k_min, int k_max) {
-    const float sz = sqrtf(__fmul_rn(__fsub_rn(x2, x1), __fsub_rn(y2, y1)));
+__device__ __forceinline__ int msroi_level(const Box& b, int k_min, int k_max) {
+    const float sz = sqrtf(__fmul_rn(__fsub_rn(b.x2, b.x1), __fsub_rn(b.y2, b.y1)));
     const float t = floorf(__fadd_rn(4.f, log2f(__fadd_rn(__fdiv_rn(sz, 224.f), 1e-6f))));
     const int lvl = !(t >= (float)k_min) ? k_min : t > (float)k_max ? k_max : (int)t;
     return lvl - k_min;
@@ -268,8 +250,8 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, i
     int img = im_id ? im_id[r] : r / rows_per_image;
     bool row = img >= 0 && img < B;
     if (row && counts) row = r - img * rows_per_image < counts[img];
-    const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
-    const int lvl = msroi_level(x1, y1, x2, y2, k_min, k_max);
+    const Box bx = load_box(boxes, r);
+    const int lvl = msroi_level(bx, k_min, k_max);
     if (lvl < 0 || lvl >= L) row = false;                          // (the entry point refuses k_max - k_min >= L: never taken)
     if (blockIdx.y == 0 && tid == 0 && levels_out) levels_out[r] = row ? lvl : -1;
     if (!row) {                                                    // a row no image owns: zeros
@@ -281,7 +263,7 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_kernel(MsLevels lv, i
     const int taps = P * g;
     for (int q = tid; q < 2 * taps; q += PRE_THREADS) {
         const int axis = q / taps, m = q - axis * taps;
-        const Tap tp = msroi_axis_tap(axis ? x1 : y1, axis ? x2 : y2, scale, P, g, m, axis ? W : H);
+        const Tap tp = msroi_axis_tap(axis ? bx.x1 : bx.y1, axis ? bx.x2 : bx.y2, scale, P, g, m, axis ? W : H);
         s_lo[axis][m] = tp.lo; s_hi[axis][m] = tp.hi; s_wl[axis][m] = tp.wl; s_wh[axis][m] = tp.wh;
     }
     __syncthreads();
@@ -335,15 +317,15 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_rows_kernel(MsLevels lv, in
     const int img = im_id ? im_id[r] : (int)(r / rows_per_image);
     bool row = img >= 0 && img < B;
     if (row && counts) row = r - (long)img * rows_per_image < counts[img];
-    const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
-    const int lvl = msroi_level(x1, y1, x2, y2, k_min, k_max);
+    const Box bx = load_box(boxes, r);
+    const int lvl = msroi_level(bx, k_min, k_max);
     if (lvl < 0 || lvl >= L) row = false;
     int lo[2] = {0x7fffffff, 0x7fffffff}, hi[2] = {-1, -1};
     if (row) {
         const float scale = lv.scale[lvl];
         for (int axis = 0; axis < 2; ++axis)
             for (int m = 0; m < P * g; ++m) {
-                const Tap t = msroi_axis_tap(axis ? x1 : y1, axis ? x2 : y2, scale, P, g, m, axis ? lv.W[lvl] : lv.H[lvl]);
+                const Tap t = msroi_axis_tap(axis ? bx.x1 : bx.y1, axis ? bx.x2 : bx.y2, scale, P, g, m, axis ? lv.W[lvl] : lv.H[lvl]);
                 if (t.lo < 0) continue;
                 lo[axis] = t.lo < lo[axis] ? t.lo : lo[axis];
                 hi[axis] = t.hi > hi[axis] ? t.hi : hi[axis];
@@ -460,20 +442,14 @@ __global__ __launch_bounds__(PRE_THREADS) void msroi_align_backward_kernel(MsLev
 }
 
 int rpn_level_args(const char* fn,const cosy_rpn_levels_t* lv, int L, int A, int B, int pre) {
-    COSY_REQUIRE(lv != nullptr, "%s: null levels", fn);
-    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "%s: L=%d outside [1, %d] levels", fn, L, COSY_RPN_MAX_LEVELS);
-    COSY_REQUIRE(A >= 1 && A <= COSY_RPN_MAX_ANCHORS, "%s: A=%d outside [1, %d] anchors per cell", fn, A, COSY_RPN_MAX_ANCHORS);
-    COSY_REQUIRE(B >= 0 && B <= RPN_MAX_IMAGES, "%s: B=%d outside [0, %d] images per call", fn, B, RPN_MAX_IMAGES);
+    long total;
+    if (int rc = rpn_levels_args(fn, lv, L, A, &total)) return rc;
+    COSY_REQUIRE(B >= 0 && B <= ARENA_MAX_IMAGES, "%s: B=%d outside [0, %d] images per call", fn, B, ARENA_MAX_IMAGES);
     COSY_REQUIRE(pre >= 1, "%s: pre_nms_top_n=%d", fn, pre);
     COSY_REQUIRE((long)pre * L <= (long)cosy_nms_max_candidates(), "%s: pre_nms_top_n L = %ld exceeds cosy_nms_max_candidates() = %d", fn, (long)pre * L,
                  cosy_nms_max_candidates());
-    long total = 0;
-    for (int l = 0; l < L; ++l) {
-        COSY_REQUIRE(lv->H[l] >= 1 && lv->W[l] >= 1, "%s: level %d is %d x %d cells", fn, l, lv->H[l], lv->W[l]);
-        total += (long)A * lv->H[l] * lv->W[l];
-        COSY_REQUIRE(total <= (1L << RPN_KEY_INDEX_BITS), "%s: more than 2^%d anchors per image (levels 0 .. %d)", fn, RPN_KEY_INDEX_BITS, l);
+    for (int l = 0; l < L; ++l)
         COSY_REQUIRE(B == 0 || (lv->objectness[l] != nullptr && lv->deltas[l] != nullptr), "%s: null objectness / deltas of level %d", fn, l);
-    }
     return COSY_OK;
 }
 
@@ -521,8 +497,7 @@ int cosy_rpn_decode(const cosy_rpn_levels_t* levels, int L, int A, int B, int pr
                     long long* cand_keys, int* counts, float* max_coord, cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     if (int rc = rpn_level_args("cosy_rpn_decode", levels, L, A, B, pre_nms_top_n)) return rc;
-    COSY_REQUIRE(cap >= 64 && cap <= cosy_nms_max_candidates() && cap % 64 == 0, "cosy_rpn_decode: cap=%d is no multiple of 64 in [64, %d]", cap,
-                 cosy_nms_max_candidates());
+    if (int rc = arena_cap_args("cosy_rpn_decode", cap)) return rc;
     COSY_REQUIRE((long)pre_nms_top_n * L <= cap, "cosy_rpn_decode: cap=%d holds fewer than pre_nms_top_n L = %ld slots", cap, (long)pre_nms_top_n * L);
     COSY_REQUIRE(min_size >= 0.f, "cosy_rpn_decode: min_size=%g is negative or NaN", (double)min_size);
     if (B == 0) return COSY_OK;
@@ -542,8 +517,8 @@ int cosy_rpn_gather(const int* kept, const int* n_kept, const float* cand_boxes,
                     const int* cand_src, int B, int cap, int max_keep, float* proposals, float* scores, int* levels, int* src, int* counts,
                     cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    COSY_REQUIRE(B >= 0 && B <= RPN_MAX_IMAGES && max_keep >= 0, "cosy_rpn_gather: B=%d max_keep=%d", B, max_keep);
-    COSY_REQUIRE(cap >= 64 && cap <= cosy_nms_max_candidates(), "cosy_rpn_gather: cap=%d outside [64, %d]", cap, cosy_nms_max_candidates());
+    COSY_REQUIRE(B >= 0 && B <= ARENA_MAX_IMAGES && max_keep >= 0, "cosy_rpn_gather: B=%d max_keep=%d", B, max_keep);
+    if (int rc = arena_cap_args("cosy_rpn_gather", cap, false)) return rc;
     COSY_REQUIRE((long)B * max_keep < (1L << 30), "cosy_rpn_gather: %d x %d rows are too many", B, max_keep);
     if (B == 0) return COSY_OK;
     COSY_REQUIRE_PTR("cosy_rpn_gather", n_kept); COSY_REQUIRE_PTR("cosy_rpn_gather", counts);

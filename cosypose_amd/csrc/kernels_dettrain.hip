@@ -9,7 +9,7 @@
 //   dt_sample_kernel     ONE workgroup per image: radix select (four passes of 8 bits, per-wave LDS histograms) of the n_pos-th smallest key
 //                        among the positives and of the n_neg-th among the negatives in the same passes, then ONE ordered compaction: sampled
 //                        candidates in ascending index (ties at a cut: lower index first), and the sampled positives on their own
-//   dt_rpn_loss_kernel   one thread per sampled anchor: label, encode, both loss terms, both gradients scattered into the NCHW planes
+//   dt_rpn_loss_kernel   one thread per sampled anchor: label, encode (det_device.h's box_encode), both loss terms, both gradients into the NCHW planes
 //   dt_roi_cands_kernel  proposals + ground truths -> the RoI side's candidates (padded rows)
 //   dt_roi_gather_kernel the sampled rows: boxes, labels, clamped matched index, regression targets; the positives on their own
 //   dt_count_kernel      N = rows with a label in [0, C)
@@ -31,10 +31,6 @@ namespace {
 constexpr int DT_THREADS = 256;
 constexpr int DT_SEL_THREADS = 1024;
 constexpr int DT_SEL_WAVES = DT_SEL_THREADS / 64;
-constexpr int DT_MAX_IMAGES = 2047;
-constexpr long DT_MAX_ANCHORS = 1L << 20;
-
-typedef cosy_rpn_levels_t RpnLevels;
 
 // where the candidates of the matcher come from: anchors formed from their index (boxes == nullptr) or N padded rows of boxes per image
 struct Cands {
@@ -43,7 +39,7 @@ struct Cands {
     int N, L, A;
 };
 
-// anchor j of an image: level, then (cell, a) with a fastest: section 22 step 1's arithmetic
+// anchor j of an image: the walk over the levels to its level and its index there, then anchor_box (det_device.h), the box rpn_decode_kernel decodes
 __device__ __forceinline__ Box dt_anchor(const RpnLevels& lv, int L, int A, int j, int* level, int* index) {
     int l = 0, first = 0;
     for (; l < L - 1; ++l) {
@@ -51,14 +47,9 @@ __device__ __forceinline__ Box dt_anchor(const RpnLevels& lv, int L, int A, int 
         if (j < first + n) break;
         first += n;
     }
-    const int idx = j - first, W = lv.W[l];
-    const int pos = idx / A, a = idx - pos * A, y = pos / W, x = pos - y * W;
-    const float sx = __fmul_rn((float)x, lv.stride_w[l]), sy = __fmul_rn((float)y, lv.stride_h[l]);
-    *level = l; *index = idx;
-    return {__fadd_rn(lv.base[l][a][0], sx), __fadd_rn(lv.base[l][a][1], sy), __fadd_rn(lv.base[l][a][2], sx), __fadd_rn(lv.base[l][a][3], sy)};
+    *level = l; *index = j - first;
+    return anchor_box(lv, l, j - first, A);
 }
-
-__device__ __forceinline__ Box load_box(const float* p, size_t row) { return {p[4 * row], p[4 * row + 1], p[4 * row + 2], p[4 * row + 3]}; }
 
 // candidate j of image b; false: a padding row (or past the end), which takes no part
 __device__ __forceinline__ bool dt_candidate(const RpnLevels& lv, const Cands& cd, int b, int j, Box* c) {
@@ -259,19 +250,7 @@ __global__ __launch_bounds__(DT_SEL_THREADS) void dt_sample_kernel(const int* __
     }
 }
 
-// ---- encode, the loss terms --------------------------------------------------------------------------------------------------------------
-// BoxCoder.encode_single: the targets that take `p` to `ref`; a zero extent gives the IEEE result
-__device__ __forceinline__ void dt_encode(const Box& ref, const Box& p, float wx, float wy, float ww, float wh, float* t) {
-    const float ew = __fsub_rn(p.x2, p.x1), eh = __fsub_rn(p.y2, p.y1);
-    const float ecx = __fadd_rn(p.x1, __fmul_rn(0.5f, ew)), ecy = __fadd_rn(p.y1, __fmul_rn(0.5f, eh));
-    const float gw = __fsub_rn(ref.x2, ref.x1), gh = __fsub_rn(ref.y2, ref.y1);
-    const float gcx = __fadd_rn(ref.x1, __fmul_rn(0.5f, gw)), gcy = __fadd_rn(ref.y1, __fmul_rn(0.5f, gh));
-    t[0] = __fdiv_rn(__fmul_rn(wx, __fsub_rn(gcx, ecx)), ew);
-    t[1] = __fdiv_rn(__fmul_rn(wy, __fsub_rn(gcy, ecy)), eh);
-    t[2] = __fmul_rn(ww, logf(__fdiv_rn(gw, ew)));
-    t[3] = __fmul_rn(wh, logf(__fdiv_rn(gh, eh)));
-}
-
+// ---- the loss terms (the encode is box_encode of det_device.h, next to the decode it inverts) ---------------------------------------------
 // smooth-L1 of torch (beta = 0: plain L1) and its derivative
 __device__ __forceinline__ float smooth_l1(float x, float beta) {
     const float ax = fabsf(x);
@@ -301,7 +280,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_encode_kernel(const float* __re
     const long at = (long)blockIdx.x * DT_THREADS + threadIdx.x;
     if (at >= n) return;
     float t[4];
-    dt_encode(load_box(ref, at), load_box(boxes, at), wx, wy, ww, wh, t);
+    box_encode(load_box(ref, at), load_box(boxes, at), wx, wy, ww, wh, t);
     for (int c = 0; c < 4; ++c) out[4 * at + c] = t[c];
 }
 
@@ -331,7 +310,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_rpn_loss_kernel(RpnLevels lv, R
             gr.objectness[l][o_at] = __fdiv_rn(__fsub_rn(sigmoid(x), y), n_s);
             if (m >= 0) {
                 float t[4];
-                dt_encode(load_box(gt, (size_t)g0 + m), anc, 1.f, 1.f, 1.f, 1.f, t);
+                box_encode(load_box(gt, (size_t)g0 + m), anc, 1.f, 1.f, 1.f, 1.f, t);
                 for (int c = 0; c < 4; ++c) {
                     const size_t d_at = ((size_t)b * 4 * A + 4 * a + c) * HW + pos;
                     const float diff = __fsub_rn(lv.deltas[l][d_at], t[c]);
@@ -373,7 +352,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_roi_cands_kernel(const float* _
     Box v = {0.f, 0.f, 0.f, 0.f};
     if (j < n) v = load_box(proposals, (size_t)b * post + j);
     else if (j < n + G) v = load_box(gt, (size_t)g0 + j - n);
-    cand[4 * at] = v.x1; cand[4 * at + 1] = v.y1; cand[4 * at + 2] = v.x2; cand[4 * at + 3] = v.y2;
+    store_box(cand, at, v);
     if (j == 0) cand_count[b] = n + G;
 }
 
@@ -405,17 +384,17 @@ __global__ __launch_bounds__(DT_THREADS) void dt_roi_gather_kernel(const float* 
         if (m < G) {
             v = load_box(cand, c_at);
             label = labels[c_at];
-            if (all) dt_encode(load_box(gt, (size_t)g0 + m), v, wx, wy, ww, wh, t);
+            if (all) box_encode(load_box(gt, (size_t)g0 + m), v, wx, wy, ww, wh, t);
         } else m = 0;
     }
     if (all) {
         const size_t o = (size_t)b * bs + r;
-        out_boxes[4 * o] = v.x1; out_boxes[4 * o + 1] = v.y1; out_boxes[4 * o + 2] = v.x2; out_boxes[4 * o + 3] = v.y2;
+        store_box(out_boxes, o, v);
         for (int c = 0; c < 4; ++c) out_targets[4 * o + c] = t[c];
         out_labels[o] = label; out_matched[o] = m;
     } else {
         const size_t o = (size_t)b * want_pos + r;
-        pos_boxes[4 * o] = v.x1; pos_boxes[4 * o + 1] = v.y1; pos_boxes[4 * o + 2] = v.x2; pos_boxes[4 * o + 3] = v.y2;
+        store_box(pos_boxes, o, v);
         pos_labels[o] = label; pos_matched[o] = m;
     }
 }
@@ -507,16 +486,16 @@ __global__ __launch_bounds__(DT_THREADS) void dt_mask_kernel(const long long* __
         if (partial && tid == 0) partial[r] = 0.;
         return;
     }
-    const float x1 = boxes[4 * (size_t)r], y1 = boxes[4 * (size_t)r + 1], x2 = boxes[4 * (size_t)r + 2], y2 = boxes[4 * (size_t)r + 3];
+    const Box roi = load_box(boxes, r);
     float bin_h, bin_w;
     int gh, gw;
-    dt_axis(y1, y2, M, &bin_h, &gh);
-    dt_axis(x1, x2, M, &bin_w, &gw);
+    dt_axis(roi.y1, roi.y2, M, &bin_h, &gh);
+    dt_axis(roi.x1, roi.x2, M, &bin_w, &gw);
     for (int q = tid; q < 2 * M; q += DT_THREADS) {                // the first and last sample of every bin that lies inside [-1, size]
         const int axis = q / M, p = q - axis * M, g = axis ? gw : gh;
         int first = g, last = -1;
         for (int i = 0; i < g; ++i)
-            if (msroi_tap(axis ? x1 : y1, axis ? bin_w : bin_h, p, i, g, axis ? W : H).lo >= 0) { first = i < first ? i : first; last = i; }
+            if (msroi_tap(axis ? roi.x1 : roi.y1, axis ? bin_w : bin_h, p, i, g, axis ? W : H).lo >= 0) { first = i < first ? i : first; last = i; }
         s_first[axis][p] = first; s_last[axis][p] = last;
     }
     __syncthreads();
@@ -528,10 +507,10 @@ __global__ __launch_bounds__(DT_THREADS) void dt_mask_kernel(const long long* __
         const int ph = o / M, pw = o - ph * M;
         float acc = 0.f;
         for (int iy = s_first[0][ph]; iy <= s_last[0][ph]; ++iy) {
-            const Tap ty = msroi_tap(y1, bin_h, ph, iy, gh, H);
+            const Tap ty = msroi_tap(roi.y1, bin_h, ph, iy, gh, H);
             if (ty.lo < 0) continue;
             for (int ix = s_first[1][pw]; ix <= s_last[1][pw]; ++ix) {
-                const Tap tx = msroi_tap(x1, bin_w, pw, ix, gw, W);
+                const Tap tx = msroi_tap(roi.x1, bin_w, pw, ix, gw, W);
                 if (tx.lo < 0) continue;
                 const float w1 = __fmul_rn(ty.wh, tx.wh), w2 = __fmul_rn(ty.wh, tx.wl), w3 = __fmul_rn(ty.wl, tx.wh), w4 = __fmul_rn(ty.wl, tx.wl);
                 float v = __fmul_rn(w1, (float)mask[ty.lo * W + tx.lo]);
@@ -556,21 +535,8 @@ __global__ __launch_bounds__(DT_THREADS) void dt_mask_kernel(const long long* __
     }
 }
 
-int dt_levels_args(const char* fn, const cosy_rpn_levels_t* lv, int L, int A, long* total) {
-    COSY_REQUIRE(lv != nullptr, "%s: null levels", fn);
-    COSY_REQUIRE(L >= 1 && L <= COSY_RPN_MAX_LEVELS, "%s: L=%d outside [1, %d] levels", fn, L, COSY_RPN_MAX_LEVELS);
-    COSY_REQUIRE(A >= 1 && A <= COSY_RPN_MAX_ANCHORS, "%s: A=%d outside [1, %d] anchors per cell", fn, A, COSY_RPN_MAX_ANCHORS);
-    *total = 0;
-    for (int l = 0; l < L; ++l) {
-        COSY_REQUIRE(lv->H[l] >= 1 && lv->W[l] >= 1, "%s: level %d is %d x %d cells", fn, l, lv->H[l], lv->W[l]);
-        *total += (long)A * lv->H[l] * lv->W[l];
-        COSY_REQUIRE(*total <= DT_MAX_ANCHORS, "%s: more than 2^20 anchors per image (levels 0 .. %d)", fn, l);
-    }
-    return COSY_OK;
-}
-
 int dt_batch_args(const char* fn, int B, long rows) {
-    COSY_REQUIRE(B >= 1 && B <= DT_MAX_IMAGES, "%s: B=%d outside [1, %d] images per call", fn, B, DT_MAX_IMAGES);
+    COSY_REQUIRE(B >= 1 && B <= ARENA_MAX_IMAGES, "%s: B=%d outside [1, %d] images per call", fn, B, ARENA_MAX_IMAGES);
     COSY_REQUIRE(rows >= 1 && (long)B * rows < (1L << 30), "%s: %ld rows per image, %d images: outside [1, 2^30) rows", fn, rows, B);
     return COSY_OK;
 }
@@ -591,7 +557,7 @@ int cosy_dt_match(const cosy_rpn_levels_t* levels, int L, int A, const float* ca
     RpnLevels lv = {};
     if (!cand_boxes) {
         long total;
-        if (int rc = dt_levels_args("cosy_dt_match", levels, L, A, &total)) return rc;
+        if (int rc = rpn_levels_args("cosy_dt_match", levels, L, A, &total)) return rc;
         COSY_REQUIRE(total == N, "cosy_dt_match: N=%d, the levels hold %ld anchors", N, total);
         COSY_REQUIRE(cand_counts == nullptr, "cosy_dt_match: cand_counts go with cand_boxes, not with anchors");
         lv = *levels;
@@ -645,7 +611,7 @@ int cosy_dt_rpn_loss(const cosy_rpn_levels_t* levels, const cosy_rpn_levels_t* g
                      cosy_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     long total;
-    if (int rc = dt_levels_args("cosy_dt_rpn_loss", levels, L, A, &total)) return rc;
+    if (int rc = rpn_levels_args("cosy_dt_rpn_loss", levels, L, A, &total)) return rc;
     if (int rc = dt_batch_args("cosy_dt_rpn_loss", B, total)) return rc;
     COSY_REQUIRE(batch_size_per_image >= 1 && batch_size_per_image <= COSY_DT_MAX_BATCH, "cosy_dt_rpn_loss: batch_size_per_image=%d outside [1, %d]",
                  batch_size_per_image, COSY_DT_MAX_BATCH);

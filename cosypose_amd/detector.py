@@ -15,19 +15,22 @@ Candidates per image are capped at `max_candidates` (default 4096, at most MAX_C
 cap^2 / 8 bytes per image); an image with more is REFUSED with a ValueError, never truncated.  Equal scores are visited lower candidate
 index first (candidate index = proposal * (C-1) + label - 1; for nms / batched_nms the box's own index).
 """
+import collections
+
 import numpy as np
 import pandas as pd
 import torch
 
 from . import _lib
 from . import tensor_collection as tc
+from .io_formats import empty_detections
 
 MAX_CANDIDATES = 16384          # cosy_nms_max_candidates()
 DEFAULT_CANDIDATES = 4096
 MAX_MASK_SIDE = 62
-MAX_IMAGES = 2047               # cosy_det_decode's limits: 11 bits of image, 21 bits of candidate index in the sort key
-MAX_CLASSES = 4096
-MAX_CANDIDATE_INDEX = 1 << 21
+MAX_IMAGES = 2047               # ARENA_MAX_IMAGES: 11 bits of image in the sort key, for every side of the detector (detector_rpn, detector_train)
+MAX_CLASSES = 4096              # cosy_det_decode's and COSY_DT_MAX_CLASSES (detector_train)
+MAX_CANDIDATE_INDEX = 1 << 21   # cosy_det_decode's 21 bits of candidate index in the sort key
 
 
 # ---- argument checks: all of them run before the library is loaded -----------------------------------------------------------------
@@ -92,6 +95,23 @@ def _nms_segments(boxes, order, labels, max_coord, seg_start, seg_count, B, cap,
     _lib.check(l.cosy_nms_scan(_lib.ptr(mask), _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(seg_count), B, N, cap, max_keep,
                                _lib.ptr(kept), _lib.ptr(n_kept), _lib.ptr(keep_flags), _lib.stream()))
     return (kept, n_kept, keep_flags) if flags else (kept, n_kept)
+
+
+_Arena = collections.namedtuple('_Arena', 'boxes scores labels src keys counts max_coord')
+
+
+def _arena(B, cap, dev):
+    """the candidate arena of B images x cap slots (csrc/det_device.h), in the order both decode entry points take it; labels: what NMS keeps apart"""
+    n, f32, i32 = B * cap, torch.float32, torch.int32
+    layout = (((n, 4), f32), (n, f32), (n, i32), (n, i32), (n, torch.int64), (B, i32), (B, f32))
+    return _Arena(*[torch.empty(shape, dtype=kind, device=dev) for shape, kind in layout])
+
+
+def _arena_nms(arena, B, cap, iou_threshold, max_keep):
+    """after the caller's decode launch: ONE sort of the keys (unique: image, score descending, candidate index), then NMS image by image"""
+    order = torch.sort(arena.keys)[1]
+    seg_start = _lib.ints_to_device(np.arange(B) * cap, arena.keys.device)
+    return _nms_segments(arena.boxes, order, arena.labels, arena.max_coord, seg_start, arena.counts, B, cap, iou_threshold, max_keep)
 
 
 def _nms(boxes, scores, idxs, iou_threshold, what):
@@ -187,27 +207,17 @@ def _run(class_logits, box_regression, proposals, net_sizes, original_sizes, cou
     ratios = np.stack([orig[:, 1].astype(f32) / net[:, 1].astype(f32), orig[:, 0].astype(f32) / net[:, 0].astype(f32)], 1)   # width, height
     tables = _lib.host_to_device(np.concatenate([net.astype(f32).reshape(-1), ratios.astype(f32).reshape(-1)]), dev)
     offsets = _lib.ints_to_device(np.concatenate([[0], np.cumsum(counts)]), dev)
-    cand_boxes = torch.empty((B * cap, 4), dtype=torch.float32, device=dev)
-    cand_scores = torch.empty(B * cap, dtype=torch.float32, device=dev)
-    cand_labels = torch.empty(B * cap, dtype=torch.int32, device=dev)
-    cand_src = torch.empty(B * cap, dtype=torch.int32, device=dev)
-    keys = torch.empty(B * cap, dtype=torch.int64, device=dev)
-    n_cand = torch.empty(B, dtype=torch.int32, device=dev)
-    max_coord = torch.empty(B, dtype=torch.float32, device=dev)
+    arena = _arena(B, cap, dev)
     l = _lib.lib()
     _lib.check(l.cosy_det_decode(_lib.ptr(class_logits), _lib.ptr(box_regression), _lib.ptr(props), _lib.ptr(offsets), _lib.ptr(tables), R, C, B,
-                                 float(score_thresh), cap, _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_labels), _lib.ptr(cand_src),
-                                 _lib.ptr(keys), _lib.ptr(n_cand), _lib.ptr(max_coord), _lib.stream()))
-    order = torch.sort(keys)[1]                                            # the keys are unique: image, score descending, candidate index
-    seg_start = _lib.ints_to_device(np.arange(B) * cap, dev)
-    kept, n_kept = _nms_segments(cand_boxes, order, cand_labels, max_coord, seg_start, n_cand, B, cap, nms_thresh, dpi)
+                                 float(score_thresh), cap, *map(_lib.ptr, arena), _lib.stream()))
+    kept, n_kept = _arena_nms(arena, B, cap, nms_thresh, dpi)
     st.boxes_net = torch.empty((B * dpi, 4), dtype=torch.float32, device=dev)
     st.boxes_frame = torch.empty((B * dpi, 4), dtype=torch.float32, device=dev)
     st.src = torch.empty(B * dpi, dtype=torch.int32, device=dev)
     st.packed = torch.empty(2 * B + 2 * B * dpi, dtype=torch.int32, device=dev)
-    _lib.check(l.cosy_det_gather(_lib.ptr(kept), _lib.ptr(n_kept), _lib.ptr(n_cand), _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_labels),
-                                 _lib.ptr(cand_src), _lib.ptr(tables[2 * B:]), B, cap, dpi, _lib.ptr(st.boxes_net), _lib.ptr(st.boxes_frame),
-                                 _lib.ptr(st.src), _lib.ptr(st.packed), _lib.stream()))
+    _lib.check(l.cosy_det_gather(_lib.ptr(kept), _lib.ptr(n_kept), _lib.ptr(arena.counts), *map(_lib.ptr, arena[:4]), _lib.ptr(tables[2 * B:]), B, cap,
+                                 dpi, _lib.ptr(st.boxes_net), _lib.ptr(st.boxes_frame), _lib.ptr(st.src), _lib.ptr(st.packed), _lib.stream()))
     return st
 
 
@@ -318,8 +328,7 @@ def detections_from_heads(class_logits, box_regression, proposals, net_sizes, or
     rows, im_ids, cat_ids, scores = _read(st)
     dev = st.device
     if len(rows) == 0:
-        return tc.PandasTensorCollection(infos=pd.DataFrame({'score': [], 'label': [], 'batch_im_id': []}),
-                                         bboxes=torch.empty(0, 4, device=dev, dtype=torch.float32))
+        return empty_detections(dev)
     labels = np.array([str(category_id_to_label[int(c)]) for c in cat_ids], dtype=object)
     keep = _filter(labels, scores, detection_th, one_instance_per_class)
     infos = pd.DataFrame({'batch_im_id': im_ids[keep], 'label': labels[keep], 'score': scores[keep].astype(np.float64)})

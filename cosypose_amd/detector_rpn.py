@@ -19,16 +19,15 @@ zero box into a zero box, which its small-box test drops, so the padded rows can
 import ctypes
 
 import numpy as np
-import pandas as pd
 import torch
 
 from . import _lib
 from . import detector
-from . import tensor_collection as tc
+from .detector import MAX_IMAGES             # the sort key: 11 bits of image, then here 32 of ordered score and 20 of candidate index
+from .io_formats import empty_detections
 
 MAX_LEVELS = 8                   # cosy_rpn_levels_t / cosy_msroi_levels_t
 MAX_ANCHORS_PER_CELL = 16
-MAX_IMAGES = 2047                # the sort key: 11 bits of image, 32 of ordered score, 20 of candidate index
 MAX_ANCHORS_PER_IMAGE = 1 << 20
 MAX_TAPS = 128                   # output_size * sampling_ratio
 DEFAULT_SIZES = ((32,), (64,), (128,), (256,), (512,))
@@ -111,8 +110,57 @@ def rpn_anchors(feature_sizes, padded_size, sizes=DEFAULT_SIZES, aspect_ratios=D
     return torch.from_numpy(np.concatenate(rows).astype(np.float32))
 
 
-def _net_sizes(net_sizes, B):
-    return detector._sizes(net_sizes, 'net_sizes', B)
+class AnchorGrid:
+    """the anchors of one image as the kernels form them from an index: section 22 step 1's level description, no table; fills every RpnLevels"""
+
+    def __init__(self, feature_sizes, padded_size, sizes=DEFAULT_SIZES, aspect_ratios=DEFAULT_RATIOS):
+        feature_sizes = [tuple(int(v) for v in s) for s in feature_sizes]
+        if not 1 <= len(feature_sizes) <= MAX_LEVELS:
+            raise ValueError(f'feature_sizes must hold 1 to {MAX_LEVELS} levels, got {len(feature_sizes)}')
+        self.tables, self.A = _anchor_tables(feature_sizes, padded_size, sizes, aspect_ratios)
+        self.L = len(feature_sizes)
+        self.N = sum(self.A * H * W for H, W, *_ in self.tables)
+
+    @classmethod
+    def cells(cls, objectness):
+        """the cells of the head's outputs alone, for a launch that forms no anchor (rpn_select): strides and base anchors stay zero"""
+        grid = cls.__new__(cls)
+        grid.tables = [(int(o.shape[2]), int(o.shape[3]), 0.0, 0.0, np.zeros((0, 4), np.float32)) for o in objectness]
+        grid.A, grid.L = int(objectness[0].shape[1]), len(objectness)
+        return grid
+
+    def levels(self, objectness=None, deltas=None):
+        lv = _lib.RpnLevels()
+        for l, (H, W, sh, sw, base) in enumerate(self.tables):
+            lv.H[l], lv.W[l], lv.stride_h[l], lv.stride_w[l] = H, W, float(sh), float(sw)
+            if objectness is not None:
+                lv.objectness[l], lv.deltas[l] = objectness[l].data_ptr(), deltas[l].data_ptr()
+            for a in range(base.shape[0]):
+                for c in range(4):
+                    lv.base[l][a][c] = float(base[a, c])
+        return lv
+
+
+def _rpn_heads(objectness, bbox_deltas):
+    """the RPN head's outputs, one (B,A,H_l,W_l) / (B,4A,H_l,W_l) pair per level, read in place -> objectness, bbox_deltas (lists), B, A, L"""
+    objectness, bbox_deltas = _levels(objectness, 'objectness'), _levels(bbox_deltas, 'bbox_deltas')
+    L = len(objectness)
+    if len(bbox_deltas) != L:
+        raise ValueError(f'objectness holds {L} levels, bbox_deltas {len(bbox_deltas)}')
+    if not torch.is_tensor(objectness[0]) or objectness[0].dim() != 4:
+        raise ValueError(f'objectness[0] must be (B,A,H,W), got {tuple(objectness[0].shape) if torch.is_tensor(objectness[0]) else type(objectness[0]).__name__}')
+    B, A = int(objectness[0].shape[0]), int(objectness[0].shape[1])
+    for l in range(L):
+        o = _feature(objectness[l], f'objectness[{l}]', (B, A, None, None))
+        _feature(bbox_deltas[l], f'bbox_deltas[{l}]', (B, 4 * A, int(o.shape[2]), int(o.shape[3])))
+    return objectness, bbox_deltas, B, A, L
+
+
+def _rpn_grid(objectness, A, padded_size, sizes, aspect_ratios):
+    grid = AnchorGrid([tuple(o.shape[2:]) for o in objectness], padded_size, sizes, aspect_ratios)
+    if grid.A != A:
+        raise ValueError(f'objectness has {A} anchors per cell, sizes x aspect_ratios give {grid.A}')
+    return grid
 
 
 def rpn_proposals(objectness, bbox_deltas, net_sizes, padded_size, sizes=DEFAULT_SIZES, aspect_ratios=DEFAULT_RATIOS, pre_nms_top_n=1000,
@@ -125,19 +173,8 @@ def rpn_proposals(objectness, bbox_deltas, net_sizes, padded_size, sizes=DEFAULT
     the rest zeros[, with return_source also levels and candidate indices (int32, -1 on padding)].  as_list: the list of (counts[b], 4)
     tensors instead (one small device-to-host copy).  Equal logits: lower candidate index first, at the k-th place too; an anchor whose
     logit or any delta is NaN is absent."""
-    objectness, bbox_deltas = _levels(objectness, 'objectness'), _levels(bbox_deltas, 'bbox_deltas')
-    L = len(objectness)
-    if len(bbox_deltas) != L:
-        raise ValueError(f'objectness holds {L} levels, bbox_deltas {len(bbox_deltas)}')
-    if not torch.is_tensor(objectness[0]) or objectness[0].dim() != 4:
-        raise ValueError(f'objectness[0] must be (B,A,H,W), got {tuple(objectness[0].shape) if torch.is_tensor(objectness[0]) else type(objectness[0]).__name__}')
-    B, A = int(objectness[0].shape[0]), int(objectness[0].shape[1])
-    for l in range(L):
-        o = _feature(objectness[l], f'objectness[{l}]', (B, A, None, None))
-        _feature(bbox_deltas[l], f'bbox_deltas[{l}]', (B, 4 * A, int(o.shape[2]), int(o.shape[3])))
-    tables, A_gen = _anchor_tables([tuple(o.shape[2:]) for o in objectness], padded_size, sizes, aspect_ratios)
-    if A_gen != A:
-        raise ValueError(f'objectness has {A} anchors per cell, sizes x aspect_ratios give {A_gen}')
+    objectness, bbox_deltas, B, A, L = _rpn_heads(objectness, bbox_deltas)
+    grid = _rpn_grid(objectness, A, padded_size, sizes, aspect_ratios)
     pre, post = int(pre_nms_top_n), int(post_nms_top_n)
     if pre < 1 or post < 1:
         raise ValueError(f'pre_nms_top_n and post_nms_top_n must be positive, got {pre}, {post}')
@@ -149,7 +186,7 @@ def rpn_proposals(objectness, bbox_deltas, net_sizes, padded_size, sizes=DEFAULT
         raise ValueError(f'{B} images exceed the limit of {MAX_IMAGES} per call')
     if not 0 <= float(min_size):
         raise ValueError(f'min_size must not be negative, got {min_size}')
-    net = _net_sizes(net_sizes, B)
+    net = detector._sizes(net_sizes, 'net_sizes', B)
     pad_h, pad_w = _pair(padded_size, 'padded_size')
     if B and ((net[:, 0] > pad_h).any() or (net[:, 1] > pad_w).any()):
         raise ValueError(f'net_sizes {net.tolist()} exceed padded_size {(pad_h, pad_w)}')
@@ -161,38 +198,22 @@ def rpn_proposals(objectness, bbox_deltas, net_sizes, padded_size, sizes=DEFAULT
         if as_list:
             return []
         return out + (torch.empty(0, dtype=torch.int32, device=dev),) * 2 if return_source else out
-    lv = _lib.RpnLevels()
-    for l, (H, W, sh, sw, base) in enumerate(tables):
-        lv.objectness[l], lv.deltas[l] = objectness[l].data_ptr(), bbox_deltas[l].data_ptr()
-        lv.H[l], lv.W[l], lv.stride_h[l], lv.stride_w[l] = H, W, float(sh), float(sw)
-        for a in range(A):
-            for c in range(4):
-                lv.base[l][a][c] = float(base[a, c])
+    lv = grid.levels(objectness, bbox_deltas)
     net_dev = _lib.host_to_device(net.astype(np.float32).reshape(-1), dev)
     sel_idx = torch.empty((B, L, pre), dtype=torch.int32, device=dev)
     sel_count = torch.empty((B, L), dtype=torch.int32, device=dev)
-    cand_boxes = torch.empty((B * cap, 4), dtype=torch.float32, device=dev)
-    cand_scores = torch.empty(B * cap, dtype=torch.float32, device=dev)
-    cand_level = torch.empty(B * cap, dtype=torch.int32, device=dev)
-    cand_src = torch.empty(B * cap, dtype=torch.int32, device=dev)
-    keys = torch.empty(B * cap, dtype=torch.int64, device=dev)
-    n_cand = torch.empty(B, dtype=torch.int32, device=dev)
-    max_coord = torch.empty(B, dtype=torch.float32, device=dev)
+    arena = detector._arena(B, cap, dev)                                 # (its labels: the candidates' levels)
     l_ = _lib.lib()
     _lib.check(l_.cosy_rpn_select(ctypes.byref(lv), L, A, B, pre, _lib.ptr(sel_idx), _lib.ptr(sel_count), _lib.stream()))
     _lib.check(l_.cosy_rpn_decode(ctypes.byref(lv), L, A, B, pre, _lib.ptr(sel_idx), _lib.ptr(sel_count), _lib.ptr(net_dev), float(min_size), cap,
-                                  _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_level), _lib.ptr(cand_src), _lib.ptr(keys),
-                                  _lib.ptr(n_cand), _lib.ptr(max_coord), _lib.stream()))
-    order = torch.sort(keys)[1]                                            # the keys are unique: image, logit descending, candidate index
-    seg_start = _lib.ints_to_device(np.arange(B) * cap, dev)
-    kept, n_kept = detector._nms_segments(cand_boxes, order, cand_level, max_coord, seg_start, n_cand, B, cap, nms_thresh, post)
+                                  *map(_lib.ptr, arena), _lib.stream()))
+    kept, n_kept = detector._arena_nms(arena, B, cap, nms_thresh, post)
     proposals = torch.empty((B * post, 4), dtype=torch.float32, device=dev)
     scores = torch.empty(B * post, dtype=torch.float32, device=dev)
     levels = torch.empty(B * post, dtype=torch.int32, device=dev)
     src = torch.empty(B * post, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(l_.cosy_rpn_gather(_lib.ptr(kept), _lib.ptr(n_kept), _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_level), _lib.ptr(cand_src),
-                                  B, cap, post, _lib.ptr(proposals), _lib.ptr(scores), _lib.ptr(levels), _lib.ptr(src), _lib.ptr(counts), _lib.stream()))
+    _lib.check(l_.cosy_rpn_gather(_lib.ptr(kept), _lib.ptr(n_kept), *map(_lib.ptr, arena[:4]), B, cap, post, _lib.ptr(proposals), _lib.ptr(scores), _lib.ptr(levels), _lib.ptr(src), _lib.ptr(counts), _lib.stream()))
     if as_list:
         host = counts.cpu().tolist()                                       # THE device-to-host copy of the list form
         return [proposals[b * post:b * post + n] for b, n in enumerate(host)]
@@ -203,19 +224,13 @@ def rpn_select(objectness, bbox_deltas, pre_nms_top_n):
     """the first launch of rpn_proposals on its own: -> sel_idx (B,L,pre_nms_top_n) int32, sel_count (B,L) int32 on the device; the first
     sel_count[b,l] entries of sel_idx[b,l] are the anchors of level l taken for image b: those strictly above the k-th logit in ascending
     index order, then the lowest-index anchors at it.  Rows past sel_count are not written."""
-    objectness, bbox_deltas = _levels(objectness, 'objectness'), _levels(bbox_deltas, 'bbox_deltas')
-    L, pre = len(objectness), int(pre_nms_top_n)
-    B, A = int(objectness[0].shape[0]), int(objectness[0].shape[1])
-    for l in range(L):
-        o = _feature(objectness[l], f'objectness[{l}]', (B, A, None, None))
-        _feature(bbox_deltas[l], f'bbox_deltas[{l}]', (B, 4 * A, int(o.shape[2]), int(o.shape[3])))
+    objectness, bbox_deltas, B, A, L = _rpn_heads(objectness, bbox_deltas)
+    pre = int(pre_nms_top_n)
     if pre < 1 or pre * L > detector.MAX_CANDIDATES:
         raise ValueError(f'pre_nms_top_n x levels = {pre} x {L} must lie in [1, cosy_nms_max_candidates() = {detector.MAX_CANDIDATES}]')
     detector._on_device(objectness=objectness, bbox_deltas=bbox_deltas)
     dev = objectness[0].device
-    lv = _lib.RpnLevels()
-    for l in range(L):
-        lv.objectness[l], lv.deltas[l], lv.H[l], lv.W[l] = objectness[l].data_ptr(), bbox_deltas[l].data_ptr(), objectness[l].shape[2], objectness[l].shape[3]
+    lv = AnchorGrid.cells(objectness).levels(objectness, bbox_deltas)
     sel_idx = torch.full((B, L, pre), -1, dtype=torch.int32, device=dev)
     sel_count = torch.zeros((B, L), dtype=torch.int32, device=dev)
     _lib.check(_lib.lib().cosy_rpn_select(ctypes.byref(lv), L, A, B, pre, _lib.ptr(sel_idx), _lib.ptr(sel_count), _lib.stream()))
@@ -289,7 +304,7 @@ def multiscale_roi_align(features, boxes, net_sizes, output_size, sampling_ratio
         if len(counts) != B or any(c < 0 for c in counts) or sum(counts) != R:
             raise ValueError(f'counts must hold one non-negative number per image ({B}) summing to {R} rows, got {counts}')
     if scales is None:
-        scales = infer_scales([tuple(int(v) for v in f.shape[2:]) for f in features], _net_sizes(net_sizes, B))
+        scales = infer_scales([tuple(int(v) for v in f.shape[2:]) for f in features], detector._sizes(net_sizes, 'net_sizes', B))
     scales = [float(s) for s in scales]
     if len(scales) != L or any(not s > 0 for s in scales):
         raise ValueError(f'scales must hold one positive number per level ({L}), got {scales}')
@@ -392,8 +407,7 @@ def detections_from_features(features, rpn_head, box_head, mask_head, net_sizes,
     rpn_kw = {k: filters.pop(k) for k in RPN_OPTIONS if k in filters}
     B = int(features[0].shape[0]) if torch.is_tensor(features[0]) and features[0].dim() == 4 else -1
     if B == 0:
-        return tc.PandasTensorCollection(infos=pd.DataFrame({'score': [], 'label': [], 'batch_im_id': []}),
-                                         bboxes=torch.empty(0, 4, device=features[0].device, dtype=torch.float32))
+        return empty_detections(features[0].device)
     roi_maps = features[:int(n_roi_levels)]
     objectness, deltas = rpn_head(features)
     objectness, deltas = [o.contiguous() for o in objectness], [d.contiguous() for d in deltas]

@@ -26,38 +26,14 @@ import torch
 from . import _lib
 from . import detector
 from . import detector_rpn
-from .detector_rpn import DEFAULT_SIZES, DEFAULT_RATIOS
+from .detector import MAX_CLASSES, MAX_IMAGES             # COSY_DT_MAX_CLASSES; the images of one call, as on every side of the detector
+from .detector_rpn import DEFAULT_SIZES, DEFAULT_RATIOS, AnchorGrid
 
 MAX_GT = 1024                    # COSY_DT_MAX_GT: ground truths per image (they sit in LDS)
 MAX_BATCH = 4096                 # COSY_DT_MAX_BATCH: batch_size_per_image
-MAX_CLASSES = 4096               # COSY_DT_MAX_CLASSES
 MAX_MASK_SIDE = 128              # COSY_DT_MAX_M
-MAX_IMAGES = 2047
 RPN_WEIGHTS, ROI_WEIGHTS = (1.0, 1.0, 1.0, 1.0), (10.0, 10.0, 5.0, 5.0)
 LOSS_KEYS = ('loss_objectness', 'loss_rpn_box_reg', 'loss_classifier', 'loss_box_reg', 'loss_mask')
-
-
-class AnchorGrid:
-    """the anchors of one image as the kernels form them from an index: section 22 step 1's level description, no table"""
-
-    def __init__(self, feature_sizes, padded_size, sizes=DEFAULT_SIZES, aspect_ratios=DEFAULT_RATIOS):
-        feature_sizes = [tuple(int(v) for v in s) for s in feature_sizes]
-        if not 1 <= len(feature_sizes) <= detector_rpn.MAX_LEVELS:
-            raise ValueError(f'feature_sizes must hold 1 to {detector_rpn.MAX_LEVELS} levels, got {len(feature_sizes)}')
-        self.tables, self.A = detector_rpn._anchor_tables(feature_sizes, padded_size, sizes, aspect_ratios)
-        self.L = len(feature_sizes)
-        self.N = sum(self.A * H * W for H, W, *_ in self.tables)
-
-    def levels(self, objectness=None, deltas=None):
-        lv = _lib.RpnLevels()
-        for l, (H, W, sh, sw, base) in enumerate(self.tables):
-            lv.H[l], lv.W[l], lv.stride_h[l], lv.stride_w[l] = H, W, float(sh), float(sw)
-            if objectness is not None:
-                lv.objectness[l], lv.deltas[l] = objectness[l].data_ptr(), deltas[l].data_ptr()
-            for a in range(self.A):
-                for c in range(4):
-                    lv.base[l][a][c] = float(base[a, c])
-        return lv
 
 
 # ---- argument checks: all of them run before the library is loaded -----------------------------------------------------------------
@@ -261,21 +237,10 @@ def rpn_loss(objectness, bbox_deltas, targets, net_sizes, padded_size, sizes=DEF
     (plain L1: 0.4.2).  objectness[l] (B,A,H_l,W_l), bbox_deltas[l] (B,4A,H_l,W_l): float32, contiguous, on the device, read in place; keys
     (B, anchors per image) int32 or None.  -> (loss_objectness, loss_rpn_box_reg), differentiable with respect to the head's outputs[, and
     with return_samples (matched_idxs, samp_idx, samp_count)]."""
-    objectness, bbox_deltas = detector_rpn._levels(objectness, 'objectness'), detector_rpn._levels(bbox_deltas, 'bbox_deltas')
-    L = len(objectness)
-    if len(bbox_deltas) != L:
-        raise ValueError(f'objectness holds {L} levels, bbox_deltas {len(bbox_deltas)}')
-    if not torch.is_tensor(objectness[0]) or objectness[0].dim() != 4:
-        raise ValueError(f'objectness[0] must be (B,A,H,W), got {tuple(objectness[0].shape) if torch.is_tensor(objectness[0]) else type(objectness[0]).__name__}')
-    B, A = int(objectness[0].shape[0]), int(objectness[0].shape[1])
-    for l in range(L):
-        o = detector_rpn._feature(objectness[l], f'objectness[{l}]', (B, A, None, None))
-        detector_rpn._feature(bbox_deltas[l], f'bbox_deltas[{l}]', (B, 4 * A, int(o.shape[2]), int(o.shape[3])))
-    grid = AnchorGrid([tuple(o.shape[2:]) for o in objectness], padded_size, sizes, aspect_ratios)
-    if grid.A != A:
-        raise ValueError(f'objectness has {A} anchors per cell, sizes x aspect_ratios give {grid.A}')
+    objectness, bbox_deltas, B, A, _ = detector_rpn._rpn_heads(objectness, bbox_deltas)
+    grid = detector_rpn._rpn_grid(objectness, A, padded_size, sizes, aspect_ratios)
     boxes, _ = _targets(targets, B)
-    detector_rpn._net_sizes(net_sizes, B)
+    detector._sizes(net_sizes, 'net_sizes', B)
     bs, n_pos_max = _sampler_args(batch_size_per_image, positive_fraction)
     keys = _keys(keys, B, grid.N)
     detector._on_device(objectness=objectness, bbox_deltas=bbox_deltas, gt_boxes=boxes, keys=keys)

@@ -33,20 +33,24 @@ def _host(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
+def empty_detections(device):
+    """the collection Detector.get_detections returns for "nothing found": no row, the reference's column order, no masks"""
+    return tc.PandasTensorCollection(infos=pd.DataFrame({'score': [], 'label': [], 'batch_im_id': []}),
+                                     bboxes=torch.empty(0, 4, device=device, dtype=torch.float32))
+
+
 def make_detections(per_image, device='cuda', detection_th=None, one_instance_per_class=False, output_masks=False, mask_th=0.8):
     """per_image: one dict per frame, in batch order: 'boxes' (n,4) xyxy px, 'labels' (n,) label strings, 'scores' (n,)
     [, 'masks' (n,1,h,w) probabilities] -> PandasTensorCollection as Detector.get_detections returns it."""
     counts = [len(out['boxes']) for out in per_image]
     total = int(sum(counts))
+    if not total:
+        return empty_detections(device)
     frame_of = np.repeat(np.arange(len(per_image)), counts)
     labels = np.array([str(l) for out in per_image for l in list(out['labels'])], dtype=object)
-    scores = np.concatenate([_host(out['scores']).astype(np.float64).reshape(-1) for out in per_image]) if total else np.zeros(0)
-    if total:
-        boxes = torch.cat([torch.as_tensor(out['boxes']).reshape(-1, 4) for out in per_image]).to(device=device, dtype=torch.float32)
-        table = pd.DataFrame({'batch_im_id': frame_of, 'label': labels, 'score': scores})
-    else:
-        boxes = torch.empty(0, 4, device=device, dtype=torch.float32)
-        table = pd.DataFrame({'score': [], 'label': [], 'batch_im_id': []})      # the reference's column order for "nothing found"
+    scores = np.concatenate([_host(out['scores']).astype(np.float64).reshape(-1) for out in per_image])
+    boxes = torch.cat([torch.as_tensor(out['boxes']).reshape(-1, 4) for out in per_image]).to(device=device, dtype=torch.float32)
+    table = pd.DataFrame({'batch_im_id': frame_of, 'label': labels, 'score': scores})
     keep = np.arange(total)
     if detection_th is not None:
         keep = keep[scores[keep] > detection_th]
@@ -55,11 +59,11 @@ def make_detections(per_image, device='cuda', detection_th=None, one_instance_pe
         ranked = keep[np.argsort(-scores[keep], kind='stable')]
         _, first = np.unique(labels[ranked].astype(str), return_index=True)
         keep = ranked[np.sort(first)]
-    fields = {'bboxes': boxes[torch.as_tensor(keep, device=boxes.device)] if total else boxes}
-    if output_masks and total:
+    fields = {'bboxes': boxes[torch.as_tensor(keep, device=boxes.device)]}
+    if output_masks:
         probs = torch.cat([torch.as_tensor(out['masks'])[:, 0] for out in per_image if len(out['boxes'])])
         fields['masks'] = (probs > mask_th).to(device)[torch.as_tensor(keep, device=device)]
-    return tc.PandasTensorCollection(infos=table.iloc[keep].reset_index(drop=True) if total else table, **fields)
+    return tc.PandasTensorCollection(infos=table.iloc[keep].reset_index(drop=True), **fields)
 
 
 def bop19_rows(predictions):

@@ -14,7 +14,7 @@ import torch
 import detpost_ref as post
 import detpre_ref as ref
 from cosypose_amd import detections_from_features, multiscale_roi_align, rpn_proposals
-from cosypose_amd import _lib, detector_rpn
+from cosypose_amd import _lib, detector, detector_rpn
 from cosypose_amd.io_formats import make_detections
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +184,40 @@ def test_proposals_of_an_image_whose_every_anchor_is_nan():
     assert got[1].cpu().tolist() == [5, 0]
     empty = rpn_proposals([dev(o[:0]) for o in obj], [dev(d[:0]) for d in dl], [], PAD, SIZES)
     assert tuple(empty[0].shape) == (0, 4) and tuple(empty[1].shape) == (0,) and empty[0].is_cuda
+
+
+def test_the_rpn_decoder_and_the_box_head_decoder_agree_to_the_byte():
+    """rpn_decode_kernel (weights 1) and det_decode_kernel (weights 10, 10, 5, 5) decode and clip through one box_decode (csrc/det_device.h).
+    The same anchors with the same deltas, handed to the box head's side multiplied by its weights, must give the same bytes: the deltas are
+    multiples of 1/8 in [-1, 1] (dx, dy in {-1/8, 0, 1/8}, so that no box leaves its image), for which d 10 and d 5 are exact in float32 and
+    so is the division back.  One level of 3 x 4 cells with strides 40/3 and 12.5; the second image is smaller, so more of its boxes clip.
+    With seed 0 every decoded box keeps sides of at least 1.7 (both CPU twins, which also agree with each other): nothing is dropped by the
+    small-box test on either side, and all 2 x 36 anchors must come back from both."""
+    H, W, pad, nets, sizes, n = 3, 4, (40, 50), [(40, 50), (38, 47)], ((16,),), 36
+    rng = np.random.RandomState(0)
+    dl = (rng.randint(-8, 9, (2, 4 * A, H, W)) / 8).astype(f32)
+    dl.reshape(2, A, 4, H, W)[:, :, :2] = (rng.randint(-1, 2, (2, A, 2, H, W)) / 8).astype(f32)
+    obj = rng.permutation(2 * n).astype(f32).reshape(2, A, H, W)
+    anchors = detector_rpn.rpn_anchors([(H, W)], pad, sizes)
+    rows = [ref.flatten_level(obj[b], dl[b])[1] for b in range(2)]                             # (36,4) per image, row = anchor index
+    for b in range(2):                                                                         # the precondition, on the CPU twins alone
+        boxes = post.clip(torch.as_tensor(ref.decode(rows[b], anchors.numpy())), nets[b]).numpy()
+        assert min((boxes[:, 2] - boxes[:, 0]).min(), (boxes[:, 3] - boxes[:, 1]).min()) >= 1e-2
+        assert 0 < ((boxes[:, :2] == 0).any(1) | (boxes[:, 2] == nets[b][1]) | (boxes[:, 3] == nets[b][0])).sum() < n   # some clip, some do not
+    props, counts, _, _, src = rpn_proposals([dev(obj)], [dev(dl)], nets, pad, sizes, pre_nms_top_n=n, post_nms_top_n=n, nms_thresh=1.0,
+                                             min_size=1e-2, return_source=True)
+    reg = np.concatenate([np.concatenate([np.zeros((n, 4), f32), r * np.array([10, 10, 5, 5], f32)], 1) for r in rows])
+    assert (reg[:, 4:] / np.array([10, 10, 5, 5], f32) == np.concatenate(rows)).all()
+    logits = np.tile(np.array([0, 20], f32), (2 * n, 1))
+    boxes, _, labels, im_ids, cand = detector.postprocess_detections(dev(logits), dev(reg), [anchors.cuda()] * 2, nets, None, nms_thresh=1.0,
+                                                                     detections_per_img=64, return_source=True)
+    assert counts.cpu().tolist() == [n, n] and tuple(boxes.shape) == (2 * n, 4) and (labels == 1).all()
+    props, src, boxes, im_ids, cand = (t.cpu().numpy() for t in (props, src, boxes, im_ids, cand))
+    for b in range(2):
+        from_rpn, from_head = props[b * n:(b + 1) * n], boxes[im_ids == b]
+        by_rpn, by_head = np.argsort(src[b * n:(b + 1) * n]), np.argsort(cand[im_ids == b])
+        assert sorted(src[b * n:(b + 1) * n].tolist()) == sorted(cand[im_ids == b].tolist()) == list(range(n))   # every anchor, on both sides
+        assert from_rpn[by_rpn].tobytes() == from_head[by_head].tobytes()
 
 
 # ---- RoIAlign ------------------------------------------------------------------------------------------------------------------------
