@@ -151,6 +151,10 @@ _SIGNATURES = {
     'cosy_resize_u8': ([_P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _SZ, _P], _I),
     'cosy_resize_frames_u8': ([_P, _I, _I, _I, _P, _L, _I, _P, _P, _P], _I),
     'cosy_detector_input': ([_P, _P, _I, _I, _I, _P, _L, _I, _I, _I, _P, _P], _I),
+    'cosy_head_big_rows': ([], _I),
+    'cosy_head_max_tile_rows': ([], _I),
+    'cosy_head_pack': ([_P, _P, _I, _I, _I, _I, _P], _I),
+    'cosy_head_conv': ([_P, _P], _I),
     'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
 }
 EXPORTS = tuple(_SIGNATURES)
@@ -187,6 +191,15 @@ class RpnLevels(ctypes.Structure):     # cosy_rpn_levels_t
 
 class MsroiLevels(ctypes.Structure):   # cosy_msroi_levels_t
     _fields_ = [('feat', _P * RPN_MAX_LEVELS), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS), ('scale', _F * RPN_MAX_LEVELS)]
+
+
+HEAD_STORE_ROWS, HEAD_STORE_NCHW, HEAD_STORE_DECONV_ROWS, HEAD_STORE_DECONV_NCHW = 0, 1, 2, 3
+
+
+class HeadLayer(ctypes.Structure):     # cosy_head_layer_t
+    _fields_ = [('x', _P), ('w', _P), ('bias', _P), ('out', _P), ('out1', _P)] + [
+        (k, _I) for k in ('dtype', 'ksize', 'c_in', 'c_out', 'relu', 'store', 'n_split', 'n_levels')] + [
+        ('row_start', _I * (RPN_MAX_LEVELS + 1)), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS)]
 
 
 class ProfRec(ctypes.Structure):

@@ -992,6 +992,48 @@ typedef struct cosy_detin_item {
 int cosy_detector_input(const cosy_detin_item_t* items_host, const cosy_detin_item_t* items, int n, int Hp, int Wp, const int* tables,
                         long n_tables, int lut, int units, int n_units, float* out_images, cosy_stream_t stream);
 
+/* ---- The detector's heads on the matrix pipe: every layer of Mask R-CNN's RPN head, box head + predictor and mask head + predictor as one
+ * implicit GEMM (inference only) ----  DESIGN.md section 26 holds the contract and the summation order.
+ * Activations are ROWS of the storage type `dtype`: M rows of c_in contiguous channels (NHWC; a linear layer's row is its input vector).
+ * The rows of a call belong to n_levels groups of whole maps: level l owns rows [row_start[l], row_start[l+1]), which are B_l maps of
+ * H[l] x W[l] cells, image-major, then y, then x; M = row_start[n_levels].  A 3x3 tap outside its map contributes nothing.
+ * cosy_head_pack: contiguous NCHW float32 (B,C,HW) -> rows (B HW, C) of `dtype` (round to nearest even).  C a positive multiple of 8.
+ * cosy_head_conv: out = act(W x + bias) of all M rows in one launch, accumulated in float32.
+ *   ksize 3: 3x3 conv, pad 1, stride 1; ksize 1: 1x1 conv, or a linear layer with H = W = 1.  c_in is the channels of a row (a multiple of 8,
+ *   anything else is refused), c_out the GEMM's columns.
+ *   w: the weight (c_out, taps, c_in) in fragment order, NP = c_out rounded up to 64, KB = 16 (float32) or 32 (16-bit), KBn = ceil(c_in / KB):
+ *     element [nt][tap][kb][lane][e], nt < NP / 16, lane < 64, e < KB / 4, holds w[16 nt + (lane & 15)][tap][KB kb + k] with
+ *     k = (KB / 4) (lane >> 4) + e; zero where the row or the channel does not exist.
+ *   bias: NP floats (zero past c_out).  relu: 1 = x < 0 ? 0 : x after the bias (a NaN stays NaN).
+ *   store COSY_HEAD_STORE_ROWS: out = rows (M, c_out) of `dtype`, c_out a multiple of 8.
+ *   store COSY_HEAD_STORE_NCHW: float32 NCHW.  Columns [0, n_split) go to `out`, the rest to `out1`; level l's maps start at element
+ *     n_split row_start[l] of out as (B_l, n_split, H, W) and at (c_out - n_split) row_start[l] of out1 (two sibling layers as one GEMM).
+ *     n_split = c_out: everything to out, out1 unused.
+ *   store COSY_HEAD_STORE_DECONV_ROWS / _DECONV_NCHW: the layer is ConvTranspose2d(k=2, s=2): c_out = 4 C_o columns (o, dy, dx), bias
+ *     repeated per column; column (o, dy, dx) of cell (y, x) is stored at (o, 2y+dy, 2x+dx) of a (2H, 2W) map, as rows of `dtype`
+ *     (level l from row 4 row_start[l]; C_o a multiple of 8) or as float32 NCHW (level l from element 4 row_start[l] C_o).
+ * Summation order of one output: accumulator +0.0; k-blocks of KB channels ascending; inside a block the taps (ky, kx) ascending; inside a
+ *   tap, float32: the block's channels in the order 4 g + t, t = 0..3 outside, g = 0..3 inside (0, 4, 8, 12, 1, 5, ...), one fmaf each;
+ *   16-bit: one MFMA over the block's 32 exact products.  Then one rounded bias add, ReLU, the conversion to the store's type.
+ * Checked on the host before the launch (COSY_EINVAL, cosy_last_error() names the argument); M = 0 returns COSY_OK and launches nothing;
+ * M <= 2^30, offsets are 64-bit.  x, w, out 16-byte aligned.  No atomics: equal inputs give equal bits.
+ * cosy_head_big_rows(): M from which the launcher picks its large row tile; cosy_head_max_tile_rows(): rows of that tile. */
+enum { COSY_HEAD_STORE_ROWS = 0, COSY_HEAD_STORE_NCHW = 1, COSY_HEAD_STORE_DECONV_ROWS = 2, COSY_HEAD_STORE_DECONV_NCHW = 3 };
+typedef struct cosy_head_layer {
+    const void* x;
+    const void* w;
+    const float* bias;
+    void* out;
+    void* out1;
+    int dtype, ksize, c_in, c_out, relu, store, n_split, n_levels;
+    int row_start[COSY_RPN_MAX_LEVELS + 1];
+    int H[COSY_RPN_MAX_LEVELS], W[COSY_RPN_MAX_LEVELS];
+} cosy_head_layer_t;
+int cosy_head_big_rows(void);
+int cosy_head_max_tile_rows(void);
+int cosy_head_pack(const float* in, void* rows, int B, int C, int HW, int dtype, cosy_stream_t stream);
+int cosy_head_conv(const cosy_head_layer_t* layer, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
