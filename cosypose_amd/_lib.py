@@ -1,163 +1,76 @@
 """ctypes binding of libcosyhip.so (the C ABI declared in include/cosyhip.h).
 
+The header is the declaration: every entry point's argtypes / restype are read from its prototype (parse_header below), so a new
+entry point needs the header and its C definition and nothing here.  The header's constants and the structs that cross the
+boundary are restated below, once each; tests/test_c_abi.py holds them against the header with the C compiler.
+
 There is no fallback: if the HIP library is missing or a call fails, this raises.
 """
 import ctypes
 import os
+import re
 
-from .build import LIB
+import torch
 
-COSY_F32, COSY_BF16, COSY_F16 = 0, 1, 2
-COSY_MASK_U8, COSY_MASK_I32 = 0, 1
+from .build import LIB, HEADER
+
+
+class CosyHipError(RuntimeError):
+    pass
+
+
 _lib = None
 
 _c = ctypes
-_P, _I, _F, _SZ, _L, _D = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_long, _c.c_double
+_P, _I, _F, _D = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double
 
-_SIGNATURES = {
-    'cosy_version': ([], _I),
-    'cosy_last_error': ([], _c.c_char_p),
-    'cosy_effnet_b3_param_count': ([], _c.c_long),
-    'cosy_effnet_b3_out_hw': ([_I, _I, _c.POINTER(_I), _c.POINTER(_I)], _I),
-    'cosy_effnet_b3_create': ([_P, _SZ, _I, _I, _I, _I, _c.POINTER(_P)], _I),
-    'cosy_effnet_b3_destroy': ([_P], _I),
-    'cosy_effnet_b3_workspace_bytes': ([_P], _SZ),
-    'cosy_effnet_b3_set_input_nchw': ([_P, _P, _I, _P], _I),
-    'cosy_effnet_b3_features_nchw': ([_P, _I, _P, _P], _I),
-    'cosy_effnet_b3_set_probe': ([_P, _I, _P], _I),
-    'cosy_effnet_b3_block_info': ([_P, _I, _c.POINTER(_I)], _I),
-    'cosy_effnet_b3_set_profiling': ([_P, _I], _I),
-    'cosy_effnet_b3_profile_read': ([_P, _P, _I, _c.POINTER(_I)], _I),
-    'cosy_frames_to_nhwc4': ([_P, _P, _I, _I, _I, _P], _I),
-    'cosy_frames_u8_to_nhwc4': ([_P, _P, _I, _I, _I, _P], _I),
-    'cosy_crop_pack': ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
-    'cosy_effnet_b3_forward': ([_P, _I, _P, _P, _P, _P], _I),
-    'cosy_crop_geometry': ([_P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
-    'cosy_roi_align': ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_pose_update': ([_P, _P, _P, _I, _P, _P], _I),
-    'cosy_tco_init_from_boxes': ([_P, _P, _P, _I, _F, _P, _P], _I),
-    'cosy_tco_init_zup_autodepth': ([_P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
-    'cosy_scatter_argmin': ([_P, _P, _I, _I, _P, _P], _I),
-    'cosy_expand_ids_for_symmetry': ([_P, _I, _P, _P, _P, _P], _I),
-    'cosy_symmetric_distance': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_loss_co_symmetric': ([_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_loss_refiner_disentangled': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
-    'cosy_dists_add': ([_P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
-    'cosy_pose_errors_workspace_bytes': ([_I, _I], _SZ),
-    'cosy_pose_errors': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P], _I),
-    'cosy_render_scratch_bytes': ([_I, _I, _I, _I], _c.c_size_t),
-    'cosy_render_meshes': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P], _I),
-    'cosy_render_meshes_ex': ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_render_crop_pack': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_render_crop_pack_to': ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_render_scene_scratch_bytes': ([_I, _I, _I, _I, _I], _SZ),
-    'cosy_render_scene': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_train_workspace_bytes': ([], _c.c_size_t),
-    'cosy_crop_pack_to': ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
-    'cosy_crop_pack_to_ws': ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_crop_pack_workspace_bytes': ([_I, _I, _I], _SZ),
-    'cosy_bn_train_stats': ([_P, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_bn_train_apply': ([_P, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _P], _I),
-    'cosy_bn_train_backward': ([_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P], _I),
-    'cosy_bn_train_backward_gated': ([_P, _P, _P, _F, _P, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P], _I),
-    'cosy_dw_train_forward': ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_dw_train_backward_data': ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_dw_train_backward_data_add': ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_dw_train_backward_weight': ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_dw_train_backward_weight_ex': ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P], _I),
-    'cosy_wgrad_tall_supported': ([_L, _I, _I], _I),
-    'cosy_wgrad_tall': ([_P, _P, _L, _I, _I, _P, _P, _P], _I),
-    'cosy_wgrad': ([_P, _P, _L, _I, _I, _P, _P, _P], _I),
-    'cosy_train_gemm': ([_P, _P, _I, _L, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_train_pack_plan': ([_I, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_train_pack_all': ([_P, _I, _c.c_longlong, _P, _P], _I),
-    'cosy_train_gemm_packed': ([_P, _P, _c.c_longlong, _L, _I, _I, _P, _P, _P], _I),
-    'cosy_stem_im2col_ld': ([_P, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_rows_mean': ([_P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_rows_mean_bn': ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_rows_dot_bn': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_bn_train_apply_gated': ([_P, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P], _I),
-    'cosy_rows_dot': ([_P, _P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_rows_scale': ([_P, _P, _P, _F, _I, _I, _I, _P, _P], _I),
-    'cosy_rows_broadcast': ([_P, _F, _I, _I, _I, _P, _P], _I),
-    'cosy_act_forward': ([_P, _L, _I, _P, _P], _I),
-    'cosy_se_train_forward': ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_se_train_backward': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_fc_small_forward': ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
-    'cosy_fc_small_backward': ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_act_backward': ([_P, _P, _L, _I, _P, _P], _I),
-    'cosy_stem_im2col': ([_P, _I, _I, _I, _P, _P], _I),
-    'cosy_loss_refiner_disentangled_backward': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_grad_norm_clip': ([_P, _L, _F, _P, _P, _P], _I),
-    'cosy_symmetric_distance_reprojected': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_ba_workspace_bytes': ([_I, _I, _I, _I], _SZ),
-    'cosy_ba_upload_ids': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_ba_align': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_ba_linearize': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_ba_solve': ([_P, _P, _I, _D, _P, _P, _P], _I),
-    'cosy_ba_batch_table_bytes': ([_I, _I, _I], _SZ),
-    'cosy_ba_batch_workspace_bytes': ([_I, _I, _c.c_longlong], _SZ),
-    'cosy_ba_batch_upload': ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _c.POINTER(_c.c_longlong), _c.POINTER(_I), _P], _I),
-    'cosy_ba_batch_linearize': ([_P, _I, _P], _I),
-    'cosy_ba_batch_solve_step': ([_P, _P], _I),
-    'cosy_ba_batch_record': ([_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_ba_batch_decide': ([_P, _I, _D, _D, _D, _P, _I, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_ba_batch_iterate': ([_P, _I, _I, _P], _I),
-    'cosy_ransac_max_tmatches': ([], _I),
-    'cosy_ransac_hypotheses': ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_ransac_score': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_ransac_best': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-                         _I),
-    'cosy_augment_workspace_bytes': ([_I, _I, _I], _SZ),
-    'cosy_augment_batch': ([_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _SZ, _P], _I),
-    'cosy_bop_mssd_mspd_workspace_bytes': ([_I, _I], _SZ),
-    'cosy_bop_mssd_mspd': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P], _I),
-    'cosy_bop_instance_boxes': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_bop_windows_workspace_bytes': ([_c.c_longlong], _SZ),
-    'cosy_bop_render_windows': ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _P, _SZ, _P], _I),
-    'cosy_bop_vsd_workspace_bytes': ([_I], _SZ),
-    'cosy_bop_vsd_counts': ([_P, _P, _P, _P, _P, _P, _c.c_longlong, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P], _I),
-    'cosy_gt_info_workspace_bytes': ([_I], _SZ),
-    'cosy_gt_info': ([_P, _P, _P, _P, _P, _c.c_longlong, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P], _I),
-    'cosy_gt_composite_u8': ([_P, _c.c_longlong, _P, _P], _I),
-    'cosy_model_info_workspace_bytes': ([_P, _I], _SZ),
-    'cosy_model_info': ([_P, _I, _P, _P, _I, _P, _P, _SZ, _P], _I),
-    'cosy_mask_instance_stats': ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_instance_masks': ([_P, _I, _P, _P, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_box_iou_pairs': ([_P, _P, _I, _P, _P], _I),
-    'cosy_box_iou_matrix': ([_P, _P, _I, _I, _P, _P], _I),
-    'cosy_nms_max_candidates': ([], _I),
-    'cosy_det_decode': ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_nms_mask': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P], _I),
-    'cosy_nms_scan': ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
-    'cosy_det_gather': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_paste_masks': ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
-    'cosy_rpn_select': ([_P, _I, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_rpn_decode': ([_P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_rpn_gather': ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_msroi_align': ([_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
-    'cosy_msroi_align_backward': ([_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
-    'cosy_dt_match': ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_dt_sample': ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_dt_encode': ([_P, _P, _L, _F, _F, _F, _F, _P, _P], _I),
-    'cosy_dt_rpn_loss': ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_dt_roi_candidates': ([_P, _P, _I, _P, _P, _I, _I, _P, _P, _P], _I),
-    'cosy_dt_roi_gather': ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_dt_fastrcnn_loss': ([_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
-    'cosy_dt_mask_loss': ([_P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P], _I),
-    'cosy_resize_ksize': ([_I, _I, _I], _I),
-    'cosy_resize_coeffs': ([_I, _I, _I, _P, _P, _SZ], _I),
-    'cosy_resize_workspace_bytes': ([_I, _I, _I, _I], _SZ),
-    'cosy_resize_u8': ([_P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _SZ, _P], _I),
-    'cosy_resize_frames_u8': ([_P, _I, _I, _I, _P, _L, _I, _P, _P, _P], _I),
-    'cosy_detector_input': ([_P, _P, _I, _I, _I, _P, _L, _I, _I, _I, _P, _P], _I),
-    'cosy_head_big_rows': ([], _I),
-    'cosy_head_max_tile_rows': ([], _I),
-    'cosy_head_pack': ([_P, _P, _I, _I, _I, _I, _P], _I),
-    'cosy_head_conv': ([_P, _P], _I),
-    'cosy_adam_step': ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P], _I),
-}
+_SCALARS = {'int': _I, 'unsigned': _c.c_uint, 'unsigned int': _c.c_uint, 'float': _F, 'double': _D, 'long': _c.c_long,
+            'unsigned long': _c.c_ulong, 'long long': _c.c_longlong, 'unsigned long long': _c.c_ulonglong, 'size_t': _c.c_size_t,
+            'cosy_stream_t': _P}
+_PROTOTYPE = re.compile(r'([\w\s*]+?)\b(cosy_\w+)\s*\(([^()]*)\)\s*;')
+
+
+def parse_header(text):
+    """C prototypes `<ret> cosy_name(<params>);` -> {name: (argtypes, restype)} in the order they are declared.  Anything with `*` or
+    `[]` is a c_void_p (device pointers, handles, struct pointers, pointers to pointers); a scalar maps by _SCALARS; a type that is in
+    neither group raises and names the declaration."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+
+    def ctype(decl, name, what):
+        words = [w for w in decl.replace('*', ' * ').split() if w != 'const']
+        if '*' in words or '[' in decl:
+            if what == 'return type':       # the one pointer the ABI returns is cosy_last_error()'s message
+                if words != ['char', '*']:
+                    raise CosyHipError(f'cosyhip.h: {name}: unsupported {what} `{decl.strip()}`')
+                return _c.c_char_p
+            return _P
+        for n in (len(words), len(words) - 1):          # without and with the parameter's name
+            if ' '.join(words[:n]) in _SCALARS:
+                return _SCALARS[' '.join(words[:n])]
+        raise CosyHipError(f'cosyhip.h: {name}: unsupported {what} `{decl.strip()}`')
+
+    out = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        params = [] if params.strip() in ('', 'void') else params.split(',')
+        out[name] = ([ctype(p, name, 'parameter') for p in params], ctype(ret, name, 'return type'))
+    return out
+
+
+with open(HEADER) as _f:
+    _SIGNATURES = parse_header(_f.read())
 EXPORTS = tuple(_SIGNATURES)
+
+# ---- the header's constants, under its names without the COSY_ prefix (COSY_F32 ... and COSY_MASK_* keep it: they are imported under it) ----
+COSY_F32, COSY_BF16, COSY_F16 = 0, 1, 2
+DTYPES = {torch.float32: COSY_F32, torch.bfloat16: COSY_BF16, torch.float16: COSY_F16}      # torch dtype -> storage type of a kernel
+COSY_MASK_U8, COSY_MASK_I32 = 0, 1
+AUG_GATE, AUG_SHARPNESS, AUG_CONTRAST, AUG_BRIGHTNESS, AUG_COLOR, AUG_GRAY = 1, 2, 4, 8, 16, 32
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3
+RPN_MAX_LEVELS, RPN_MAX_ANCHORS = 8, 16
+DT_MAX_GT, DT_MAX_BATCH, DT_MAX_CLASSES, DT_MAX_M = 1024, 4096, 4096, 128
+DETIN_ONE_TAP = 1
+HEAD_STORE_ROWS, HEAD_STORE_NCHW, HEAD_STORE_DECONV_ROWS, HEAD_STORE_DECONV_NCHW = 0, 1, 2, 3
 
 
 class MeshSet(ctypes.Structure):       # cosy_mesh_t
@@ -181,9 +94,6 @@ class BaBatch(ctypes.Structure):       # cosy_ba_batch_t
                           'ctrl', 'hist_iteration', 'hist_lambda', 'hist_loss', 'hist_TWO_9d', 'hist_TCW_9d', 'workspace')]
 
 
-RPN_MAX_LEVELS, RPN_MAX_ANCHORS = 8, 16
-
-
 class RpnLevels(ctypes.Structure):     # cosy_rpn_levels_t
     _fields_ = [('objectness', _P * RPN_MAX_LEVELS), ('deltas', _P * RPN_MAX_LEVELS), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS),
                 ('stride_h', _F * RPN_MAX_LEVELS), ('stride_w', _F * RPN_MAX_LEVELS), ('base', _F * 4 * RPN_MAX_ANCHORS * RPN_MAX_LEVELS)]
@@ -193,16 +103,13 @@ class MsroiLevels(ctypes.Structure):   # cosy_msroi_levels_t
     _fields_ = [('feat', _P * RPN_MAX_LEVELS), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS), ('scale', _F * RPN_MAX_LEVELS)]
 
 
-HEAD_STORE_ROWS, HEAD_STORE_NCHW, HEAD_STORE_DECONV_ROWS, HEAD_STORE_DECONV_NCHW = 0, 1, 2, 3
-
-
 class HeadLayer(ctypes.Structure):     # cosy_head_layer_t
     _fields_ = [('x', _P), ('w', _P), ('bias', _P), ('out', _P), ('out1', _P)] + [
         (k, _I) for k in ('dtype', 'ksize', 'c_in', 'c_out', 'relu', 'store', 'n_split', 'n_levels')] + [
         ('row_start', _I * (RPN_MAX_LEVELS + 1)), ('H', _I * RPN_MAX_LEVELS), ('W', _I * RPN_MAX_LEVELS)]
 
 
-class ProfRec(ctypes.Structure):
+class ProfRec(ctypes.Structure):       # cosy_prof_rec_t
     _fields_ = [('name', _c.c_char * 64), ('layer', _I), ('n', _I), ('ms_avg', _F), ('ms_min', _F),
                 ('bytes', _c.c_double), ('flops', _c.c_double), ('cbytes', _c.c_double)]
 
@@ -214,10 +121,6 @@ def profile_read(handle):
     check(lib().cosy_effnet_b3_profile_read(handle, recs, 1100, ctypes.byref(n)))
     return [dict(name=r.name.decode(), layer=r.layer, n=r.n, ms_avg=r.ms_avg, ms_min=r.ms_min, bytes=r.bytes, flops=r.flops, cbytes=r.cbytes)
             for r in recs[:n.value]]
-
-
-class CosyHipError(RuntimeError):
-    pass
 
 
 def lib():

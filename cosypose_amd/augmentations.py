@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib
 
-GATE, SHARPNESS, CONTRAST, BRIGHTNESS, COLOR, GRAY = 1, 2, 4, 8, 16, 32           # cosyhip.h: COSY_AUG_*
+GATE, SHARPNESS, CONTRAST, BRIGHTNESS, COLOR, GRAY = (_lib.AUG_GATE, _lib.AUG_SHARPNESS, _lib.AUG_CONTRAST, _lib.AUG_BRIGHTNESS, _lib.AUG_COLOR,
+                                                       _lib.AUG_GRAY)
 RGB_GATE_P = 0.8
 # stage -> (p, factor interval, present bit), in the order PoseDataset applies them (pose_dataset.py:54-60)
 STAGES = (('sharpness', 0.3, (0., 50.), SHARPNESS), ('contrast', 0.3, (0.2, 50.), CONTRAST),

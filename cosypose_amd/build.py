@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libcosyhip.so')
+HEADER = os.path.normpath(os.path.join(HERE, '..', 'include', 'cosyhip.h'))     # the C ABI's one declaration (_lib.py binds from it)
 SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_dethead.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
            'kernels_dw.hip', 'kernels_wave.hip', 'kernels_stem.hip', 'kernels_smx.hip', 'effnet.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
@@ -43,7 +44,7 @@ FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    return hs + [os.path.join(HERE, '..', 'include', 'cosyhip.h')]
+    return hs + [HEADER]
 
 
 TUNE_LIB = os.path.join(LIBDIR, 'libcosyhip_tune.so')   # -DCOSY_TUNE build: env knobs + phase knock-outs, experiments only
@@ -176,7 +177,7 @@ def _csrc_sha():
         if f.endswith(('.hip', '.h', '.inc')):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), 'rb').read())
-    h.update(open(os.path.join(HERE, '..', 'include', 'cosyhip.h'), 'rb').read())
+    h.update(open(HEADER, 'rb').read())
     h.update(' '.join(FLAGS + [f'{k}:{" ".join(v)}' for k, v in sorted(FILE_FLAGS.items())]).encode())
     return h.hexdigest()[:16]
 

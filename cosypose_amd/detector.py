@@ -29,7 +29,7 @@ MAX_CANDIDATES = 16384          # cosy_nms_max_candidates()
 DEFAULT_CANDIDATES = 4096
 MAX_MASK_SIDE = 62
 MAX_IMAGES = 2047               # ARENA_MAX_IMAGES: 11 bits of image in the sort key, for every side of the detector (detector_rpn, detector_train)
-MAX_CLASSES = 4096              # cosy_det_decode's and COSY_DT_MAX_CLASSES (detector_train)
+MAX_CLASSES = _lib.DT_MAX_CLASSES       # cosy_det_decode's limit too
 MAX_CANDIDATE_INDEX = 1 << 21   # cosy_det_decode's 21 bits of candidate index in the sort key
 
 

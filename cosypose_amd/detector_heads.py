@@ -16,9 +16,9 @@ import torch
 
 from . import _lib
 
-MAX_LEVELS = 8
+MAX_LEVELS = _lib.RPN_MAX_LEVELS
 MAX_ROWS = 1 << 30
-_DTYPES = {torch.float32: _lib.COSY_F32, torch.bfloat16: _lib.COSY_BF16, torch.float16: _lib.COSY_F16}
+_DTYPES = _lib.DTYPES
 
 RPN_KEYS = ('rpn.head.conv', 'rpn.head.cls_logits', 'rpn.head.bbox_pred')
 BOX_KEYS = ('roi_heads.box_head.fc6', 'roi_heads.box_head.fc7', 'roi_heads.box_predictor.cls_score', 'roi_heads.box_predictor.bbox_pred')

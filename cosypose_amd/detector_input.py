@@ -33,7 +33,7 @@ ITEM_DTYPE = np.dtype([('frame', '<u8'), ('sc', '<i8'), ('sy', '<i8'), ('sx', '<
                        ('boxes_out', '<u8'), ('h', '<i4'), ('w', '<i4'), ('nh', '<i4'), ('nw', '<i4'), ('xb', '<i4'), ('yb', '<i4'), ('xn', '<i4'),
                        ('yn', '<i4'), ('n_masks', '<i4'), ('n_boxes', '<i4'), ('rw', '<f4'), ('rh', '<f4'), ('flags', '<i4'), ('reserved', '<i4', (3,))])
 assert ITEM_DTYPE.itemsize == 128
-ONE_TAP = 1                                                  # COSY_DETIN_ONE_TAP
+ONE_TAP = _lib.DETIN_ONE_TAP
 MAX_UNITS = 65535                                            # frames + mask planes of one call: the grid's z dimension
 MAX_ROWS = 524280                                            # 8 rows per workgroup, 65535 workgroups
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)

@@ -26,8 +26,8 @@ from . import detector
 from .detector import MAX_IMAGES             # the sort key: 11 bits of image, then here 32 of ordered score and 20 of candidate index
 from .io_formats import empty_detections
 
-MAX_LEVELS = 8                   # cosy_rpn_levels_t / cosy_msroi_levels_t
-MAX_ANCHORS_PER_CELL = 16
+MAX_LEVELS = _lib.RPN_MAX_LEVELS                 # cosy_rpn_levels_t / cosy_msroi_levels_t
+MAX_ANCHORS_PER_CELL = _lib.RPN_MAX_ANCHORS
 MAX_ANCHORS_PER_IMAGE = 1 << 20
 MAX_TAPS = 128                   # output_size * sampling_ratio
 DEFAULT_SIZES = ((32,), (64,), (128,), (256,), (512,))

@@ -29,9 +29,9 @@ from . import detector_rpn
 from .detector import MAX_CLASSES, MAX_IMAGES             # COSY_DT_MAX_CLASSES; the images of one call, as on every side of the detector
 from .detector_rpn import DEFAULT_SIZES, DEFAULT_RATIOS, AnchorGrid
 
-MAX_GT = 1024                    # COSY_DT_MAX_GT: ground truths per image (they sit in LDS)
-MAX_BATCH = 4096                 # COSY_DT_MAX_BATCH: batch_size_per_image
-MAX_MASK_SIDE = 128              # COSY_DT_MAX_M
+MAX_GT = _lib.DT_MAX_GT          # ground truths per image (they sit in LDS)
+MAX_BATCH = _lib.DT_MAX_BATCH    # batch_size_per_image
+MAX_MASK_SIDE = _lib.DT_MAX_M
 RPN_WEIGHTS, ROI_WEIGHTS = (1.0, 1.0, 1.0, 1.0), (10.0, 10.0, 5.0, 5.0)
 LOSS_KEYS = ('loss_objectness', 'loss_rpn_box_reg', 'loss_classifier', 'loss_box_reg', 'loss_mask')
 

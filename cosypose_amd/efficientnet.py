@@ -19,10 +19,10 @@ import torch
 from torch import nn
 
 from . import arch
-from ._lib import lib, check, ptr, stream, require_device, COSY_F32, COSY_BF16, COSY_F16, CosyHipError
+from ._lib import lib, check, ptr, stream, require_device, DTYPES, CosyHipError
 
-_DTYPES = {'fp32': COSY_F32, 'f32': COSY_F32, 'float32': COSY_F32, 'bf16': COSY_BF16, 'bfloat16': COSY_BF16,
-           'fp16': COSY_F16, 'f16': COSY_F16, 'float16': COSY_F16, 'half': COSY_F16}
+_DTYPES = {name: DTYPES[t] for t, names in ((torch.float32, ('fp32', 'f32', 'float32')), (torch.bfloat16, ('bf16', 'bfloat16')),
+                                            (torch.float16, ('fp16', 'f16', 'float16', 'half'))) for name in names}
 
 
 class _Block(nn.Module):

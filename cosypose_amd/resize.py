@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 
-FILTERS = {'bilinear': 2, 'bicubic': 3}                      # cosyhip.h: COSY_RESIZE_BILINEAR, COSY_RESIZE_BICUBIC
+FILTERS = {'bilinear': _lib.RESIZE_BILINEAR, 'bicubic': _lib.RESIZE_BICUBIC}
 # cosy_resize_item_t
 ITEM_DTYPE = np.dtype([('src', '<u8'), ('h', '<i4'), ('w', '<i4'), ('hb', '<i4'), ('hk', '<i4'), ('hks', '<i4'), ('vb', '<i4'), ('vk', '<i4'),
                        ('vks', '<i4')])

@@ -1,9 +1,7 @@
 """CPU tests of the BOP errors and scores: the numpy twins (tests/bop_ref.py) against hand values, the host halves of
 cosypose_amd/bop_errors.py and bop_meters.py (window planning, matching, recall, summary) on tables alone, and the C ABI's host-side
 argument checks.  No GPU."""
-import ctypes
 import pathlib
-import re
 
 import numpy as np
 import pandas as pd
@@ -265,12 +263,10 @@ BOP_SYMBOLS = ('cosy_bop_mssd_mspd_workspace_bytes', 'cosy_bop_mssd_mspd', 'cosy
 
 def test_c_abi_declares_exports_and_builds_the_bop_entry_points():
     from cosypose_amd import _lib
-    from cosypose_amd.build import build, LIB, SOURCES, FILE_FLAGS
+    from cosypose_amd.build import build, SOURCES, FILE_FLAGS
     build()
-    lib = ctypes.CDLL(LIB)
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
     for name in BOP_SYMBOLS:
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in _lib.EXPORTS and hasattr(lib, name), name
+        assert name in _lib.EXPORTS, name           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points
     assert 'kernels_bop.hip' in SOURCES and '-ffp-contract=off' in FILE_FLAGS['kernels_bop.hip']
 
 

@@ -2,8 +2,6 @@
 hand, the pixel table against the installed torch bit for bit, the numpy twin tests/detin_ref.py against the installed torch -- nearest and
 boxes equal, the bilinear image within the derived per-pixel bound of detin_ref.bilinear_bound, with 1 and with 2 threads -- the host
 tables of the package against the twin's, the refusals that need no device and no library, and the C ABI."""
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -170,13 +168,9 @@ def test_c_abi_exports_the_entry_point():
     import cosypose_amd
     from cosypose_amd import _lib, build
     from cosypose_amd import detector_input as di
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
-    assert re.search(r'\bcosy_detector_input\s*\(', header) and 'cosy_detector_input' in _lib.EXPORTS
-    fields = re.search(r'typedef struct cosy_detin_item \{(.*?)\}', header, flags=re.S).group(1)
-    names = re.findall(r'\b(frame|sc|sy|sx|masks_out|masks|boxes_out|boxes|h|w|nh|nw|xb|yb|xn|yn|n_masks|n_boxes|rw|rh|flags|reserved)\b', fields)
-    assert names == list(di.ITEM_DTYPE.names) and di.ITEM_DTYPE.itemsize == 128
-    assert int(re.search(r'COSY_DETIN_ONE_TAP\s*=\s*(\d+)', header).group(1)) == di.ONE_TAP
-    assert len(_lib._SIGNATURES['cosy_detector_input'][0]) == 12
+    # test_c_abi.py: EXPORTS, the header and the built library name the same entry points; cosy_detin_item_t field by field, COSY_DETIN_ONE_TAP
+    # and the twelve arguments of the signature
+    assert 'cosy_detector_input' in _lib.EXPORTS
     assert 'kernels_detin.hip' in build.SOURCES and '-ffp-contract=off' in build.FILE_FLAGS['kernels_detin.hip']
     assert (REPO / 'cosypose_amd' / 'csrc' / 'kernels_detin.hip').exists()
     assert callable(cosypose_amd.detector_input) and cosypose_amd.detector_input.detector_input is di.detector_input

@@ -127,10 +127,7 @@ def test_host_tables_equal_the_restatement():
 def test_c_abi_exports_the_frames_entry_point():
     import cosypose_amd
     from cosypose_amd import _lib, build, frames
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
-    assert re.search(r'\bcosy_resize_frames_u8\s*\(', header) and 'cosy_resize_frames_u8' in _lib.EXPORTS
-    fields = re.search(r'typedef struct cosy_frame_item \{(.*?)\}', header, flags=re.S).group(1)
-    assert re.findall(r'\b(image|mask|h|w|xb|yb|xn|yn)\b', fields) == list(frames.ITEM_DTYPE.names) and frames.ITEM_DTYPE.itemsize == 40
+    assert 'cosy_resize_frames_u8' in _lib.EXPORTS           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points, cosy_frame_item_t field by field
     assert 'kernels_frames.hip' in build.SOURCES and '-ffp-contract=off' in build.FILE_FLAGS['kernels_frames.hip']
     assert cosypose_amd.resize_frames is frames.resize_frames
 

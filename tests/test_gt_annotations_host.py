@@ -1,9 +1,7 @@
 """CPU tests of the BOP ground-truth annotations: the numpy twin (tests/gt_ref.py) against hand values, the host half of
 cosypose_amd/gt_annotations.py (chunks, id_in_segm, refusals, box conventions), io_formats.scene_gt_info_rows, and the C ABI's host-side
 argument checks.  No GPU."""
-import ctypes
 import pathlib
-import re
 
 import numpy as np
 import pandas as pd
@@ -172,12 +170,10 @@ GT_SYMBOLS = ('cosy_gt_info_workspace_bytes', 'cosy_gt_info', 'cosy_gt_composite
 
 def test_c_abi_declares_exports_and_builds_the_gt_entry_points():
     from cosypose_amd import _lib
-    from cosypose_amd.build import build, LIB, SOURCES, FILE_FLAGS
+    from cosypose_amd.build import build, SOURCES, FILE_FLAGS
     build()
-    lib = ctypes.CDLL(LIB)
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
     for name in GT_SYMBOLS:
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in _lib.EXPORTS and hasattr(lib, name), name
+        assert name in _lib.EXPORTS, name           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points
     assert 'kernels_gt.hip' in SOURCES and '-ffp-contract=off' in FILE_FLAGS['kernels_gt.hip']
     # both files compile one text of the distance function and the window helpers
     bop, gt = ((REPO / 'cosypose_amd' / 'csrc' / f).read_text() for f in ('kernels_bop.hip', 'kernels_gt.hip'))

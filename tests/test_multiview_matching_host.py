@@ -191,15 +191,11 @@ def test_ids_are_checked_on_the_host(g):
 
 
 def test_new_symbols_declared_bound_and_exported():
-    import ctypes
     from cosypose_amd import _lib
-    from cosypose_amd.build import build, LIB, SOURCES
-    from conftest import REPO
+    from cosypose_amd.build import build, SOURCES
     build()
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
-    lib = ctypes.CDLL(LIB)
     for name in ('cosy_ransac_max_tmatches', 'cosy_ransac_hypotheses', 'cosy_ransac_score', 'cosy_ransac_best'):
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in _lib.EXPORTS and hasattr(lib, name)
+        assert name in _lib.EXPORTS           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points
     assert 'kernels_ransac.hip' in SOURCES
     import cosypose_amd
     from cosypose_amd import multiview_matching, multiview_predictor

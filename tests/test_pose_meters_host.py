@@ -226,15 +226,11 @@ def test_n_top_changes_the_ground_truth_count():
 
 # ---- plumbing ------------------------------------------------------------------------------------------------------------------------------
 def test_new_symbols_declared_bound_and_exported():
-    import ctypes
     from cosypose_amd import _lib
-    from cosypose_amd.build import build, LIB, SOURCES
-    from conftest import REPO
+    from cosypose_amd.build import build, SOURCES
     build()
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
-    lib = ctypes.CDLL(LIB)
     for name in ('cosy_pose_errors', 'cosy_pose_errors_workspace_bytes'):
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in _lib.EXPORTS and hasattr(lib, name)
+        assert name in _lib.EXPORTS           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points
     assert 'kernels_eval.hip' in SOURCES
     import cosypose_amd
     from cosypose_amd import pose_meters, distances

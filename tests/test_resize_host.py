@@ -119,14 +119,10 @@ def test_host_routine_refuses_what_it_cannot_serve(hostlib):
 
 def test_c_abi_exports_the_resize_entry_points(hostlib):
     from cosypose_amd import _lib, resize
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'cosyhip.h').read_text(), flags=re.S)
     for name in ('cosy_resize_ksize', 'cosy_resize_coeffs', 'cosy_resize_workspace_bytes', 'cosy_resize_u8'):
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in _lib.EXPORTS and hasattr(hostlib, name), name
-    for name, value in resize.FILTERS.items():
-        assert re.search(r'COSY_RESIZE_' + name.upper() + r' = ' + str(value) + r'\b', header), name
+        assert name in _lib.EXPORTS, name           # test_c_abi.py: EXPORTS, the header and the built library name the same entry points,
+                                                    # the COSY_RESIZE_* values and cosy_resize_item_t field by field
     assert resize.FILTERS == resize_ref.FILTERS
-    fields = re.search(r'typedef struct cosy_resize_item \{(.*?)\}', header, flags=re.S).group(1)
-    assert re.findall(r'\b(src|h|w|hb|hk|hks|vb|vk|vks)\b', fields) == list(resize.ITEM_DTYPE.names) and resize.ITEM_DTYPE.itemsize == 40
     f = hostlib.cosy_resize_workspace_bytes
     f.restype, f.argtypes = ctypes.c_size_t, [ctypes.c_int] * 4
     assert f(64, 3, 500, 640) >= 64 * 3 * 500 * 640 and f(0, 3, 500, 640) == 0

@@ -130,14 +130,13 @@ def test_lazy_names():
 def test_abi_names_source_and_flags():
     """the entry point is declared in the header, listed in _lib.EXPORTS with as many arguments as the header names, and exported by the
     built library; its source file is compiled with contraction off"""
-    import ctypes
     from cosypose_amd import _lib
-    from cosypose_amd.build import build, LIB, SOURCES, FILE_FLAGS
+    from cosypose_amd.build import build, SOURCES, FILE_FLAGS
     header = open(os.path.join(os.path.dirname(_lib.__file__), '..', 'include', 'cosyhip.h')).read()
     build()
     name = 'cosy_msroi_align_backward'
     decl = re.search(r'\bint ' + name + r'\s*\(([^;]*)\);', header)
-    assert decl and name in _lib.EXPORTS and hasattr(ctypes.CDLL(LIB), name)
+    assert decl and name in _lib.EXPORTS           # test_c_abi.py: the library exports what EXPORTS names
     assert len(decl.group(1).split(',')) == len(_lib._SIGNATURES[name][0]) == 17
     src = open(os.path.join(os.path.dirname(_lib.__file__), 'csrc', 'kernels_detpre.hip')).read()
     assert re.search(r'\bint ' + name + r'\s*\(', src) and 'kernels_detpre.hip' in SOURCES and '-ffp-contract=off' in FILE_FLAGS['kernels_detpre.hip']
