@@ -172,6 +172,17 @@ def require_device(*tensors):
             raise CosyHipError('cosypose_amd runs on a ROCm device only (got a CPU tensor); there is no CPU fallback')
 
 
+def out_or_new(out, what, shape, dtype, device, empty=None):
+    """`out` (`what` in a refusal) if it is a contiguous `shape` `dtype` tensor on `device`; for None a new one from `empty` (torch.empty)"""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device) if empty is None else empty(shape, dtype, device)
+    require_device(out)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'{what} must be a contiguous {str(dtype)[6:]} tensor of shape {tuple(shape)} on {device}')
+    return out
+
+
 import collections as _collections
 
 _id_cache = _collections.OrderedDict()       # (device index, shape, bytes) -> int32 device tensor

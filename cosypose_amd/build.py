@@ -38,7 +38,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-u
 # kernels_dettrain.hip: the same for the matcher's IoU, the encode, the loss terms and the mask targets, which hold the CPU twin's bits: DESIGN section 23.
 # kernels_resize.hip: the same for its HOST routine, which computes Pillow's resampling coefficients in double (its kernels are integer only).
 # kernels_frames.hip: its kernel writes the fused operations of DESIGN section 18 as fmaf and must round every other product on its own.
-# kernels_detin.hip: the same for the fused operations of DESIGN section 25 and the one product of a box coordinate.
+# kernels_detin.hip: the same for the fused operations of DESIGN section 25 and the one product of a box coordinate (csrc/image_device.h,
+# which states those operations once, is compiled by both).
 FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['-ffp-contract=off'], 'kernels_frames.hip': ['-ffp-contract=off'], 'kernels_detin.hip': ['-ffp-contract=off'], 'kernels_bop.hip': ['-ffp-contract=off'], 'kernels_gt.hip': ['-ffp-contract=off'], 'kernels_models.hip': ['-ffp-contract=off'], 'kernels_det.hip': ['-ffp-contract=off'], 'kernels_detpost.hip': ['-ffp-contract=off'], 'kernels_detpre.hip': ['-ffp-contract=off'], 'kernels_dettrain.hip': ['-ffp-contract=off'], 'kernels_wave.hip': ['-fno-slp-vectorize'], 'kernels_dw.hip': ['-fno-slp-vectorize'], 'kernels_stem.hip': ['-fno-slp-vectorize'], 'kernels_smx.hip': ['-fno-slp-vectorize']}   # kernels_dw.hip: see its header
 
 

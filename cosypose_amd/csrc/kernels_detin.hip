@@ -3,11 +3,11 @@
 // and to the targets of training: boxes scaled, masks resized through nearest.  For uint8 frames, read in place through their strides.
 // DESIGN.md section 25 states the arithmetic; tests/detin_ref.py is its numpy twin.
 //
-// Everything that divides is computed on the host (cosypose_amd/detector_input.py, numpy float32 and Python doubles) and arrives in one
-// table: the 3 x 256 values p_c(u) = ((float32(u) / 255f) - mean_c) / std_c, per axis and output index i0, i1, l0, l1 (the two taps and
-// their float32 weights) and the nearest source index, the two box ratios of a frame in its descriptor.  The kernel does the three fused
-// multiply-adds and the three lone products of section 25 and nothing else in floating point: fmaf and __fmul_rn, so that nothing is
-// contracted or reassociated.  Scalar float32 only.
+// Everything that divides is computed on the host (cosypose_amd/detector_input.py, numpy float32 and Python doubles) and arrives in the one
+// table of section 18: the 3 x 256 values p_c(u) = ((float32(u) / 255f) - mean_c) / std_c at its head, the axes' tap and nearest tables, the
+// mask planes' units; the two box ratios of a frame ride in its descriptor.  The tap load, the two-tap sample, the nearest gather, the byte
+// store and the rules for a descriptor's table offsets are image_device.h's, shared with kernels_frames.hip.  In floating point the kernel does
+// section 18's three fused multiply-adds and three lone products, one product per box coordinate, and nothing else.  Scalar float32 only.
 //
 // One launch over a batch of frames of ANY sizes and all their masks: blockIdx.z < n is the image of frame z, every later z one mask
 // plane named by the unit table.  A thread of an image unit owns DI_PX horizontally adjacent columns of one row of the PADDED image in all
@@ -17,14 +17,13 @@
 // frame's boxes.  A thread of a mask unit owns DI_PX adjacent bytes and stores them as one dword where the address allows.  Every
 // workgroup takes its branches uniformly, the barrier behind the load of p into LDS included.
 #include "cosy_common.h"
+#include "image_device.h"
 
 namespace cosy {
 namespace {
 
-constexpr int DI_THREADS = 256, DI_LANES = 32, DI_ROWS = DI_THREADS / DI_LANES, DI_PX = 4, DI_TILE_W = DI_LANES * DI_PX;
+constexpr int DI_THREADS = 256, DI_LANES = 32, DI_ROWS = DI_THREADS / DI_LANES, DI_PX = IMG_PX, DI_TILE_W = DI_LANES * DI_PX;
 constexpr int DI_LUT = 3 * 256;
-
-__host__ __device__ __forceinline__ int di_clamp(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
 
 // what both sides ask of a descriptor before anything is read or written through it: -> 0, or the number of the rule it breaks
 __host__ __device__ inline int detin_item_fault(const cosy_detin_item_t& it, int Hp, int Wp, long n_tables) {
@@ -34,26 +33,15 @@ __host__ __device__ inline int detin_item_fault(const cosy_detin_item_t& it, int
     if (it.sc < 0 || it.sy < 0 || it.sx < 0 || it.n_masks < 0 || it.n_boxes < 0) return 4;
     const bool one_tap = (it.flags & COSY_DETIN_ONE_TAP) && it.nh == it.h && it.nw == it.w;
     if (!one_tap) {
-        if (it.xb < 0 || it.yb < 0 || (long)it.xb + 4L * it.nw > n_tables || (long)it.yb + 4L * it.nh > n_tables) return 5;
-        if ((it.xb | it.yb) & 3) return 6;                    // the tap tables are read as 16-byte entries
+        if (!table_inside(it.xb, 4L * it.nw, n_tables) || !table_inside(it.yb, 4L * it.nh, n_tables)) return 5;
+        if (!tap_table_aligned(it.xb) || !tap_table_aligned(it.yb)) return 6;
     }
     if (it.n_masks > 0) {
         if (it.masks == nullptr || it.masks_out == nullptr) return 7;
-        if (it.xn < 0 || it.yn < 0 || (long)it.xn + it.nw > n_tables || (long)it.yn + it.nh > n_tables) return 8;
+        if (!nearest_table_ok(it.xn, it.nw, n_tables) || !nearest_table_ok(it.yn, it.nh, n_tables)) return 8;
     }
     if (it.n_boxes > 0 && (it.boxes == nullptr || it.boxes_out == nullptr)) return 9;
     return 0;
-}
-
-// the valid bytes of px[] to p: one dword where all four are there and p is 4-byte aligned
-__device__ __forceinline__ void store_px4(unsigned char* p, const unsigned* px, int n_valid) {
-    if (n_valid == DI_PX && ((uintptr_t)p & 3) == 0) {
-        *reinterpret_cast<unsigned*>(p) = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < DI_PX; ++j)
-        if (j < n_valid) p[j] = (unsigned char)px[j];
 }
 
 // the valid floats of v[] to p: one 16-byte vector where all four are there and p is 16-byte aligned
@@ -94,11 +82,8 @@ __global__ __launch_bounds__(DI_THREADS) void detector_input_kernel(const cosy_d
         if (y >= it.nh || x0 >= it.nw) return;
         const int n_valid = it.nw - x0 < DI_PX ? it.nw - x0 : DI_PX;
         const unsigned char* src = it.masks + (size_t)plane * it.h * it.w;
-        const unsigned char* row = src + (size_t)di_clamp(tables[it.yn + y], it.h - 1) * it.w;
         unsigned px[DI_PX] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int j = 0; j < DI_PX; ++j)
-            if (j < n_valid) px[j] = row[di_clamp(tables[it.xn + x0 + j], it.w - 1)];
+        gather_nearest(src + (size_t)clamp_index(tables[it.yn + y], it.h - 1) * it.w, tables, it.xn + x0, it.w, n_valid, px);
         store_px4(it.masks_out + ((size_t)plane * it.nh + y) * it.nw + x0, px, n_valid);
         return;
     }
@@ -127,23 +112,19 @@ __global__ __launch_bounds__(DI_THREADS) void detector_input_kernel(const cosy_d
                 }
             }
         } else {
-            const int4 ty = *reinterpret_cast<const int4*>(tables + it.yb + 4 * (size_t)y);
-            const unsigned char* r0 = it.frame + (size_t)di_clamp(ty.x, it.h - 1) * it.sy;
-            const unsigned char* r1 = it.frame + (size_t)di_clamp(ty.y, it.h - 1) * it.sy;
-            const float ly0 = __int_as_float(ty.z), ly1 = __int_as_float(ty.w);
+            const AxisTap ty = load_tap(tables, it.yb, y, it.h);
+            const unsigned char* r0 = it.frame + (size_t)ty.i0 * it.sy;
+            const unsigned char* r1 = it.frame + (size_t)ty.i1 * it.sy;
 #pragma unroll
             for (int j = 0; j < DI_PX; ++j) {
                 if (x0 + j < it.nw) {
-                    const int4 tx = *reinterpret_cast<const int4*>(tables + it.xb + 4 * (size_t)(x0 + j));
-                    const size_t xa = (size_t)di_clamp(tx.x, it.w - 1) * it.sx, xb = (size_t)di_clamp(tx.y, it.w - 1) * it.sx;
-                    const float lx0 = __int_as_float(tx.z), lx1 = __int_as_float(tx.w);
+                    const AxisTap tx = load_tap(tables, it.xb, x0 + j, it.w);
+                    const size_t xa = (size_t)tx.i0 * it.sx, xb = (size_t)tx.i1 * it.sx;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         const size_t oc = (size_t)c * it.sc;
                         const float* p = p_of + c * 256;
-                        const float top = fmaf(lx0, p[r0[oc + xa]], __fmul_rn(lx1, p[r0[oc + xb]]));
-                        const float bot = fmaf(lx0, p[r1[oc + xa]], __fmul_rn(lx1, p[r1[oc + xb]]));
-                        v[c][j] = fmaf(ly0, top, __fmul_rn(ly1, bot));
+                        v[c][j] = two_tap(tx, ty, p[r0[oc + xa]], p[r0[oc + xb]], p[r1[oc + xa]], p[r1[oc + xb]]);
                     }
                 }
             }

@@ -3,36 +3,24 @@
 // centres (F.interpolate, align_corners=False) and a truncating cast to bytes, the instance mask through nearest.  DESIGN.md section 18
 // states the arithmetic; tests/frames_ref.py is its numpy twin.
 //
-// Everything that divides is computed on the host (cosypose_amd/frames.py, numpy float32) and arrives in one table: per axis and output
-// index i0, i1, l0, l1 (the two taps and their float32 weights) and the nearest source index, and the 256 values float32(u) / 255f.  The
-// kernel does the three fused multiply-adds and the three lone products of section 18 and nothing else in floating point: fmaf and
-// __fmul_rn, so that nothing is contracted or reassociated.  Scalar float32 only.
+// Everything that divides is computed on the host (cosypose_amd/frames.py, numpy float32) and arrives in the one table of section 18,
+// the 256 values float32(u) / 255f at its head.  The tap load, the two-tap sample, the nearest gather, the byte store and the test of a
+// descriptor's table offsets are image_device.h's, shared with kernels_detin.hip.  In floating point the kernel does section 18's three
+// fused multiply-adds and four lone products and nothing else: fmaf and __fmul_rn, nothing contracted or reassociated.  Scalar float32 only.
 //
 // One launch over a batch of frames of ANY sizes (a per-frame descriptor names the sources and the tables of its two axes).  A thread
 // owns FR_PX horizontally adjacent output bytes of one plane and stores them as one dword where the address allows; it reads its row's
 // taps and weights once.  blockIdx.z = frame * 4 + plane: planes 0-2 are the image's channels, plane 3 is the mask.  Every workgroup
 // takes its branches uniformly.  A frame already at (H, W) is copied.  No workspace: both passes are two-tap.
 #include "cosy_common.h"
+#include "image_device.h"
 
 namespace cosy {
 namespace {
 
-constexpr int FR_THREADS = 256, FR_LANES = 32, FR_ROWS = FR_THREADS / FR_LANES, FR_PX = 4, FR_TILE_W = FR_LANES * FR_PX;
+constexpr int FR_THREADS = 256, FR_LANES = 32, FR_ROWS = FR_THREADS / FR_LANES, FR_PX = IMG_PX, FR_TILE_W = FR_LANES * FR_PX;
 constexpr int FR_PLANES = 4;                                 // three channels and the mask
 constexpr int FR_LUT = 256;
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
-
-// the valid bytes of px[] to p: one dword where all four are there and p is 4-byte aligned
-__device__ __forceinline__ void store_px4(unsigned char* p, const unsigned* px, int n_valid) {
-    if (n_valid == FR_PX && ((uintptr_t)p & 3) == 0) {
-        *reinterpret_cast<unsigned*>(p) = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < FR_PX; ++j)
-        if (j < n_valid) p[j] = (unsigned char)px[j];
-}
 
 __global__ __launch_bounds__(FR_THREADS) void resize_frames_kernel(const cosy_frame_item_t* __restrict__ items, int H, int W,
                                                                    const int* __restrict__ tables, long n_tables, int lut,
@@ -46,11 +34,9 @@ __global__ __launch_bounds__(FR_THREADS) void resize_frames_kernel(const cosy_fr
     // a descriptor the kernel cannot serve leaves its frame of the outputs untouched and nothing is read through it
     if (src == nullptr || it.h < 1 || it.w < 1 || (is_mask && out_masks == nullptr)) return;
     const bool copy = it.h == H && it.w == W;
-    if (!copy) {
-        const long xo = is_mask ? it.xn : it.xb, yo = is_mask ? it.yn : it.yb, per = is_mask ? 1 : 4;
-        if (xo < 0 || yo < 0 || xo + per * W > n_tables || yo + per * H > n_tables) return;
-        if (!is_mask && ((xo | yo) & 3)) return;              // the tap tables are read as 16-byte entries
-    }
+    if (!copy && !(is_mask ? nearest_table_ok(it.xn, W, n_tables) && nearest_table_ok(it.yn, H, n_tables)
+                           : tap_table_ok(it.xb, W, n_tables) && tap_table_ok(it.yb, H, n_tables)))
+        return;
     const bool interpolate = !copy && !is_mask;
     if (interpolate) {                                        // block-uniform: every thread of the workgroup reaches the barrier
         p_of[threadIdx.x] = __int_as_float(tables[lut + threadIdx.x]);
@@ -61,37 +47,24 @@ __global__ __launch_bounds__(FR_THREADS) void resize_frames_kernel(const cosy_fr
     if (y >= H || x0 >= W) return;
     const int n_valid = W - x0 < FR_PX ? W - x0 : FR_PX;
     unsigned px[FR_PX] = {0u, 0u, 0u, 0u};
-    unsigned char* dst;
-    if (is_mask) {
-        dst = out_masks + ((size_t)i * H + y) * W + x0;
-        const int sy = copy ? y : clampi(tables[it.yn + y], it.h - 1);
-        const unsigned char* row = src + (size_t)sy * it.w;
+    const unsigned char* img = is_mask ? src : src + (size_t)plane * it.h * it.w;            // this plane of the source
+    unsigned char* dst = is_mask ? out_masks + ((size_t)i * H + y) * W + x0 : out_images + (((size_t)i * 3 + plane) * H + y) * W + x0;
+    if (copy) {
 #pragma unroll
         for (int j = 0; j < FR_PX; ++j)
-            if (j < n_valid) px[j] = row[copy ? x0 + j : clampi(tables[it.xn + x0 + j], it.w - 1)];
+            if (j < n_valid) px[j] = img[(size_t)y * W + x0 + j];
+    } else if (is_mask) {
+        gather_nearest(img + (size_t)clamp_index(tables[it.yn + y], it.h - 1) * it.w, tables, it.xn + x0, it.w, n_valid, px);
     } else {
-        dst = out_images + (((size_t)i * 3 + plane) * H + y) * W + x0;
-        const unsigned char* img = src + (size_t)plane * it.h * it.w;
-        if (copy) {
+        const AxisTap ty = load_tap(tables, it.yb, y, it.h);
+        const unsigned char* r0 = img + (size_t)ty.i0 * it.w;
+        const unsigned char* r1 = img + (size_t)ty.i1 * it.w;
 #pragma unroll
-            for (int j = 0; j < FR_PX; ++j)
-                if (j < n_valid) px[j] = img[(size_t)y * W + x0 + j];
-        } else {
-            const int4 ty = *reinterpret_cast<const int4*>(tables + it.yb + 4 * (size_t)y);
-            const unsigned char* r0 = img + (size_t)clampi(ty.x, it.h - 1) * it.w;
-            const unsigned char* r1 = img + (size_t)clampi(ty.y, it.h - 1) * it.w;
-            const float ly0 = __int_as_float(ty.z), ly1 = __int_as_float(ty.w);
-#pragma unroll
-            for (int j = 0; j < FR_PX; ++j) {
-                if (j < n_valid) {
-                    const int4 tx = *reinterpret_cast<const int4*>(tables + it.xb + 4 * (size_t)(x0 + j));
-                    const int xa = clampi(tx.x, it.w - 1), xb = clampi(tx.y, it.w - 1);
-                    const float lx0 = __int_as_float(tx.z), lx1 = __int_as_float(tx.w);
-                    const float top = fmaf(lx0, p_of[r0[xa]], __fmul_rn(lx1, p_of[r0[xb]]));
-                    const float bot = fmaf(lx0, p_of[r1[xa]], __fmul_rn(lx1, p_of[r1[xb]]));
-                    const float v = fmaf(ly0, top, __fmul_rn(ly1, bot));
-                    px[j] = (unsigned)(int)__fmul_rn(v, 255.0f) & 255u;       // (uint8) of the truncated product
-                }
+        for (int j = 0; j < FR_PX; ++j) {
+            if (j < n_valid) {
+                const AxisTap tx = load_tap(tables, it.xb, x0 + j, it.w);
+                const float v = two_tap(tx, ty, p_of[r0[tx.i0]], p_of[r0[tx.i1]], p_of[r1[tx.i0]], p_of[r1[tx.i1]]);
+                px[j] = (unsigned)(int)__fmul_rn(v, 255.0f) & 255u;           // (uint8) of the truncated product
             }
         }
     }

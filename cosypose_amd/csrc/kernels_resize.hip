@@ -5,8 +5,8 @@
 // Host: cosy_resize_coeffs computes, in double and with one rounding per operation, the bounds (first tap, number of taps) and the 2^-22
 // integer coefficients of every output index of one axis.  The file is compiled with contraction off (the pragma below and
 // -ffp-contract=off in build.FILE_FLAGS): a fused multiply-add in the filter polynomial gives other coefficients.
-// Device: integer arithmetic only, two launches over a batch of images of ANY sizes (a per-image descriptor table names the source and the
-// tables of its two axes):
+// Device: integer arithmetic only, two launches over a batch of images of ANY sizes (a per-image descriptor names the source and, by offsets
+// into one int32 table, the bounds and coefficients of its two axes; cosypose_amd/_tables.py packs both):
 //   resize_rows_kernel   the horizontal pass, items -> workspace as BYTES (or -> out for an image that has no vertical pass)
 //   resize_cols_kernel   the vertical pass, workspace -> out (or items -> out where there was no horizontal pass; an image already at
 //                        (H, W) is copied through the same loop with one tap of weight 2^22)

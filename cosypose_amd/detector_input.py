@@ -25,7 +25,8 @@ import types
 import numpy as np
 
 from . import _lib
-from .frames import axis_tables
+from ._tables import TablePacker
+from .frames import axis_offsets
 
 F32 = np.float32
 # cosy_detin_item_t
@@ -200,27 +201,10 @@ def detector_input(frames, targets=None, min_size=480, max_size=640, image_mean=
     device = tensors[0].device
     if any(t.device != device for t in tensors):
         raise ValueError('the frames live on one device')
-    if out is None:
-        out = _empty((B, 3, Hp, Wp), torch.float32, device)
-    else:
-        _lib.require_device(out)
-        if out.dtype != torch.float32 or tuple(out.shape) != (B, 3, Hp, Wp) or not out.is_contiguous() or out.device != device:
-            raise ValueError(f'out must be a contiguous float32 tensor of shape {(B, 3, Hp, Wp)} on {device}')
+    out = _lib.out_or_new(out, 'out', (B, 3, Hp, Wp), torch.float32, device, _empty)
 
-    # one table: the 3 x 256 pixel values, then the tables of every axis this call uses, then the mask planes' units; one descriptor per
-    # frame with its offsets (in ints)
-    offsets, parts, at = {}, [table.reshape(-1).view(np.int32)], table.size
-
-    def place(n_in, n_out):
-        nonlocal at
-        key = (n_in, n_out)
-        if key not in offsets:
-            taps, nearest = axis_tables(n_in, n_out)
-            pad = -nearest.size % 4                          # tap tables start at a multiple of 4 ints: they are read as 16-byte entries
-            offsets[key] = (at, at + taps.size)
-            parts.extend((taps.reshape(-1), nearest, np.zeros(pad, np.int32)))
-            at += taps.size + nearest.size + pad
-        return offsets[key]
+    # one table: the 3 x 256 pixel values, the tap and nearest tables of every axis used, the mask planes' units; one descriptor per frame
+    packer = TablePacker(table)
 
     # p00 alone holds the bits of the three fused operations at scale 1 unless a table entry is -0.0 (0 * p01 may be -0.0 and p00 + -0.0 is
     # p00 for every p00 but -0.0 + +0.0): such a table, which no positive std gives, takes the general path
@@ -234,7 +218,7 @@ def detector_input(frames, targets=None, min_size=480, max_size=640, image_mean=
         if plain and (nh, nw) == (h, w):
             it['flags'] = ONE_TAP
         else:
-            (it['xb'], it['xn']), (it['yb'], it['yn']) = place(w, nw), place(h, nh)
+            (it['xb'], it['xn']), (it['yb'], it['yn']) = axis_offsets(packer, w, nw), axis_offsets(packer, h, nh)
     if tgt is not None:
         for i, (b, m) in enumerate(tgt):
             _lib.require_device(b, m)
@@ -268,21 +252,11 @@ def detector_input(frames, targets=None, min_size=480, max_size=640, image_mean=
                     it['masks'], it['masks_out'], it['n_masks'] = m.data_ptr(), new['masks'].data_ptr(), G
                     units.extend((i, g) for g in range(G))   # the nearest tables of a resized frame are placed already
             new_targets.append(new)
-    units = np.asarray(units, np.int32).reshape(-1)
-    units_at = at
-    parts.append(units)
-    at += units.size
-    if at >= 2 ** 31:
-        raise ValueError('the tables of this call exceed 2^31 entries')
-    tables = np.concatenate(parts)
-    items_bytes = items.nbytes                               # a multiple of 128: the tables behind the descriptors stay 16-byte aligned
-    blob = np.zeros(items_bytes + tables.nbytes, np.uint8)
-    blob[:items_bytes] = items.view(np.uint8)
-    blob[items_bytes:] = tables.view(np.uint8)
-    blob_d = _lib.host_to_device(blob, device)
+    units_at = packer.append(np.asarray(units, np.int32))
+    blob_d, items_p, tables_p, n_tables = packer.upload(items, device)
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().cosy_detector_input(items.ctypes.data, blob_d.data_ptr(), B, Hp, Wp, blob_d.data_ptr() + items_bytes, int(tables.size), 0,
-                                                 units_at, units.size // 2, _lib.ptr(out), _lib.stream()))
+        _lib.check(_lib.lib().cosy_detector_input(items.ctypes.data, items_p, B, Hp, Wp, tables_p, n_tables, 0, units_at, len(units), _lib.ptr(out),
+                                                 _lib.stream()))
     del keep
     return DetectorInput(out, nets, (Hp, Wp), originals, new_targets)
 

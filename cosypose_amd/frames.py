@@ -18,6 +18,7 @@ import functools
 import numpy as np
 
 from . import _lib
+from ._tables import TablePacker
 
 F32 = np.float32
 # cosy_frame_item_t
@@ -54,6 +55,12 @@ def axis_tables(n_in, n_out):
     taps.setflags(write=False)
     nearest.setflags(write=False)
     return taps, nearest
+
+
+def axis_offsets(packer, n_in, n_out):
+    """-> offsets of (tap table, nearest table) of an axis in a _tables.TablePacker, placed on first use, the taps' a multiple of 4 ints"""
+    key = (n_in, n_out)
+    return packer.offsets.get(key) or packer.place(key, *axis_tables(n_in, n_out), align_ints=4)
 
 
 def resized_K(K, h, w, H, W):
@@ -111,15 +118,6 @@ def _planes(what, value, dim, torch):
     return [t.contiguous() for t in planes]
 
 
-def _out(out, what, shape, device, torch):
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=device)
-    _lib.require_device(out)
-    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
-        raise ValueError(f'{what} must be a contiguous uint8 tensor of shape {tuple(shape)} on {device}')
-    return out
-
-
 def resize_frames(images, resize=(640, 480), masks=None, K=None, boxes=False, out=None, out_masks=None):
     """images: a list of (3,h_i,w_i) uint8 device tensors whose sizes may differ, or one (N,3,h,w) tensor.  masks: a list of (h_i,w_i)
     uint8 device tensors or one (N,h,w), or None.  K: (N,3,3), tensor on either side or numpy, or None.  (H, W) = (min(resize),
@@ -153,44 +151,23 @@ def resize_frames(images, resize=(640, 480), masks=None, K=None, boxes=False, ou
         K_host = (K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).astype(F32)
         if K_host.shape != (n, 3, 3):
             raise ValueError(f'K must be ({n},3,3), got {K_host.shape}')
-    out = _out(out, 'out', (n, 3, H, W), device, torch)
+    out = _lib.out_or_new(out, 'out', (n, 3, H, W), torch.uint8, device)
     if mask_planes is not None:
-        out_masks = _out(out_masks, 'out_masks', (n, H, W), device, torch)
+        out_masks = _lib.out_or_new(out_masks, 'out_masks', (n, H, W), torch.uint8, device)
 
-    # one table: the 256 byte values, then the tables of every axis this call uses; one descriptor per frame with its offsets (in ints)
-    offsets, parts, at = {}, [byte_values()], 256
-
-    def place(n_in, n_out):
-        nonlocal at
-        key = (n_in, n_out)
-        if key not in offsets:
-            taps, nearest = axis_tables(n_in, n_out)
-            pad = -nearest.size % 4                          # tap tables start at a multiple of 4 ints: they are read as 16-byte entries
-            offsets[key] = (at, at + taps.size)
-            parts.extend((taps.reshape(-1), nearest, np.zeros(pad, np.int32)))
-            at += taps.size + nearest.size + pad
-        return offsets[key]
-
+    # one table: the 256 byte values, then the tap and nearest tables of every axis this call uses; one descriptor per frame with their offsets
+    packer = TablePacker(byte_values())
     items = np.zeros(n, ITEM_DTYPE)
     items['image'] = [t.data_ptr() for t in frames]
     if mask_planes is not None:
         items['mask'] = [m.data_ptr() for m in mask_planes]
     items['h'], items['w'] = zip(*sizes)
     resized = [s != (H, W) for s in sizes]
-    for i, (h, w) in enumerate(sizes):
-        if resized[i]:
-            (items['xb'][i], items['xn'][i]), (items['yb'][i], items['yn'][i]) = place(w, W), place(h, H)
-    if at >= 2 ** 31:
-        raise ValueError('the tables of this call exceed 2^31 entries')
-    tables = np.concatenate(parts)
-    items_bytes = -(-items.nbytes // 16) * 16                # the tables behind the descriptors stay 16-byte aligned
-    blob = np.zeros(items_bytes + tables.nbytes, np.uint8)
-    blob[:items.nbytes] = items.view(np.uint8)
-    blob[items_bytes:] = tables.view(np.uint8)
-    blob_d = _lib.host_to_device(blob, device)
+    at = {(h, w): axis_offsets(packer, w, W) + axis_offsets(packer, h, H) for h, w in dict.fromkeys(sizes) if (h, w) != (H, W)}
+    items['xb'], items['xn'], items['yb'], items['yn'] = zip(*(at.get(s, (0, 0, 0, 0)) for s in sizes))
+    blob_d, items_p, tables_p, n_tables = packer.upload(items, device)
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().cosy_resize_frames_u8(blob_d.data_ptr(), n, H, W, blob_d.data_ptr() + items_bytes, int(tables.size), 0, _lib.ptr(out),
-                                                   _lib.ptr(out_masks), _lib.stream()))
+        _lib.check(_lib.lib().cosy_resize_frames_u8(items_p, n, H, W, tables_p, n_tables, 0, _lib.ptr(out), _lib.ptr(out_masks), _lib.stream()))
         stats = None
         if boxes:
             from .mask_ops import mask_instance_stats

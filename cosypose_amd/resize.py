@@ -16,6 +16,7 @@ import functools
 import numpy as np
 
 from . import _lib
+from ._tables import TablePacker
 
 FILTERS = {'bilinear': _lib.RESIZE_BILINEAR, 'bicubic': _lib.RESIZE_BICUBIC}
 # cosy_resize_item_t
@@ -66,7 +67,7 @@ def resize_images(images, size, resample='bicubic', out=None):
         planes = list(batch.unbind(0)) if batch.shape[0] else []
         device = batch.device
         if batch.shape[0] == 0 and C in (1, 3):
-            return _empty_or_out(out, (0, C, H, W), device)
+            return _lib.out_or_new(out, 'out', (0, C, H, W), torch.uint8, device)
     else:
         planes = list(images)
         _lib.require_device(*planes, out)
@@ -79,7 +80,7 @@ def resize_images(images, size, resample='bicubic', out=None):
             _lib.require_device(out)
             if out.dim() != 4 or out.shape[1] not in (1, 3):
                 raise ValueError('out must be a contiguous uint8 tensor of the shape and device of the result')
-            return _empty_or_out(out, (0, out.shape[1], H, W), out.device)
+            return _lib.out_or_new(out, 'out', (0, out.shape[1], H, W), torch.uint8, out.device)
         C, device = planes[0].shape[0], planes[0].device
         if any(t.shape[0] != C for t in planes) or any(t.device != device for t in planes):
             raise ValueError('the images of a list have the same number of channels and live on one device')
@@ -89,50 +90,30 @@ def resize_images(images, size, resample='bicubic', out=None):
     if any(t.shape[1] < 1 or t.shape[2] < 1 for t in planes):
         raise ValueError('an image without pixels cannot be resized')
     n = len(planes)
-    out = _empty_or_out(out, (n, C, H, W), device)
+    out = _lib.out_or_new(out, 'out', (n, C, H, W), torch.uint8, device)
 
     # one table of all the axes this call uses, and one descriptor per image with its offsets into it (in ints)
-    offsets, parts, at = {}, [], 0
+    packer = TablePacker(what='coefficient tables')
 
-    def place(n_in, n_out):
-        nonlocal at
+    def axis(n_in, n_out):
         if n_in == n_out:
             return 0, 0, 0                                   # ksize 0: the pass is skipped
-        key = (n_in, n_out)
-        if key not in offsets:
-            bounds, k = axis_tables(n_in, n_out, resample)
-            offsets[key] = (at, at + bounds.size, k.shape[1])
-            parts.extend((bounds.reshape(-1), k.reshape(-1)))
-            at += bounds.size + k.size
-        return offsets[key]
+        bounds, k = axis_tables(n_in, n_out, resample)
+        return (*packer.place((n_in, n_out), bounds, k), k.shape[1])
 
     items = np.zeros(n, ITEM_DTYPE)
     items['src'] = [t.data_ptr() for t in planes]
-    items['h'], items['w'] = [t.shape[1] for t in planes], [t.shape[2] for t in planes]
-    items['hb'], items['hk'], items['hks'] = zip(*(place(t.shape[2], W) for t in planes))
-    items['vb'], items['vk'], items['vks'] = zip(*(place(t.shape[1], H) for t in planes))
-    if at >= 2 ** 31:
-        raise ValueError('the coefficient tables of this call exceed 2^31 entries')
-    tables = np.concatenate(parts) if parts else np.zeros(0, np.int32)
-    n_tables = max(int(tables.size), 1)                      # never an empty upload: the library wants a table pointer
-    blob = np.zeros(items.nbytes + 4 * n_tables, np.uint8)
-    blob[:items.nbytes] = items.view(np.uint8)
-    blob[items.nbytes:items.nbytes + tables.nbytes] = tables.view(np.uint8)
-    blob_d = _lib.host_to_device(blob, device)
+    heights, widths = [t.shape[1] for t in planes], [t.shape[2] for t in planes]
+    rows, cols = {w: axis(w, W) for w in dict.fromkeys(widths)}, {h: axis(h, H) for h in dict.fromkeys(heights)}
+    items['h'], items['w'] = heights, widths
+    items['hb'], items['hk'], items['hks'] = zip(*(rows[w] for w in widths))
+    items['vb'], items['vk'], items['vks'] = zip(*(cols[h] for h in heights))
+    blob_d, items_p, tables_p, n_tables = packer.upload(items, device)
     max_h = max(t.shape[1] for t in planes)
     lib = _lib.lib()
     with torch.cuda.device(device):
         ws_bytes = lib.cosy_resize_workspace_bytes(n, C, max_h, W)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.cosy_resize_u8(blob_d.data_ptr(), n, C, H, W, max_h, blob_d.data_ptr() + items.nbytes, n_tables, _lib.ptr(out), _lib.ptr(ws),
-                                      ws_bytes, _lib.stream()))
+        _lib.check(lib.cosy_resize_u8(items_p, n, C, H, W, max_h, tables_p, n_tables, _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream()))
     return out
 
-
-def _empty_or_out(out, shape, device):
-    import torch
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
-        raise ValueError(f'out must be a contiguous uint8 tensor of shape {tuple(shape)} on {device}')
-    return out

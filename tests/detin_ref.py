@@ -47,30 +47,12 @@ def pixels(frame, table):
 
 def image(frame, nh, nw, table):
     """(3,h,w) uint8 -> (3,nh,nw) float32: the general path, whatever the sizes"""
-    _, h, w = frame.shape
-    p = pixels(frame, table)
-    y0, y1, ly0, ly1 = frames_ref.axis(h, nh)
-    x0, x1, lx0, lx1 = frames_ref.axis(w, nw)
-    lx0, lx1 = lx0[None, None, :], lx1[None, None, :]
-    ly0, ly1 = ly0[None, :, None], ly1[None, :, None]
-    p00, p01 = p[:, y0][:, :, x0], p[:, y0][:, :, x1]
-    p10, p11 = p[:, y1][:, :, x0], p[:, y1][:, :, x1]
-    top = frames_ref.fma32(lx0, p00, (lx1 * p01).astype(F32))
-    bot = frames_ref.fma32(lx0, p10, (lx1 * p11).astype(F32))
-    return frames_ref.fma32(ly0, top, (ly1 * bot).astype(F32))
+    return frames_ref.two_tap(pixels(frame, table), nh, nw)
 
 
 def image_float64(frame, nh, nw, table):
     """the same bilinear form with the twin's float32 weights and table, every product and sum in float64"""
-    _, h, w = frame.shape
-    p = pixels(frame, table).astype(np.float64)
-    y0, y1, ly0, ly1 = frames_ref.axis(h, nh)
-    x0, x1, lx0, lx1 = frames_ref.axis(w, nw)
-    lx0, lx1 = lx0.astype(np.float64)[None, None, :], lx1.astype(np.float64)[None, None, :]
-    ly0, ly1 = ly0.astype(np.float64)[None, :, None], ly1.astype(np.float64)[None, :, None]
-    top = lx0 * p[:, y0][:, :, x0] + lx1 * p[:, y0][:, :, x1]
-    bot = lx0 * p[:, y1][:, :, x0] + lx1 * p[:, y1][:, :, x1]
-    return ly0 * top + ly1 * bot
+    return frames_ref.two_tap_float64(pixels(frame, table), nh, nw)
 
 
 def _coordinate_slack(n_in, n_out):

@@ -304,18 +304,13 @@ class Call:
 
 
 def by_hand(frame_d, masks_d, boxes_d, nh, nw, masks_out, boxes_out, table):
-    """one item and its tables, laid out here and not by the package -> items (1,), tables, offset of the units"""
+    """one item and its tables, the twin's, in the package's layout -> items (1,), tables, offset of the units"""
+    from cosypose_amd._tables import TablePacker
     _, h, w = frame_d.shape
     G = int(masks_d.shape[0])
-    parts, at, place = [table.reshape(-1).view(np.int32)], 768, {}
-    for n_in, n_out in ((w, nw), (h, nh)):
-        taps, nearest = ref.axis_ints(n_in, n_out)
-        pad = -nearest.size % 4
-        place[n_in, n_out] = (at, at + taps.size)
-        parts += [taps.reshape(-1), nearest, np.zeros(pad, np.int32)]
-        at += taps.size + nearest.size + pad
-    units = np.array([(0, g) for g in range(G)], np.int32).reshape(-1)
-    parts.append(units)
+    packer = TablePacker(table)
+    place = {key: packer.place(key, *ref.axis_ints(*key), align_ints=4) for key in ((w, nw), (h, nh))}
+    units_at = packer.append(np.array([(0, g) for g in range(G)], np.int32))
     items = np.zeros(1, di.ITEM_DTYPE)
     it = items[0]
     it['frame'], it['sc'], it['sy'], it['sx'] = frame_d.data_ptr(), frame_d.stride(0), frame_d.stride(1), frame_d.stride(2)
@@ -323,7 +318,7 @@ def by_hand(frame_d, masks_d, boxes_d, nh, nw, masks_out, boxes_out, table):
     it['h'], it['w'], it['nh'], it['nw'], it['n_masks'], it['n_boxes'] = h, w, nh, nw, G, int(boxes_d.shape[0])
     (it['xb'], it['xn']), (it['yb'], it['yn']) = place[w, nw], place[h, nh]
     it['rw'], it['rh'] = f32(float(nw) / float(w)), f32(float(nh) / float(h))
-    return items, np.concatenate(parts), at
+    return items, np.concatenate(packer.parts), units_at
 
 
 def test_c_abi_by_hand_and_its_refusals():

@@ -124,6 +124,42 @@ def test_host_tables_equal_the_restatement():
         assert got.dtype == np.float32 and np.array_equal(got, frames_ref.K_resize(K, h, w, H, W))
 
 
+def test_table_packer_layout_is_pinned():
+    """the one buffer of a host-packed call (cosypose_amd/_tables.py), on 3 -> 2 and 5 -> 4 behind the 256 byte values: every offset as a
+    literal, the bytes of the buffer against the parts, the descriptor block rounded to 16 bytes"""
+    from cosypose_amd import frames
+    from cosypose_amd._tables import TablePacker
+    packer = TablePacker(frames.byte_values())
+    assert frames.axis_offsets(packer, 3, 2) == (256, 264) and packer.size == 268          # 8 tap ints, 2 nearest, 2 of padding
+    assert frames.axis_offsets(packer, 5, 4) == (268, 284) and packer.size == 288          # 16 tap ints, 4 nearest, none
+    assert frames.axis_offsets(packer, 3, 2) == (256, 264) and packer.size == 288          # a repeated key is placed once
+    assert packer.place('a', np.arange(3, dtype=np.int32), align_ints=4) == (288,) and packer.size == 292
+    assert packer.append(np.array([(0, 0), (0, 1), (2, 0)], np.int32)) == 292 and packer.size == 298      # the detector's units: no padding
+    assert packer.place('b', np.zeros((2, 4), np.int32), np.zeros(2, np.int32), align_ints=4) == (300, 308) and packer.size == 312
+    assert all(at % 4 == 0 for at in (256, 268, 300))                                      # every tap table at a multiple of 4 ints
+    (t32, n32), (t54, n54) = frames.axis_tables(3, 2), frames.axis_tables(5, 4)
+    want = np.concatenate([frames.byte_values(), t32.reshape(-1), n32, [0, 0], t54.reshape(-1), n54, [0, 1, 2, 0], [0, 0, 0, 1, 2, 0], np.zeros(14)])
+    assert want.size == 312
+    for n, at in ((1, 48), (2, 80), (3, 128), (4, 160)):                                   # descriptors of 40 bytes
+        items = np.zeros(n, frames.ITEM_DTYPE)
+        items['h'], items['w'], items['image'] = 3 + np.arange(n), 5, 0x0102030405060708
+        blob, tables_at, n_tables = packer.blob(items)
+        assert (tables_at, n_tables) == (at, 312) and tables_at % 16 == 0
+        assert blob.dtype == np.uint8 and blob.size == at + 4 * 312
+        assert blob[:40 * n].tobytes() == items.tobytes() and not blob[40 * n:at].any()
+        assert blob[at:].tobytes() == want.astype(np.int32).tobytes()
+    # no head, no padding asked for, as resize_images packs; and never an empty table: one zero stands for none
+    bare = TablePacker(what='coefficient tables')
+    assert bare.blob(np.zeros(1, frames.ITEM_DTYPE))[1:] == (48, 1) and bare.blob(np.zeros(1, frames.ITEM_DTYPE))[0].size == 52
+    assert bare.place((7, 5), np.ones((5, 2), np.int32), np.ones((5, 3), np.int32)) == (0, 10) and bare.size == 25
+    assert bare.place((9, 5), np.ones((5, 2), np.int32), np.ones((5, 4), np.int32)) == (25, 35) and bare.size == 55
+    assert bare.blob(np.zeros(2, frames.ITEM_DTYPE))[1:] == (80, 55)
+    for p, text in ((packer, r'the tables of this call exceed 2\^31 entries'), (bare, r'the coefficient tables of this call exceed 2\^31 entries')):
+        p.size = 2 ** 31
+        with pytest.raises(ValueError, match=text):
+            p.blob(np.zeros(1, frames.ITEM_DTYPE))
+
+
 def test_c_abi_exports_the_frames_entry_point():
     import cosypose_amd
     from cosypose_amd import _lib, build, frames

@@ -337,20 +337,14 @@ def frames_by_hand(sources, H, W):
     """items and tables as cosypose_amd.frames.resize_frames lays them out, for a list of (image, mask) device tensors of one size
     -> items (numpy, ITEM_DTYPE), tables (numpy int32: the 256 byte values first)"""
     from cosypose_amd import frames
+    from cosypose_amd._tables import TablePacker
     h, w = sources[0][0].shape[1:]
-    parts, at = [frames.byte_values()], 256
-    place = {}
-    for key in ((w, W), (h, H)):
-        taps, nearest = frames.axis_tables(*key)
-        pad = -nearest.size % 4
-        place[key] = (at, at + taps.size)
-        parts.extend((taps.reshape(-1), nearest, np.zeros(pad, np.int32)))
-        at += taps.size + nearest.size + pad
+    packer = TablePacker(frames.byte_values())
     items = np.zeros(len(sources), frames.ITEM_DTYPE)
     items['image'], items['mask'] = [im.data_ptr() for im, _ in sources], [m.data_ptr() for _, m in sources]
     items['h'], items['w'] = h, w
-    (items['xb'], items['xn']), (items['yb'], items['yn']) = place[w, W], place[h, H]
-    return items, np.concatenate(parts)
+    (items['xb'], items['xn']), (items['yb'], items['yn']) = frames.axis_offsets(packer, w, W), frames.axis_offsets(packer, h, H)
+    return items, np.concatenate(packer.parts)
 
 
 def upload(items, tables, shift_items=0, shift_tables=0):
