@@ -86,6 +86,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('DetectorHeads', 'HeadLayer', 'conv_layer'):
         from . import detector_heads
         return getattr(detector_heads, name)
+    if name in ('DetectorTrunk', 'Detector', 'TrunkLayer', 'trunk_conv_layer'):
+        from . import detector_trunk
+        return getattr(detector_trunk, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

@@ -1034,6 +1034,25 @@ int cosy_head_max_tile_rows(void);
 int cosy_head_pack(const float* in, void* rows, int B, int C, int HW, int dtype, cosy_stream_t stream);
 int cosy_head_conv(const cosy_head_layer_t* layer, cosy_stream_t stream);
 
+/* ---- the detector's trunk on the matrix pipe: the ResNet body and the FPN as the heads' implicit GEMM (inference only) ----  DESIGN.md
+ * section 27 holds the contract.  Rows, weights (fragment order), summation order, tiles and stores are those of cosy_head_conv.
+ * cosy_trunk_conv: layer->H / W / row_start describe the INPUT maps; the output maps are Ho = (H - 1) / stride + 1, Wo likewise, and the launch
+ *   owns the B Ho Wo output cells.  ksize 1 or 3 (pad ksize / 2), stride 1 or 2 (2: one level).  Output cell (y, x) reads the input cells
+ *   (stride y + dy, stride x + dx); a tap outside the map feeds +0.0 and its address is never formed.
+ *   Epilogue per output, in this order: v = fmaf(acc, scale[c], bias[c]) (scale NULL: acc + bias[c]; scale is padded like bias);
+ *   residual != NULL: v = v + r, one rounded add; relu: x < 0 ? 0 : x (a NaN stays NaN); the conversion to the store's type.
+ *   residual: rows of c_out channels of `dtype` on maps of res_H x res_W per image (one level, c_out a multiple of 8); output cell (y, x) takes
+ *   the cell (min(floor(y sy), res_H - 1), min(floor(x sx), res_W - 1)) with sy = (float)res_H / Ho and the product in float32: torch's legacy
+ *   mode='nearest' (res_H == Ho: the identity).
+ *   store: COSY_HEAD_STORE_ROWS, or COSY_HEAD_STORE_NCHW with n_split == c_out; anything else is refused (COSY_EINVAL), as is what
+ *   cosy_head_conv refuses.  M = 0 returns COSY_OK and launches nothing.  No atomics: equal inputs give equal bits.
+ * cosy_trunk_stem_pack: images (B,3,H,W) contiguous float32 -> rows (B Ho Wo, 152) of `dtype` for the 7x7 stride-2 pad-3 stem: element
+ *   (ky 7 + kx) 3 + c of output cell (y, x) is images[b, c, 2y - 3 + ky, 2x - 3 + kx], +0.0 outside the image; elements 147..151 are +0.0.
+ * cosy_trunk_maxpool: rows (B H W, C) -> rows (B Ho Wo, C): max_pool2d(3, 2, 1), padding -inf, v > m || isnan(v) takes v.  C a multiple of 8. */
+int cosy_trunk_conv(const cosy_head_layer_t* layer, int stride, const float* scale, const void* residual, int res_H, int res_W, cosy_stream_t stream);
+int cosy_trunk_stem_pack(const float* images, void* rows, int B, int H, int W, int dtype, cosy_stream_t stream);
+int cosy_trunk_maxpool(const void* x, void* out, int B, int H, int W, int C, int dtype, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
