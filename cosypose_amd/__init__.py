@@ -83,7 +83,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('detections_from_frames', 'detector_losses_from_frames', 'DetectorInput'):
         from . import detector_input
         return getattr(detector_input, name)
-    if name in ('DetectorHeads', 'HeadLayer', 'conv_layer'):
+    if name in ('DetectorHeads', 'HeadLayer', 'conv_layer', 'TrainableLayer', 'layer_backward'):
         from . import detector_heads
         return getattr(detector_heads, name)
     if name in ('DetectorTrunk', 'Detector', 'TrunkLayer', 'trunk_conv_layer'):

@@ -43,9 +43,21 @@ struct conv_epi_t {
 template <int STRIDE_, bool TRUNK_> struct ConvPolicy {
     static constexpr int STRIDE = STRIDE_;
     static constexpr bool TRUNK = TRUNK_;
+    static constexpr bool GRAD = false, TAPS2 = false;
     typedef typename std::conditional<TRUNK_, conv_epi_t, no_epi_t>::type epi_t;
 };
 typedef ConvPolicy<1, false> HeadPolicy;
+
+// The data gradient of a head layer is the same GEMM over the transposed, tap-flipped weight: the rows are the upstream
+// gradient, no bias is added, and a row store may apply the ReLU mask of the layer below: y <= 0 ? +0.0 : v with y that layer's stored rows
+// (torch's threshold_backward: a NaN y passes v).  TAPS2: the four taps (dy, dx) = (0..1, 0..1) at stride 2, pad 0 -- the data gradient of
+// ConvTranspose2d(2, 2); the rows of the launch are the cells of the (H / 2, W / 2) map and no tap ever leaves the (H, W) map.
+struct grad_epi_t { const float* y; };       // rows (M, c_out) float32, or null
+template <bool TAPS2_> struct GradPolicy {
+    static constexpr int STRIDE = TAPS2_ ? 2 : 1;
+    static constexpr bool TRUNK = false, GRAD = true, TAPS2 = TAPS2_;
+    typedef grad_epi_t epi_t;
+};
 
 template <typename T> __device__ __forceinline__ typename DT<T>::raw_t zero_frag() {
     typename DT<T>::raw_t z;
@@ -94,7 +106,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void conv_gemm_kernel(const cosy_head
     const int C_in = a.c_in, N = a.c_out;
     const T* __restrict__ x = (const T*)a.x;
     const frag_t* __restrict__ w = (const frag_t*)a.w;
-    const int taps = a.ksize == 3 ? 9 : 1;
+    const int taps = P::TAPS2 ? 4 : a.ksize == 3 ? 9 : 1;
     const long S = (long)taps * KBn;                           // k-steps of one output
 
     // this lane's pixel of every row tile: the B operand's column and the result's column alike.  pH, pW: the INPUT map (the taps' bounds);
@@ -129,7 +141,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void conv_gemm_kernel(const cosy_head
 
     for (int kb = 0; kb < KBn; ++kb) {
         for (int tap = 0; tap < taps; ++tap) {
-            const int dy = taps == 9 ? tap / 3 - 1 : 0, dx = taps == 9 ? tap - (tap / 3) * 3 - 1 : 0;
+            const int dy = P::TAPS2 ? tap >> 1 : taps == 9 ? tap / 3 - 1 : 0, dx = P::TAPS2 ? tap & 1 : taps == 9 ? tap - (tap / 3) * 3 - 1 : 0;
             const long s = (long)tap * KBn + kb;
             frag_t xf[MT], wf[NT];
 #pragma unroll
@@ -188,6 +200,11 @@ __global__ __launch_bounds__(HEAD_THREADS) void conv_gemm_kernel(const cosy_head
                     if (e.residual != nullptr) v[q] = v[q] + res[q];
                     if (a.relu) v[q] = relu_keep_nan(v[q]);
                 }
+            } else if constexpr (P::GRAD) {
+                float yv[4] = {1.f, 1.f, 1.f, 1.f};
+                if (a.store == COSY_HEAD_STORE_ROWS && e.y != nullptr) load4(e.y + (long)r[mt] * N + col0, yv);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = yv[q] <= 0.f ? 0.f : acc[mt][nt][q];
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -197,7 +214,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void conv_gemm_kernel(const cosy_head
             }
             if (a.store == COSY_HEAD_STORE_ROWS) {             // N is a multiple of 8: the four channels exist
                 put4((T*)a.out + (long)r[mt] * N + col0, v);
-            } else if (!P::TRUNK && (a.store == COSY_HEAD_STORE_DECONV_ROWS || a.store == COSY_HEAD_STORE_DECONV_NCHW)) {
+            } else if (!P::TRUNK && !P::GRAD && (a.store == COSY_HEAD_STORE_DECONV_ROWS || a.store == COSY_HEAD_STORE_DECONV_NCHW)) {
                 const int o = col0 >> 2, Co = N >> 2;          // the lane's four columns: (o, dy, dx), dy, dx = 0, 1
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {

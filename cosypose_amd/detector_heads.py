@@ -1,6 +1,7 @@
 """The detector's heads on the matrix pipe: Mask R-CNN's RPN head, box head + predictor and mask head + predictor (torchvision 0.4.2), the
-convolutions and linears between the FPN and detector.detections_from_heads.  Inference only: training keeps the torch modules and autograd
-(detector_train.detector_losses).  DESIGN.md section 26 states the contract; HIP: csrc/kernels_dethead.hip (cosy_head_pack, cosy_head_conv).
+convolutions and linears between the FPN and detector.detections_from_heads.  By default inference only (HIP: csrc/kernels_dethead.hip, cosy_head_pack and
+cosy_head_conv).  DetectorHeads(..., trainable=True) are float32 heads with parameters and a backward on the same matrix pipe, behind autograd
+(HIP: csrc/kernels_detheadbwd.hip); the trunk's backward is not built.
 
 Every layer is one implicit GEMM over ROWS: a row is one cell (level, image, y, x) with its channels contiguous in the storage type (float32,
 float16 or bfloat16; a linear layer's row is its input vector).  The heads' inputs arrive as contiguous NCHW float32 (what the FPN and
@@ -115,6 +116,114 @@ class HeadLayer:
         return layer
 
 
+def _pad8(n):
+    return -(-n // 8) * 8
+
+
+def transposed_weight(kind, weight):
+    """a parameter in torchvision's layout (CPU) -> (C_in, taps, O) float32, the weight of the data gradient's GEMM: rows c, reduction o;
+    conv: the taps in reverse order (the gradient at cell - tap meets tap); deconv (C_in, O, 2, 2): the four taps (dy, dx) ascending.
+    pack_weight(transposed_weight(...), torch.float32) is the host statement of what cosy_head_weight_pack writes as `bwd`."""
+    w = weight.detach().to(device='cpu', dtype=torch.float32)
+    if kind == 'linear':
+        return w.t().reshape(w.shape[1], 1, w.shape[0])
+    if kind == 'conv':
+        return w.flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], w.shape[2] * w.shape[3], w.shape[0])
+    if kind == 'deconv':
+        return w.permute(0, 2, 3, 1).reshape(w.shape[0], 4, w.shape[1])
+    raise ValueError(f'kind must be conv, linear or deconv, got {kind}')
+
+
+class TrainableLayer:
+    """A layer of trainable heads, float32: its parameters are torch.nn.Parameters on the device in torchvision's layout
+    (one (weight, bias) pair, or the two siblings of one GEMM); w / bias (what cosy_head_conv reads) and w_t (the transposed, tap-flipped
+    packing the data gradient reads) are written by cosy_head_weight_pack on the device, when a parameter has moved since the last pack.
+    kind, ksize, relu, c_in, c_out, n_out as HeadLayer; grad_ksize: 3, 1, or 2 for the deconvolution; n_grad: the outputs o of the gradient
+    rows (deconv: C_o, else c_out)."""
+    dtype = torch.float32
+
+    def __init__(self, kind, pairs, relu, device, counter=None):
+        if device is None or torch.device(device).type != 'cuda':
+            raise ValueError(f'trainable heads live on the ROCm device: give device=, got {device}')
+        self.kind, self.relu, self.device = kind, bool(relu), torch.device(device)
+        self.counter = counter if counter is not None else [0]
+        self.pairs = []
+        for w, b in pairs:
+            if b is None:
+                b = torch.zeros(w.shape[1] if kind == 'deconv' else w.shape[0])
+            self.pairs.append(tuple(p if isinstance(p, torch.nn.Parameter) and p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+                                    else torch.nn.Parameter(p.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()) for p in (w, b)))
+        w0 = self.pairs[0][0]
+        self.device = w0.device                                   # 'cuda' resolved to the device the parameters landed on
+        dims = {'conv': 4, 'linear': 2, 'deconv': 4}[kind]
+        for w, b in self.pairs:
+            if w.dim() != dims or b.dim() != 1:
+                raise ValueError(f'a {kind} layer takes a {dims}-d weight and a 1-d bias, got {tuple(w.shape)} and {tuple(b.shape)}')
+        if kind == 'deconv':
+            if tuple(w0.shape[2:]) != (2, 2) or len(self.pairs) != 1:
+                raise ValueError(f'a deconv layer is one ConvTranspose2d(k=2, s=2), got a kernel of {tuple(w0.shape[2:])}')
+            self.c_in, self.n_grad, self.ksize, self.grad_ksize = int(w0.shape[0]), int(w0.shape[1]), 1, 2
+            self.c_out, self.n_out = 4 * self.n_grad, self.n_grad
+            if self.n_grad % 8:
+                raise ValueError(f'a trainable deconv layer has a multiple of 8 output channels, got {self.n_grad}')
+        else:
+            k = int(w0.shape[2]) if kind == 'conv' else 1
+            if k not in (1, 3) or (kind == 'conv' and w0.shape[3] != k):
+                raise ValueError(f'a conv layer is 3x3 or 1x1, got a kernel of {tuple(w0.shape[2:])}')
+            if any(tuple(w.shape[1:]) != tuple(w0.shape[1:]) for w, _ in self.pairs):
+                raise ValueError(f'sibling layers read the same input, got weights {[tuple(w.shape) for w, _ in self.pairs]}')
+            self.c_in, self.ksize, self.grad_ksize = int(w0.shape[1]), k, k
+            self.c_out = self.n_out = self.n_grad = sum(int(w.shape[0]) for w, _ in self.pairs)
+        for w, b in self.pairs:
+            if int(b.shape[0]) != int(w.shape[1] if kind == 'deconv' else w.shape[0]):
+                raise ValueError(f'bias must be ({int(w.shape[1] if kind == "deconv" else w.shape[0])}), got {tuple(b.shape)}')
+        if self.c_in < 8 or self.c_in % 8:
+            raise ValueError(f'{kind} layer: the reduction length {self.c_in} must be a positive multiple of 8 (it is not padded silently)')
+        if len(self.pairs) == 2:
+            self.n_split = int(w0.shape[0])
+        C, O = self.c_in, self.n_grad
+        taps, gtaps = (9 if self.ksize == 3 else 1), {1: 1, 3: 9, 2: 4}[self.grad_ksize]
+        NP = -(-self.c_out // 64) * 64
+        self.w = torch.empty(NP * taps * (-(-C // 16) * 16), dtype=torch.float32, device=self.device)
+        self.bias = torch.empty(NP, dtype=torch.float32, device=self.device)
+        self.w_t = torch.empty((-(-C // 64) * 64) * gtaps * (-(-O // 16) * 16), dtype=torch.float32, device=self.device)
+        self.versions = None
+
+    def parameters(self):
+        return [p for pair in self.pairs for p in pair]
+
+    def refresh(self, dev=None):
+        """pack on the device when a parameter's _version (or its storage) has moved since the last pack, and not otherwise"""
+        if dev is not None and torch.device(dev) != self.device:
+            raise ValueError(f'the input lives on {dev}, the parameters on {self.device}: build the heads with device={dev!s}')
+        now = tuple((p._version, p.data_ptr()) for p in self.parameters())
+        if now != self.versions:
+            (w0, b0), (w1, b1) = self.pairs[0], (self.pairs[1] if len(self.pairs) == 2 else (None, None))
+            n0 = int(w0.shape[1] if self.kind == 'deconv' else w0.shape[0])
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().cosy_head_weight_pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0,
+                                                            _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
+            self.versions = now
+            self.counter[0] += 1
+        return self
+
+    @classmethod
+    def conv(cls, weight, bias=None, relu=False, device=None, counter=None):
+        return cls('conv', [(weight, bias)], relu, device, counter)
+
+    @classmethod
+    def linear(cls, weight, bias=None, relu=False, device=None, counter=None):
+        return cls('linear', [(weight, bias)], relu, device, counter)
+
+    @classmethod
+    def deconv(cls, weight, bias=None, relu=False, device=None, counter=None):
+        return cls('deconv', [(weight, bias)], relu, device, counter)
+
+    @classmethod
+    def siblings(cls, first, second, kind, device=None, counter=None):
+        return cls(kind, [tuple(first), tuple(second)], False, device, counter)
+
+
 # ---- launches ------------------------------------------------------------------------------------------------------------------------
 def _check_input(x, name, dims, channels, what):
     """the style of detector_rpn: a ValueError that names the argument, before anything touches the library"""
@@ -129,11 +238,11 @@ def _check_input(x, name, dims, channels, what):
     return x
 
 
-def _on_device(x, name):
+def _on_device(x, name, trainable=False):
     """after every shape and dtype check, before anything touches the library"""
     if not x.is_cuda:
         raise ValueError(f'{name} must live on the ROCm device (got a CPU tensor); there is no CPU fallback')
-    if torch.is_grad_enabled() and x.requires_grad:
+    if torch.is_grad_enabled() and x.requires_grad and not trainable:
         raise RuntimeError(f'{name} requires grad: DetectorHeads is inference only, training keeps the torch.nn modules and autograd '
                            '(detector_train.detector_losses); call it under torch.no_grad() or detach the input')
     return x.contiguous()
@@ -142,6 +251,8 @@ def _on_device(x, name):
 def _ready(layer, dev):
     """the layer's weights on the input's device: a layer packed without a device is uploaded on its first use and stays there; a layer
     that lives on another device is refused (a silent re-upload would move the weights under another stream's feet)"""
+    if isinstance(layer, TrainableLayer):
+        return layer.refresh(dev)
     if layer.w is None:
         layer.w, layer.bias, layer.device = layer.packed.to(dev), layer.packed_bias.to(dev), dev
     elif layer.w.device != dev:
@@ -181,7 +292,7 @@ def _gemm(layer, x_rows, maps, store, out, out1=None, n_split=None):
 def conv_layer(x, layer):
     """One layer through the kernel.  conv: x (B,C,H,W) -> (B,N,H,W); linear: x (M,K) -> (M,N); deconv: x (B,C,H,W) -> (B,N/4,2H,2W).
     x float32, contiguous, on the device; the result is float32 NCHW.  x is rounded to the layer's storage type on the way in."""
-    if not isinstance(layer, HeadLayer):
+    if not isinstance(layer, (HeadLayer, TrainableLayer)):
         raise ValueError(f'layer must be a HeadLayer, got {type(layer).__name__}')
     if layer.kind == 'linear':
         x = _on_device(_check_input(x, 'x', 2, layer.c_in, '(M,K)'), 'x')
@@ -206,15 +317,207 @@ def conv_layer(x, layer):
     return _gemm(layer, rows, [(B, H, W)], _lib.HEAD_STORE_NCHW, torch.empty((B, layer.c_out, H, W), dtype=torch.float32, device=dev))
 
 
+# ---- backward: float32 rows, the gradient g of a layer is taken at its PRE-activation output ---------------------
+def wgrad_slab_rows(M):
+    """cells of one slab of the weight gradient of M cells (the library's; tests sit on its edges)"""
+    return int(_lib.lib().cosy_head_wgrad_slab_rows(int(M)))
+
+
+def _describe(d, maps):
+    d.n_levels = len(maps)
+    row = 0
+    for l, (n, H, W) in enumerate(maps):
+        d.row_start[l], d.H[l], d.W[l] = row, H, W
+        row += n * H * W
+        if row > MAX_ROWS:
+            raise ValueError(f'{row} rows (cells of all maps) exceed the limit of 2^30 per launch')
+    d.row_start[len(maps)] = row
+    return row
+
+
+def _grad_pack(g0, g1, rows, B, n0, n1, HW):
+    """NCHW float32 gradients of a sibling pair (or of one tensor, n1 = 0; None: zeros) -> rows (B HW, pad8(n0 + n1)), one launch"""
+    for g, n in ((g0, n0), (g1, n1)):
+        if g is not None and (g.dtype != torch.float32 or g.numel() != B * n * HW or not g.is_cuda):
+            raise ValueError(f'a gradient of {B} x {n} x {HW} float32 values on the device was expected, got {tuple(g.shape)} {g.dtype} on {g.device}')
+    if B:
+        _lib.check(_lib.lib().cosy_head_grad_pack(_lib.ptr(None if g0 is None else g0.contiguous()), _lib.ptr(None if g1 is None else g1.contiguous()),
+                                                  _lib.ptr(rows), B, n0, n1, HW, _lib.stream()))
+    return rows
+
+
+def _dgrad(layer, g_rows, maps, store, out, y=None):
+    """the data gradient of layer from its gradient rows; maps: those of g_rows.  y: the stored rows of the layer below (the ReLU mask)"""
+    d = _lib.HeadLayer()
+    d.x, d.w, d.out = _lib.ptr(g_rows), _lib.ptr(layer.w_t), _lib.ptr(out)
+    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[torch.float32], layer.grad_ksize, int(g_rows.shape[1]), layer.c_in, 0, store
+    d.n_split = layer.c_in
+    if _describe(d, maps):
+        _lib.check(_lib.lib().cosy_head_dgrad(ctypes.byref(d), _lib.ptr(y), _lib.stream()))
+    return out
+
+
+def _wgrad(layer, x_rows, g_rows, maps):
+    """-> [dW, db] per parameter pair of layer, float32 in the parameters' own layout; maps: those of x_rows"""
+    d = _lib.HeadLayer()
+    d.x = _lib.ptr(x_rows)
+    d.dtype, d.ksize, d.c_in, d.c_out = _DTYPES[torch.float32], layer.grad_ksize, layer.c_in, layer.n_grad
+    d.n_split = getattr(layer, 'n_split', layer.n_grad)
+    M = _describe(d, maps)
+    out = [torch.empty_like(p) for p in layer.parameters()]
+    need = int(_lib.lib().cosy_head_wgrad_workspace_bytes(M, layer.grad_ksize, layer.c_in, layer.n_grad))
+    if M and not need:
+        raise ValueError(f'the weight gradient of {M} rows, c_in={layer.c_in}, c_out={layer.n_grad} does not fit the library\'s limits')
+    ws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=layer.device)
+    _lib.check(_lib.lib().cosy_head_wgrad(ctypes.byref(d), _lib.ptr(g_rows), *[_lib.ptr(t) for t in (out + [None, None])[:4]], _lib.ptr(ws), need, _lib.stream()))
+    return out
+
+
+def layer_backward(layer, x, grad, need_dx=True):
+    """One TrainableLayer's backward through the kernels.  x as conv_layer takes it; grad: the gradient at the layer's PRE-activation output,
+    float32 with the shape of conv_layer's result (the layer's own ReLU is not applied: in a head the launch above masks).
+    -> dX (float32, the shape of x; None without need_dx), [dW, db (, dW, db of the second sibling)] in the parameters' layout"""
+    if not isinstance(layer, TrainableLayer):
+        raise ValueError(f'layer must be a TrainableLayer, got {type(layer).__name__}')
+    linear = layer.kind == 'linear'
+    x = _on_device(_check_input(x, 'x', 2 if linear else 4, layer.c_in, '(M,K)' if linear else '(B,C,H,W)'), 'x', True).detach()
+    dev = x.device
+    _ready(layer, dev)
+    B, C, H, W = (int(v) for v in x.shape) if not linear else (int(x.shape[0]), layer.c_in, 1, 1)
+    up = 2 if layer.kind == 'deconv' else 1
+    want = (B, layer.n_out) if linear else (B, layer.n_out, up * H, up * W)
+    if not torch.is_tensor(grad) or tuple(grad.shape) != want or grad.dtype != torch.float32 or not grad.is_cuda:
+        raise ValueError(f'grad must be a float32 tensor of shape {want} on the device')
+    rows = x if linear else torch.empty((B * H * W, C), dtype=torch.float32, device=dev)
+    if not linear:
+        _pack(x, rows, B, C, H * W, torch.float32)
+    g = _grad_pack(grad.detach(), None, torch.empty((B * up * H * up * W, _pad8(layer.n_out)), dtype=torch.float32, device=dev), B, layer.n_out, 0, up * H * up * W)
+    grads = _wgrad(layer, rows, g, [(B, H, W)])
+    dx = None
+    if need_dx:
+        dx = _dgrad(layer, g, [(B, up * H, up * W)], _lib.HEAD_STORE_NCHW, torch.empty_like(x))
+    return dx, grads
+
+
+def _wants_grad(head, inputs):
+    return head.trainable and torch.is_grad_enabled() and any(t.requires_grad for t in list(inputs) + head.parameters())
+
+
+def _once(name):
+    if torch.is_grad_enabled():
+        raise RuntimeError(f'DetectorHeads.{name}: double backward is not built (the backward of the heads\' backward has no kernel); '
+                           'call backward() without create_graph')
+
+
+def _g(t):
+    return None if t is None else t.contiguous()
+
+
+class _RpnFn(torch.autograd.Function):
+    """rpn_head as one node: forward = RpnHead._forward's launches; backward = per level one gradient pack, then for the sibling 1x1 GEMM and
+    the 3x3 conv the weight gradient and the data gradient (the first masked by the stored hidden rows, the second stored NCHW per level)"""
+
+    @staticmethod
+    def forward(ctx, head, L, *tensors):
+        keep = {}
+        obj, dlt = head._forward(list(tensors[:L]), keep)
+        ctx.head, ctx.keep, ctx.L = head, keep, L
+        return tuple(obj) + tuple(dlt)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _once('rpn_head')
+        head, k, L = ctx.head, ctx.keep, ctx.L
+        maps, starts, A = k['maps'], k['starts'], head.A
+        M, dev = starts[-1], k['x'].device
+        g = torch.empty((M, _pad8(5 * A)), dtype=torch.float32, device=dev)
+        for l, (B, H, W) in enumerate(maps):
+            _grad_pack(_g(grads[l]), _g(grads[L + l]), g[starts[l]:starts[l + 1]], B, A, 4 * A, H * W)
+        d_pred = _wgrad(head.pred, k['hidden'], g, maps)
+        gh = _dgrad(head.pred, g, maps, _lib.HEAD_STORE_ROWS, torch.empty((M, head.conv.c_out), dtype=torch.float32, device=dev), y=k['hidden'])
+        d_conv = _wgrad(head.conv, k['x'], gh, maps)
+        dfeat = [None] * L
+        if any(ctx.needs_input_grad[2:2 + L]):
+            C = head.conv.c_in
+            flat = _dgrad(head.conv, gh, maps, _lib.HEAD_STORE_NCHW, torch.empty(C * M, dtype=torch.float32, device=dev))
+            dfeat = [flat[C * starts[l]:C * starts[l + 1]].view(B, C, H, W) if ctx.needs_input_grad[2 + l] else None for l, (B, H, W) in enumerate(maps)]
+        return (None, None) + tuple(dfeat) + tuple(d_conv) + tuple(d_pred)
+
+
+class _BoxFn(torch.autograd.Function):
+    """box_head as one node: the predictors, fc7 and fc6 backwards, each a weight gradient and a data gradient masked by the rows below"""
+
+    @staticmethod
+    def forward(ctx, head, flat, *params):
+        keep = {}
+        out = head._forward(flat, keep)
+        ctx.head, ctx.keep = head, keep
+        return out
+
+    @staticmethod
+    def backward(ctx, g_logits, g_boxes):
+        _once('box_head')
+        head, k = ctx.head, ctx.keep
+        maps, K, x = k['maps'], head.K, k['x']
+        R, dev = int(x.shape[0]), x.device
+        new = lambda n: torch.empty((R, n), dtype=torch.float32, device=dev)
+        g = _grad_pack(_g(g_logits), _g(g_boxes), new(_pad8(5 * K)), R, K, 4 * K, 1)
+        d_pred = _wgrad(head.pred, k['h7'], g, maps)
+        g7 = _dgrad(head.pred, g, maps, _lib.HEAD_STORE_ROWS, new(head.fc7.c_out), y=k['h7'])
+        d_fc7 = _wgrad(head.fc7, k['h6'], g7, maps)
+        g6 = _dgrad(head.fc7, g7, maps, _lib.HEAD_STORE_ROWS, new(head.fc6.c_out), y=k['h6'])
+        d_fc6 = _wgrad(head.fc6, x, g6, maps)
+        dx = _dgrad(head.fc6, g6, maps, _lib.HEAD_STORE_NCHW, new(head.fc6.c_in)) if ctx.needs_input_grad[1] else None
+        return (None, dx) + tuple(d_fc6) + tuple(d_fc7) + tuple(d_pred)
+
+
+class _MaskFn(torch.autograd.Function):
+    """mask_head as one node: the 1x1 logits, the deconvolution (four stride-2 taps) and the four 3x3 convs, last to first"""
+
+    @staticmethod
+    def forward(ctx, head, x, *params):
+        keep = {}
+        out = head._forward(x, keep)
+        ctx.head, ctx.keep, ctx.shape = head, keep, tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        _once('mask_head')
+        head, k = ctx.head, ctx.keep
+        (D, H, W), = k['maps']
+        maps, maps2, rows, up, dev = k['maps'], [(D, 2 * H, 2 * W)], k['rows'], k['up'], k['up'].device
+        M, K = D * H * W, head.logits.c_out
+        new = lambda m, n: torch.empty((m, n), dtype=torch.float32, device=dev)
+        g = _grad_pack(_g(g_out), None, new(4 * M, _pad8(K)), D, K, 0, 4 * H * W)
+        d_logits = _wgrad(head.logits, up, g, maps2)
+        g_up = _dgrad(head.logits, g, maps2, _lib.HEAD_STORE_ROWS, new(4 * M, head.deconv.n_out), y=up)
+        d_deconv = _wgrad(head.deconv, rows[-1], g_up, maps)
+        g_cur = _dgrad(head.deconv, g_up, maps2, _lib.HEAD_STORE_ROWS, new(M, head.deconv.c_in), y=rows[-1])
+        d_convs, dx = [], None
+        for i in range(len(head.convs) - 1, -1, -1):
+            layer = head.convs[i]
+            d_convs = _wgrad(layer, rows[i], g_cur, maps) + d_convs
+            if i:
+                g_cur = _dgrad(layer, g_cur, maps, _lib.HEAD_STORE_ROWS, new(M, layer.c_in), y=rows[i])
+            elif ctx.needs_input_grad[1]:
+                dx = _dgrad(layer, g_cur, maps, _lib.HEAD_STORE_NCHW, torch.empty(ctx.shape, dtype=torch.float32, device=dev))
+        return (None, dx) + tuple(d_convs) + tuple(d_deconv) + tuple(d_logits)
+
+
 # ---- the three heads -----------------------------------------------------------------------------------------------------------------
 class RpnHead:
     """rpn_head(features) -> (objectness, bbox_deltas): per level (B,A,H,W) and (B,4A,H,W) float32, views of two flat buffers"""
 
     def __init__(self, conv, pred):
         self.conv, self.pred = conv, pred
+        self.trainable = isinstance(conv, TrainableLayer)
         self.A = pred.n_split
         if pred.c_out != 5 * self.A:
             raise ValueError(f'rpn.head.bbox_pred must have 4 x the {self.A} outputs of cls_logits, got {pred.c_out - self.A}')
+
+    def parameters(self):
+        return self.conv.parameters() + self.pred.parameters() if self.trainable else []
 
     def __call__(self, features):
         if torch.is_tensor(features) or not isinstance(features, (list, tuple)):
@@ -227,7 +530,14 @@ class RpnHead:
             raise ValueError(f'every level must hold the same {B} images, got {[tuple(f.shape) for f in feats]}')
         if B and any(f.shape[2] < 1 or f.shape[3] < 1 for f in feats):
             raise ValueError(f'features must have at least one cell, got {[tuple(f.shape) for f in feats]}')
-        feats = [_on_device(f, f'features[{l}]') for l, f in enumerate(feats)]
+        feats = [_on_device(f, f'features[{l}]', self.trainable) for l, f in enumerate(feats)]
+        if _wants_grad(self, feats):
+            out = _RpnFn.apply(self, len(feats), *feats, *self.parameters())
+            return list(out[:len(feats)]), list(out[len(feats):])
+        return self._forward(feats)
+
+    def _forward(self, feats, keep=None):
+        B = int(feats[0].shape[0])
         dev = feats[0].device
         _ready(self.conv, dev), _ready(self.pred, dev)
         maps = [(B, int(f.shape[2]), int(f.shape[3])) for f in feats]
@@ -242,6 +552,8 @@ class RpnHead:
         obj = torch.empty(A * M, dtype=torch.float32, device=dev)
         dlt = torch.empty(4 * A * M, dtype=torch.float32, device=dev)
         _gemm(self.pred, hidden, maps, _lib.HEAD_STORE_NCHW, obj, dlt, n_split=A)
+        if keep is not None:
+            keep.update(x=x, hidden=hidden, maps=maps, starts=starts)
         return ([obj[A * starts[l]:A * starts[l + 1]].view(B, A, H, W) for l, (_, H, W) in enumerate(maps)],
                 [dlt[4 * A * starts[l]:4 * A * starts[l + 1]].view(B, 4 * A, H, W) for l, (_, H, W) in enumerate(maps)])
 
@@ -251,17 +563,26 @@ class BoxHead:
 
     def __init__(self, fc6, fc7, pred):
         self.fc6, self.fc7, self.pred = fc6, fc7, pred
+        self.trainable = isinstance(fc6, TrainableLayer)
         self.K = pred.n_split
         if pred.c_out != 5 * self.K:
             raise ValueError(f'box_predictor.bbox_pred must have 4 x the {self.K} outputs of cls_score, got {pred.c_out - self.K}')
         if fc7.c_in != fc6.c_out or pred.c_in != fc7.c_out:
             raise ValueError(f'box head widths do not chain: fc6 -> {fc6.c_out}, fc7 {fc7.c_in} -> {fc7.c_out}, predictors {pred.c_in}')
 
+    def parameters(self):
+        return self.fc6.parameters() + self.fc7.parameters() + self.pred.parameters() if self.trainable else []
+
     def __call__(self, roi_feats):
         if not torch.is_tensor(roi_feats) or roi_feats.dim() != 4:
             raise ValueError(f'roi_feats must be (R,C,P,P), got {tuple(roi_feats.shape) if torch.is_tensor(roi_feats) else type(roi_feats).__name__}')
         flat = roi_feats.contiguous().view(roi_feats.shape[0], int(roi_feats.shape[1] * roi_feats.shape[2] * roi_feats.shape[3]))      # torch's (c, y, x) order
-        flat = _on_device(_check_input(flat, 'roi_feats, flattened,', 2, self.fc6.c_in, '(R, C x P x P)'), 'roi_feats')
+        flat = _on_device(_check_input(flat, 'roi_feats, flattened,', 2, self.fc6.c_in, '(R, C x P x P)'), 'roi_feats', self.trainable)
+        if _wants_grad(self, [flat]):
+            return _BoxFn.apply(self, flat, *self.parameters())
+        return self._forward(flat)
+
+    def _forward(self, flat, keep=None):
         R, dev, K = int(flat.shape[0]), flat.device, self.K
         for layer in (self.fc6, self.fc7, self.pred):
             _ready(layer, dev)
@@ -275,6 +596,8 @@ class BoxHead:
         logits = torch.empty((R, K), dtype=torch.float32, device=dev)
         boxes = torch.empty((R, 4 * K), dtype=torch.float32, device=dev)
         _gemm(self.pred, h7, maps, _lib.HEAD_STORE_NCHW, logits, boxes, n_split=K)
+        if keep is not None:
+            keep.update(x=rows, h6=h6, h7=h7, maps=maps)
         return logits, boxes
 
 
@@ -283,6 +606,7 @@ class MaskHead:
 
     def __init__(self, convs, deconv, logits):
         self.convs, self.deconv, self.logits = list(convs), deconv, logits
+        self.trainable = isinstance(deconv, TrainableLayer)
         chain = self.convs + [deconv]
         for a, b in zip(chain[:-1], chain[1:]):
             if b.c_in != a.n_out:
@@ -290,21 +614,33 @@ class MaskHead:
         if logits.c_in != deconv.n_out:
             raise ValueError(f'mask head widths do not chain: {deconv.n_out} channels into mask_fcn_logits of {logits.c_in}')
 
+    def parameters(self):
+        return [p for layer in self.convs + [self.deconv, self.logits] for p in layer.parameters()] if self.trainable else []
+
     def __call__(self, roi_feats):
-        x = _on_device(_check_input(roi_feats, 'roi_feats', 4, self.convs[0].c_in, '(D,C,H,W)'), 'roi_feats')
+        x = _on_device(_check_input(roi_feats, 'roi_feats', 4, self.convs[0].c_in, '(D,C,H,W)'), 'roi_feats', self.trainable)
+        if x.shape[0] and x.shape[2] * x.shape[3] < 1:
+            raise ValueError(f'roi_feats must have at least one cell, got {tuple(x.shape)}')
+        if _wants_grad(self, [x]):
+            return _MaskFn.apply(self, x, *self.parameters())
+        return self._forward(x)
+
+    def _forward(self, x, keep=None):
         D, C, H, W = (int(v) for v in x.shape)
         dev = x.device
-        if D and H * W < 1:
-            raise ValueError(f'roi_feats must have at least one cell, got {tuple(x.shape)}')
         for layer in self.convs + [self.deconv, self.logits]:
             _ready(layer, dev)
         maps = [(D, H, W)]
         rows = _rows(D * H * W, C, self.convs[0], dev)
         _pack(x, rows, D, C, H * W, self.convs[0].dtype)
+        stored = [rows]
         for layer in self.convs:
             rows = _gemm(layer, rows, maps, _lib.HEAD_STORE_ROWS, _rows(D * H * W, layer.c_out, layer, dev))
+            stored.append(rows)
         up = _gemm(self.deconv, rows, maps, _lib.HEAD_STORE_DECONV_ROWS, _rows(4 * D * H * W, self.deconv.n_out, self.deconv, dev))
         out = torch.empty((D, self.logits.c_out, 2 * H, 2 * W), dtype=torch.float32, device=dev)
+        if keep is not None:
+            keep.update(rows=stored, up=up, maps=maps)
         return _gemm(self.logits, up, [(D, 2 * H, 2 * W)], _lib.HEAD_STORE_NCHW, out)
 
 
@@ -312,12 +648,16 @@ class DetectorHeads:
     """The three heads as callables with the signatures detector_rpn.detections_from_features documents: .rpn_head, .box_head, .mask_head
     (None without a mask branch).  Weights are packed once, here."""
 
-    def __init__(self, params, dtype=torch.float32, device=None):
-        """params: {key: (weight, bias)} under the names of a torchvision 0.4.2 Mask R-CNN state_dict, without the '.weight' / '.bias'"""
+    def __init__(self, params, dtype=torch.float32, device=None, trainable=False):
+        """params: {key: (weight, bias)} under the names of a torchvision 0.4.2 Mask R-CNN state_dict, without the '.weight' / '.bias'.
+        trainable: the parameters become torch.nn.Parameters on the device and the three heads autograd nodes (float32 only; see _init_trainable)"""
         dtype = _dtype(dtype)
         kw = dict(dtype=dtype, device=device)
         p = params
         self.dtype = dtype
+        self.trainable = bool(trainable)
+        if self.trainable:
+            return self._init_trainable(p, dtype, device)
         self.rpn_head = RpnHead(HeadLayer.conv(*p[RPN_KEYS[0]], relu=True, **kw), HeadLayer.siblings(p[RPN_KEYS[1]], p[RPN_KEYS[2]], 'conv', **kw))
         self.box_head = BoxHead(HeadLayer.linear(*p[BOX_KEYS[0]], relu=True, **kw), HeadLayer.linear(*p[BOX_KEYS[1]], relu=True, **kw),
                                 HeadLayer.siblings(p[BOX_KEYS[2]], p[BOX_KEYS[3]], 'linear', **kw))
@@ -325,6 +665,73 @@ class DetectorHeads:
         if MASK_KEYS[0] in p:
             self.mask_head = MaskHead([HeadLayer.conv(*p[k], relu=True, **kw) for k in MASK_KEYS[:4]], HeadLayer.deconv(*p[MASK_KEYS[4]], relu=True, **kw),
                                       HeadLayer.conv(*p[MASK_KEYS[5]], relu=False, **kw))
+
+    def _init_trainable(self, p, dtype, device):
+        """DESIGN.md section 28.  The parameters live on the device in torchvision's layout under torchvision's names (parameters(),
+        named_parameters(), state_dict(), load_state_dict(): a checkpoint's head keys go in and out as they are; torch.optim works on them).
+        Forward and backward read packings made on the device (cosy_head_weight_pack) when a parameter's _version has moved; pack_count counts
+        those launches.  rpn_head / box_head / mask_head are one autograd node each when grad is enabled and an input or a parameter requires
+        grad, and exactly the inference path otherwise."""
+        if dtype != torch.float32:
+            raise ValueError(f'trainable heads are float32 only (16-bit training and master weights are not built), got dtype={dtype}')
+        if device is None:
+            w = p[RPN_KEYS[0]][0]
+            device = w.device if torch.is_tensor(w) and w.is_cuda else None
+        self._counter = [0]
+        kw = dict(device=device, counter=self._counter)
+        T = TrainableLayer
+        self.rpn_head = RpnHead(T.conv(*p[RPN_KEYS[0]], relu=True, **kw), T.siblings(p[RPN_KEYS[1]], p[RPN_KEYS[2]], 'conv', **kw))
+        self.box_head = BoxHead(T.linear(*p[BOX_KEYS[0]], relu=True, **kw), T.linear(*p[BOX_KEYS[1]], relu=True, **kw),
+                                T.siblings(p[BOX_KEYS[2]], p[BOX_KEYS[3]], 'linear', **kw))
+        self.mask_head = None
+        named = [(RPN_KEYS[0], self.rpn_head.conv.pairs[0]), (RPN_KEYS[1], self.rpn_head.pred.pairs[0]), (RPN_KEYS[2], self.rpn_head.pred.pairs[1]),
+                 (BOX_KEYS[0], self.box_head.fc6.pairs[0]), (BOX_KEYS[1], self.box_head.fc7.pairs[0]), (BOX_KEYS[2], self.box_head.pred.pairs[0]),
+                 (BOX_KEYS[3], self.box_head.pred.pairs[1])]
+        if MASK_KEYS[0] in p:
+            self.mask_head = MaskHead([T.conv(*p[k], relu=True, **kw) for k in MASK_KEYS[:4]], T.deconv(*p[MASK_KEYS[4]], relu=True, **kw),
+                                      T.conv(*p[MASK_KEYS[5]], relu=False, **kw))
+            named += [(k, layer.pairs[0]) for k, layer in zip(MASK_KEYS, self.mask_head.convs + [self.mask_head.deconv, self.mask_head.logits])]
+        self._named = [(f'{k}.{part}', t) for k, pair in named for part, t in zip(('weight', 'bias'), pair)]
+
+    @property
+    def pack_count(self):
+        """device weight packs launched so far (trainable heads): one per layer whose parameters moved since its last pack"""
+        return self._counter[0]
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError(f'{what}: these DetectorHeads are inference only; build them with trainable=True')
+
+    def named_parameters(self):
+        self._need_trainable('named_parameters')
+        return list(self._named)
+
+    def parameters(self):
+        self._need_trainable('parameters')
+        return [t for _, t in self._named]
+
+    def state_dict(self):
+        """{torchvision's key: a detached copy of the parameter}"""
+        self._need_trainable('state_dict')
+        return {k: t.detach().clone() for k, t in self._named}
+
+    def load_state_dict(self, sd, strict=True):
+        """copies a Mask R-CNN state_dict's head keys into the parameters (in place: their _version moves, the next forward packs again); the
+        trunk's and the FPN's keys are ignored, a missing head key is a KeyError naming it (strict) or is left as it is"""
+        self._need_trainable('load_state_dict')
+        for k, t in self._named:
+            if k not in sd:
+                if strict:
+                    raise KeyError(k)
+                continue
+            if tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f'{k} must be {tuple(t.shape)}, got {tuple(sd[k].shape)}')
+            with torch.no_grad():
+                t.copy_(sd[k])
+
+    def zero_grad(self):
+        for t in self.parameters():
+            t.grad = None
 
     def layers(self):
         """every packed layer, in a fixed order (tests compare their bytes)"""
@@ -334,18 +741,20 @@ class DetectorHeads:
         return out
 
     @classmethod
-    def from_state_dict(cls, sd, dtype=torch.float32, device=None):
+    def from_state_dict(cls, sd, dtype=torch.float32, device=None, trainable=False):
         """a Mask R-CNN state_dict as it is: the trunk's and the FPN's keys are ignored, a missing head key is a KeyError naming it"""
+        if trainable and dtype != torch.float32:
+            raise ValueError(f'trainable heads are float32 only (16-bit training and master weights are not built), got dtype={dtype}')
         params = {}
         for k in RPN_KEYS + BOX_KEYS + MASK_KEYS:
             for part in ('weight', 'bias'):
                 if f'{k}.{part}' not in sd:
                     raise KeyError(f'{k}.{part}')
             params[k] = (sd[f'{k}.weight'], sd[f'{k}.bias'])
-        return cls(params, dtype, device)
+        return cls(params, dtype, device, trainable)
 
     @classmethod
-    def from_modules(cls, rpn_head, box_head, box_predictor, mask_head=None, mask_predictor=None, dtype=torch.float32, device=None):
+    def from_modules(cls, rpn_head, box_head, box_predictor, mask_head=None, mask_predictor=None, dtype=torch.float32, device=None, trainable=False):
         """the same from modules, duck-typed on torchvision's attribute names (conv, cls_logits, bbox_pred; fc6, fc7; cls_score, bbox_pred;
         mask_fcn1..4; conv5_mask, mask_fcn_logits)"""
         if (mask_head is None) != (mask_predictor is None):
@@ -363,4 +772,6 @@ class DetectorHeads:
         if device is None:
             device = rpn_head.conv.weight.device
             device = device if device.type != 'cpu' else None
-        return cls(params, dtype, device)
+        if trainable:           # parameters of the heads' own: a copy, never the modules' tensors
+            params = {k: tuple(None if t is None else t.detach().clone() for t in pair) for k, pair in params.items()}
+        return cls(params, dtype, device, trainable)

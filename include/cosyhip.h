@@ -1053,6 +1053,44 @@ int cosy_trunk_conv(const cosy_head_layer_t* layer, int stride, const float* sca
 int cosy_trunk_stem_pack(const float* images, void* rows, int B, int H, int W, int dtype, cosy_stream_t stream);
 int cosy_trunk_maxpool(const void* x, void* out, int B, int H, int W, int C, int dtype, cosy_stream_t stream);
 
+/* ---- the backward of the detector's heads on the matrix pipe, float32 only ----  DESIGN.md section 28 holds the contract.
+ * A head layer is y = act(W x + b) as cosy_head_conv runs it; g is the gradient at its PRE-activation output, as float32 rows
+ * (M, GP), GP = c_out rounded up to a multiple of 8, the pad columns +0.0.  ksize 1 / 3 as in cosy_head_conv; ksize 2 is
+ * ConvTranspose2d(k=2, s=2): x rows (B H W, C), g rows (B 2H 2W, C_o) over the (2H, 2W) map, C_o a multiple of 8.
+ * cosy_head_grad_pack: contiguous NCHW float32 (B, n0, HW) and (B, n1, HW) -> rows (B HW, GP), GP = (n0 + n1) rounded up to 8: the columns
+ *   of g0, then those of g1, then +0.0.  A NULL g0 or g1 is a tensor of zeros.  B = 0 launches nothing.
+ * cosy_head_dgrad: the data gradient dX[cell][c] = sum over (tap, o) of w[o][tap][c] g[cell - tap][o] as cosy_head_conv's GEMM, in its
+ *   summation order, with no bias add.  layer->x = the rows g, c_in = GP (the reduction length, a multiple of 8), c_out = the layer's input
+ *   channels (a multiple of 8), dtype COSY_F32, relu 0, bias unused, w = the transposed packing of cosy_head_weight_pack.
+ *   ksize 2: H / W / row_start describe the maps of g, (2H, 2W), one level, as cosy_trunk_conv's stride 2 does; the launch owns the B H W cells;
+ *   output cell (y, x) reads g at (2y + dy, 2x + dx), taps (dy, dx) ascending.
+ *   store COSY_HEAD_STORE_ROWS: out = rows (M, c_out) float32; y != NULL: the rows the layer BELOW stored in forward, same shape: out = y <= 0 ?
+ *   +0.0 : dX (torch's threshold_backward: a NaN y passes dX), i.e. the pre-activation gradient of that layer.
+ *   store COSY_HEAD_STORE_NCHW: float32 NCHW as cosy_head_conv's, n_split == c_out, y NULL.
+ * cosy_head_wgrad: dW[o][tap][c] = sum over cells of g[cell][o] x[cell + tap][c] (x = +0.0 outside its map, no address formed),
+ *   db[o] = sum over cells of g[cell][o], on v_mfma_f32_16x16x4_f32 with the cells as the k dimension.  layer->x = the rows the layer read in
+ *   forward, c_in, c_out (ksize 2: C_o), n_split, n_levels / row_start / H / W = the maps of x, dtype COSY_F32; w, bias, out, out1 unused.
+ *   The M cells are cut into slabs of cosy_head_wgrad_slab_rows(M) cells (a function of M alone); every slab writes a partial tile to the
+ *   workspace and a second pass adds the slabs in ascending order.  No atomics: equal inputs give equal bits.
+ *   Results, float32, in torchvision's layout: ksize 1 / 3: (O, C, k, k) (a linear layer: (N, K)), outputs [0, n_split) to dw0 / db0 and the
+ *   rest to dw1 / db1 (two sibling layers as one GEMM; n_split = c_out: dw1, db1 unused); ksize 2: dw0 (C, C_o, 2, 2), db0 (C_o).
+ *   workspace: cosy_head_wgrad_workspace_bytes(M, ksize, c_in, c_out) bytes (0 for a shape the call refuses), allocated by the caller;
+ *   a smaller workspace_bytes is refused, nothing is truncated.  M = 0 writes zeros to the results.
+ * cosy_head_weight_pack: a parameter on the device in torchvision's layout -> fwd, the fragment order cosy_head_conv reads (float32; the
+ *   bytes of the host packing), fwd_bias (c_out rounded up to 64 floats; ksize 2: 4 C_o, every bias four times) and bwd, the packing
+ *   cosy_head_dgrad reads: rows c, reduction o rounded up to 16 with zeros, taps in reverse order (ksize 3) or (dy, dx) ascending (ksize 2).
+ *   w0 / b0 (n0 outputs), then w1 / b1 (n1 outputs, n1 = 0: none) are the siblings of one GEMM.  One launch, no host round trip.
+ * All: checked on the host before the launch (COSY_EINVAL, cosy_last_error() names the argument); M <= 2^30, 64-bit offsets; 1 to
+ * COSY_RPN_MAX_LEVELS levels; pointers 16-byte aligned where cosy_head_conv asks for it. */
+int cosy_head_wgrad_slab_rows(int M);
+size_t cosy_head_wgrad_workspace_bytes(int M, int ksize, int c_in, int c_out);
+int cosy_head_grad_pack(const float* g0, const float* g1, float* rows, int B, int n0, int n1, int HW, cosy_stream_t stream);
+int cosy_head_weight_pack(const float* w0, const float* b0, const float* w1, const float* b1, int ksize, int c_in, int n0, int n1, float* fwd,
+                          float* fwd_bias, float* bwd, cosy_stream_t stream);
+int cosy_head_dgrad(const cosy_head_layer_t* layer, const float* y, cosy_stream_t stream);
+int cosy_head_wgrad(const cosy_head_layer_t* layer, const float* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace,
+                    size_t workspace_bytes, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
