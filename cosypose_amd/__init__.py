@@ -89,6 +89,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('DetectorTrunk', 'Detector', 'TrunkLayer', 'trunk_conv_layer'):
         from . import detector_trunk
         return getattr(detector_trunk, name)
+    if name in ('TrainableTrunkLayer', 'trunk_dgrad', 'trunk_wgrad', 'layer_dgrad', 'layer_wgrad'):
+        from . import detector_trunk_backward
+        return getattr(detector_trunk_backward, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

@@ -71,6 +71,7 @@ RPN_MAX_LEVELS, RPN_MAX_ANCHORS = 8, 16
 DT_MAX_GT, DT_MAX_BATCH, DT_MAX_CLASSES, DT_MAX_M = 1024, 4096, 4096, 128
 DETIN_ONE_TAP = 1
 HEAD_STORE_ROWS, HEAD_STORE_NCHW, HEAD_STORE_DECONV_ROWS, HEAD_STORE_DECONV_NCHW = 0, 1, 2, 3
+TRUNK_ADD_NONE, TRUNK_ADD_SAME, TRUNK_ADD_EVEN, TRUNK_ADD_NEAREST_T = 0, 1, 2, 3
 
 
 class MeshSet(ctypes.Structure):       # cosy_mesh_t

@@ -1,7 +1,7 @@
 """The detector's heads on the matrix pipe: Mask R-CNN's RPN head, box head + predictor and mask head + predictor (torchvision 0.4.2), the
 convolutions and linears between the FPN and detector.detections_from_heads.  By default inference only (HIP: csrc/kernels_dethead.hip, cosy_head_pack and
 cosy_head_conv).  DetectorHeads(..., trainable=True) are float32 heads with parameters and a backward on the same matrix pipe, behind autograd
-(HIP: csrc/kernels_detheadbwd.hip); the trunk's backward is not built.
+(HIP: csrc/kernels_detheadbwd.hip); the trunk's backward is detector_trunk_backward.py (section 29).
 
 Every layer is one implicit GEMM over ROWS: a row is one cell (level, image, y, x) with its channels contiguous in the storage type (float32,
 float16 or bfloat16; a linear layer's row is its input vector).  The heads' inputs arrive as contiguous NCHW float32 (what the FPN and

@@ -1,5 +1,6 @@
 """The detector's trunk on the matrix pipe: torchvision 0.4.2's ResNet-50 body with FrozenBatchNorm2d and its FeaturePyramidNetwork, the part
-of Mask R-CNN between detector_input and DetectorHeads, and `Detector`, the reference's interface over the whole chain.  Inference only.
+of Mask R-CNN between detector_input and DetectorHeads, and `Detector`, the reference's interface over the whole chain.  Inference only by
+default; trainable=True (float32) makes the trunk an autograd node with parameters (detector_trunk_backward.py).
 DESIGN.md section 27 states the contract; HIP: csrc/kernels_dettrunk.hip (cosy_trunk_conv, cosy_trunk_stem_pack, cosy_trunk_maxpool) and the
 GEMM it shares with the heads (csrc/dethead_device.h).
 
@@ -224,15 +225,36 @@ class DetectorTrunk:
             if lat.c_in != width or lay.c_in != lat.c_out or lay.c_out != outer[0].c_out or lat.c_out != inner[0].c_out:
                 raise ValueError(f'{lat.name}: the FPN\'s widths do not match the stage ({width}) or one another')
         self._arena = {}
+        self.trainable, self.train_from_stage = False, None
+        self.keep_rows, self.timer, self.last_rows, self.last_kept_bytes = False, None, None, 0
 
     # ---- construction ----
     @classmethod
-    def from_state_dict(cls, sd, dtype=torch.float32, device=None, prefix='backbone.'):
+    def from_state_dict(cls, sd, dtype=torch.float32, device=None, prefix='backbone.', trainable=False, train_from_stage=2):
         """torchvision 0.4.2's keys under `prefix`: body.conv1 / bn1, body.layer{s}.{i}.conv{1,2,3} / bn{1,2,3} / downsample.{0,1}, fpn.inner_blocks.{l},
         fpn.layer_blocks.{l}.  Block counts and widths are the keys' and the shapes'; num_batches_tracked and every other key are ignored; a
-        missing key is a KeyError naming it"""
+        missing key is a KeyError naming it.
+        trainable (float32 only): the conv weights of body.layer{train_from_stage}.. and the FPN's weights and biases are
+        torch.nn.Parameters on the device under torchvision's names; the stem, the stages below and every FrozenBatchNorm stay constants.
+        train_from_stage = stages + 1 trains the FPN alone; 0 (the stem and the pool) is refused: their backward is not built"""
         dtype = _dtype(dtype)
         kw = dict(dtype=dtype, device=device)
+        if trainable:
+            if dtype != torch.float32:
+                raise ValueError(f'a trainable trunk is float32 only (16-bit training and master weights are not built), got dtype={dtype}')
+            if isinstance(train_from_stage, bool) or not isinstance(train_from_stage, int):
+                raise ValueError(f'train_from_stage must be an int, got {train_from_stage!r}')
+            if train_from_stage < 1:
+                raise ValueError(f'train_from_stage={train_from_stage}: the backward of the 7x7 stem and of the 3x3 max pool is not built; the first '
+                                 'trainable stage is body.layer1 (train_from_stage=1)')
+            if device is None:
+                first = next((t for t in sd.values() if torch.is_tensor(t) and t.is_cuda), None)
+                device = first.device if first is not None else None
+            if device is None or torch.device(device).type != 'cuda':
+                raise ValueError(f'a trainable trunk lives on the ROCm device: give device=, got {device}')
+            kw['device'] = device
+            from .detector_trunk_backward import TrainableTrunkLayer
+            counter = [0]
 
         def get(key):
             if prefix + key not in sd:
@@ -246,8 +268,15 @@ class DetectorTrunk:
         def bn(name):
             return tuple(get(f'{name}.{part}') for part in _BN)
 
-        def conv_bn(conv, norm, stride=1, relu=True):
+        def conv_bn(conv, norm, stride=1, relu=True, train=False):
+            if train:
+                return TrainableTrunkLayer(prefix + conv, get(conv + '.weight'), bn=bn(norm), stride=stride, relu=relu, device=device, counter=counter)
             return TrunkLayer(prefix + conv, get(conv + '.weight'), bn=bn(norm), stride=stride, relu=relu, **kw)
+
+        def fpn_layer(key):
+            if trainable:
+                return TrainableTrunkLayer(prefix + key, get(key + '.weight'), bias=get(key + '.bias'), device=device, counter=counter)
+            return TrunkLayer(prefix + key, get(key + '.weight'), bias=get(key + '.bias'), **kw)
         found = {}
         for k in sd:
             m = re.match(re.escape(prefix) + r'body\.layer(\d+)\.(\d+)\.', k)
@@ -255,36 +284,101 @@ class DetectorTrunk:
                 found.setdefault(int(m.group(1)), set()).add(int(m.group(2)))
         if not found:
             raise KeyError(prefix + 'body.layer1.0.conv1.weight')
+        if trainable and train_from_stage > max(found) + 1:
+            raise ValueError(f'train_from_stage={train_from_stage} exceeds {max(found) + 1} (the {max(found)} stages + 1: the FPN alone)')
         stem = conv_bn('body.conv1', 'body.bn1', stride=2)
         stages = []
         for s in range(1, max(found) + 1):
             blocks = []
+            t = bool(trainable) and s >= train_from_stage
             for i in range(max(found.get(s, {0})) + 1):
                 p = f'body.layer{s}.{i}'
                 stride = 2 if (s > 1 and i == 0) else 1               # ResNet v1.5: the stride sits on the 3x3 and on downsample.0
                 down = None
                 if any(k.startswith(f'{prefix}{p}.downsample.') for k in sd):
-                    down = conv_bn(f'{p}.downsample.0', f'{p}.downsample.1', stride=stride, relu=False)
-                blocks.append(Bottleneck(conv_bn(f'{p}.conv1', f'{p}.bn1'), conv_bn(f'{p}.conv2', f'{p}.bn2', stride=stride),
-                                         conv_bn(f'{p}.conv3', f'{p}.bn3'), down))       # conv3's ReLU follows the shortcut's add
+                    down = conv_bn(f'{p}.downsample.0', f'{p}.downsample.1', stride=stride, relu=False, train=t)
+                blocks.append(Bottleneck(conv_bn(f'{p}.conv1', f'{p}.bn1', train=t), conv_bn(f'{p}.conv2', f'{p}.bn2', stride=stride, train=t),
+                                         conv_bn(f'{p}.conv3', f'{p}.bn3', train=t), down))       # conv3's ReLU follows the shortcut's add
             stages.append(blocks)
-        inner = [TrunkLayer(f'{prefix}fpn.inner_blocks.{l}', get(f'fpn.inner_blocks.{l}.weight'), bias=get(f'fpn.inner_blocks.{l}.bias'), **kw)
-                 for l in range(len(stages))]
-        outer = [TrunkLayer(f'{prefix}fpn.layer_blocks.{l}', get(f'fpn.layer_blocks.{l}.weight'), bias=get(f'fpn.layer_blocks.{l}.bias'), **kw)
-                 for l in range(len(stages))]
+        inner = [fpn_layer(f'fpn.inner_blocks.{l}') for l in range(len(stages))]
+        outer = [fpn_layer(f'fpn.layer_blocks.{l}') for l in range(len(stages))]
         for lay in outer:
             if lay.ksize != 3:
                 raise ValueError(f'{lay.name}: an FPN output block is a 3x3 convolution, got {lay.ksize}x{lay.ksize}')
-        return cls(stem, stages, inner, outer, dtype)
+        trunk = cls(stem, stages, inner, outer, dtype)
+        if trainable:
+            trunk._init_trainable(sd, prefix, train_from_stage, counter)
+        return trunk
 
     @classmethod
-    def from_modules(cls, backbone, dtype=torch.float32, device=None):
-        """the same from a module with torchvision's attribute names (body, fpn): its state_dict under no prefix"""
+    def from_modules(cls, backbone, dtype=torch.float32, device=None, trainable=False, train_from_stage=2):
+        """the same from a module with torchvision's attribute names (body, fpn): its state_dict under no prefix (trainable: copies, never
+        the module's own tensors)"""
         sd = backbone.state_dict()
         if device is None:
             first = next(iter(sd.values())).device
             device = first if first.type != 'cpu' else None
-        return cls.from_state_dict(sd, dtype, device, prefix='')
+        return cls.from_state_dict(sd, dtype, device, prefix='', trainable=trainable, train_from_stage=train_from_stage)
+
+    # ---- the trainable trunk (DESIGN.md section 29) ----
+    def _init_trainable(self, sd, prefix, train_from_stage, counter):
+        self.trainable, self.train_from_stage, self._counter, self._prefix = True, int(train_from_stage), counter, prefix
+        self._named = []
+        for layer in self.layers():
+            if hasattr(layer, 'weight'):
+                self._named += [(f'{layer.name}.{part}', p) for part, p in zip(('weight', 'bias'), layer.parameters())]
+        own = re.compile(re.escape(prefix) + r'(body|fpn)\.')
+        trained = {k for k, _ in self._named}
+        # every key of the trunk, in the state dict's order: parameters by reference, the frozen weights and the BatchNorm buffers as CPU copies
+        self._keys = [k for k in sd if own.match(k)]
+        self._frozen = {k: sd[k].detach().to('cpu').clone() for k in self._keys if k not in trained}
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError(f'{what}: this DetectorTrunk is inference only; build it with trainable=True')
+
+    @property
+    def pack_count(self):
+        """device weight packs launched so far: one per layer whose parameters moved since its last pack"""
+        self._need_trainable('pack_count')
+        return self._counter[0]
+
+    def named_parameters(self):
+        self._need_trainable('named_parameters')
+        return list(self._named)
+
+    def parameters(self):
+        self._need_trainable('parameters')
+        return [t for _, t in self._named]
+
+    def zero_grad(self):
+        for t in self.parameters():
+            t.grad = None
+
+    def state_dict(self):
+        """ALL the trunk's keys under the prefix it was built with, the frozen layers and the BatchNorm buffers included: detached copies"""
+        self._need_trainable('state_dict')
+        live = dict(self._named)
+        return {k: (live[k].detach().clone() if k in live else self._frozen[k].clone()) for k in self._keys}
+
+    def load_state_dict(self, sd, strict=True):
+        """copies the trainable keys into the parameters in place (their _version moves, the next forward packs again).  The frozen keys are
+        constants of this trunk: a value that differs from the one it was built with is refused (build a new trunk from that state dict)"""
+        self._need_trainable('load_state_dict')
+        for k, t in self._named:
+            if k not in sd:
+                if strict:
+                    raise KeyError(k)
+                continue
+            if tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f'{k} must be {tuple(t.shape)}, got {tuple(sd[k].shape)}')
+        for k, t in self._frozen.items():
+            if k in sd and not k.endswith('num_batches_tracked') and not torch.equal(sd[k].detach().to('cpu', t.dtype), t):
+                raise ValueError(f'{k} is frozen in this trunk and differs from the value it was built with: build a new trunk with from_state_dict')
+        with torch.no_grad():
+            for k, t in self._named:
+                if k in sd:
+                    t.copy_(sd[k])
 
     def layers(self):
         """every packed layer, in a fixed order (tests compare their bytes)"""
@@ -365,9 +459,15 @@ class DetectorTrunk:
         return self.fpn_rows([(_to_rows(f, self.dtype), int(f.shape[2]), int(f.shape[3])) for f in feats], B)
 
     def __call__(self, images):
+        if self.trainable and torch.is_grad_enabled() and torch.is_tensor(images) and images.requires_grad:
+            raise RuntimeError('images requires grad: the backward of the 7x7 stem and of the 3x3 max pool is not built; detach the input')
         images = _input(images, 'images', 3)
         self._ready(images.device)
         with torch.cuda.device(images.device):
+            if self.trainable and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                from .detector_trunk_backward import TrunkFn
+                out = list(TrunkFn.apply(self, images, *self.parameters()))
+                return out + [out[-1][..., ::2, ::2].contiguous()]      # LastLevelMaxPool: a torch slice of the node's last output
             B = int(images.shape[0])
             x, H, W = self.stem_rows(images)
             return self.fpn_rows(self.stage_rows(x, B, H, W), B)
@@ -388,10 +488,59 @@ class Detector:
         self.min_size, self.max_size = int(min(input_resize)), int(max(input_resize))
 
     @classmethod
-    def from_state_dict(cls, sd, label_to_category_id, input_resize=(480, 640), dtype=torch.float32, device='cuda'):
-        """a reference detector checkpoint's state_dict as it is (backbone.*, rpn.head.*, roi_heads.*)"""
+    def from_state_dict(cls, sd, label_to_category_id, input_resize=(480, 640), dtype=torch.float32, device='cuda', trainable=False, train_from_stage=2):
+        """a reference detector checkpoint's state_dict as it is (backbone.*, rpn.head.*, roi_heads.*).  trainable: the trainable trunk
+         and the trainable heads (section 28), float32"""
         from .detector_heads import DetectorHeads
-        return cls(DetectorTrunk.from_state_dict(sd, dtype, device), DetectorHeads.from_state_dict(sd, dtype, device), label_to_category_id, input_resize)
+        if trainable and dtype != torch.float32:
+            raise ValueError(f'a trainable detector is float32 only (16-bit training and master weights are not built), got dtype={dtype}')
+        trunk = DetectorTrunk.from_state_dict(sd, dtype, device, trainable=trainable, train_from_stage=train_from_stage)
+        return cls(trunk, DetectorHeads.from_state_dict(sd, dtype, device, trainable=trainable), label_to_category_id, input_resize)
+
+    # ---- training (trainable=True): the reference's train_detector.py loop on this library's kernels ----
+    @property
+    def trainable(self):
+        return bool(getattr(self.trunk, 'trainable', False) and getattr(self.heads, 'trainable', False))
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError(f'{what}: this Detector is inference only; build it with trainable=True')
+
+    def losses(self, frames, targets, keys=None, generator=None):
+        """uint8 frames and their targets (boxes, labels, masks at the frames' sizes) -> the reference's loss_dict, with autograd history
+        through the heads, both RoIAligns and the trunk; the detector's sizes and the RPN settings of get_detections"""
+        from .detector_input import detector_losses_from_frames
+        self._need_trainable('losses')
+        return detector_losses_from_frames(frames, targets, self.trunk, self.heads.rpn_head, self.heads.box_head, self.heads.mask_head,
+                                           min_size=self.min_size, max_size=self.max_size, keys=keys, generator=generator, sizes=ANCHOR_SIZES,
+                                           aspect_ratios=ASPECT_RATIOS)
+
+    def named_parameters(self):
+        self._need_trainable('named_parameters')
+        return self.trunk.named_parameters() + self.heads.named_parameters()
+
+    def parameters(self):
+        return [t for _, t in self.named_parameters()]
+
+    def zero_grad(self):
+        for t in self.parameters():
+            t.grad = None
+
+    def state_dict(self):
+        self._need_trainable('state_dict')
+        return {**self.trunk.state_dict(), **self.heads.state_dict()}
+
+    def load_state_dict(self, sd, strict=True):
+        self._need_trainable('load_state_dict')
+        self.trunk.load_state_dict(sd, strict)
+        self.heads.load_state_dict(sd, strict)
+
+    def train(self, mode=True):
+        """nothing here has a mode (every BatchNorm is frozen, there is no dropout): returns self"""
+        return self
+
+    def eval(self):
+        return self
 
     def get_detections(self, images, detection_th=None, output_masks=False, mask_th=0.8, one_instance_per_class=False):
         """images: uint8 frames (B,H,W,3) or (B,3,H,W), or a list of them; float frames are refused (detector_input)"""

@@ -1,0 +1,310 @@
+"""The backward of the detector's trunk on the matrix pipe, float32 only: the data and weight gradients of the ResNet
+bottlenecks and the FPN as GEMMs (HIP: csrc/kernels_dettrunkbwd.hip -- cosy_trunk_weight_pack, cosy_trunk_dgrad, cosy_trunk_wgrad), the
+trainable layer that holds a trunk parameter, and the autograd node behind DetectorTrunk(trainable=True).
+
+A trunk layer is v = fmaf(conv_stride(x, W), scale, shift) [+ r], y = relu(v).  Its gradient rows g are the gradient at v, float32 rows on
+the layer's OUTPUT grid.  No scaled copy of g is stored: the data gradient reads ws = w scale[o] (packed once per weight version), the weight
+gradient multiplies by scale[o] in its second pass.  The store of a data-gradient launch adds the shortcut's and the FPN's contributions and
+applies the ReLU mask of the block below: no element-wise launch sits between two GEMMs.
+"""
+import contextlib
+import ctypes
+
+import torch
+
+from . import _lib
+from .detector_heads import MAX_ROWS, _g, _grad_pack, _gemm
+
+F32 = torch.float32
+SAME, EVEN, NEAREST_T = _lib.TRUNK_ADD_SAME, _lib.TRUNK_ADD_EVEN, _lib.TRUNK_ADD_NEAREST_T
+
+
+def _out(n, stride):
+    return (n - 1) // stride + 1
+
+
+class TrainableTrunkLayer:
+    """A trainable convolution of the trunk: weight is a torch.nn.Parameter (O,C,k,k) on the device under torchvision's name; a layer followed
+    by FrozenBatchNorm keeps its scale and shift as constants, an FPN layer has a bias Parameter and no scale.  w / bias (what cosy_trunk_conv
+    and cosy_head_conv read, the host packing's bytes) and w_t (the transposed, tap-flipped packing of ws = w scale[o]) are written by
+    cosy_trunk_weight_pack when a parameter's _version or storage has moved since the last pack."""
+    kind, dtype = 'conv', F32
+
+    def __init__(self, name, weight, bn=None, bias=None, stride=1, relu=False, device=None, counter=None):
+        from .detector_trunk import frozen_bn
+        if device is None or torch.device(device).type != 'cuda':
+            raise ValueError(f'{name}: a trainable trunk lives on the ROCm device: give device=, got {device}')
+        if not torch.is_tensor(weight) or weight.dim() != 4:
+            raise ValueError(f'{name}.weight must be a 4-d tensor')
+        O, C, k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+        if weight.shape[3] != k or k not in (1, 3):
+            raise ValueError(f'{name}: a trainable trunk convolution is 1x1 or 3x3, got a weight of {tuple(weight.shape)}')
+        if stride not in (1, 2):
+            raise ValueError(f'{name}: stride must be 1 or 2, got {stride}')
+        if C % 8 or O % 8:
+            raise ValueError(f'{name}: {C} -> {O} channels: every channel count must be a multiple of 8')
+        self.name, self.ksize, self.stride, self.relu = name, k, int(stride), bool(relu)
+        self.c_in, self.c_out, self.n_out = C, O, O
+        self.counter = counter if counter is not None else [0]
+        self.weight = torch.nn.Parameter(weight.detach().to(device=device, dtype=F32).contiguous().clone())
+        self.device = dev = self.weight.device
+        NP = -(-O // 64) * 64
+        self.bias_param, self.scale, self.shift = None, None, None
+        if bn is not None:
+            scale, shift = frozen_bn(*bn)
+            if scale.shape[0] != O:
+                raise ValueError(f'{name}: the batch norm holds {scale.shape[0]} channels, the convolution {O}')
+            self.scale = torch.zeros(NP, dtype=F32)
+            self.scale[:O] = scale
+            self.scale, self.shift = self.scale.to(dev), shift.to(dev).contiguous()
+        else:
+            b = torch.zeros(O) if bias is None else bias
+            if b.dim() != 1 or b.shape[0] != O:
+                raise ValueError(f'{name}.bias must be ({O}), got {tuple(b.shape)}')
+            self.bias_param = torch.nn.Parameter(b.detach().to(device=dev, dtype=F32).contiguous().clone())
+        taps = k * k
+        self.w = torch.empty(NP * taps * (-(-C // 16) * 16), dtype=F32, device=dev)
+        self.bias = torch.empty(NP, dtype=F32, device=dev)
+        self.w_t = torch.empty((-(-C // 64) * 64) * taps * (-(-O // 16) * 16), dtype=F32, device=dev)
+        self.versions = None
+
+    def parameters(self):
+        return [self.weight] + ([self.bias_param] if self.bias_param is not None else [])
+
+    def refresh(self, dev=None):
+        if dev is not None and torch.device(dev) != self.device:
+            raise ValueError(f'the input lives on {dev}, the parameters on {self.device}: build the trunk with device={dev!s}')
+        now = tuple((p._version, p.data_ptr()) for p in self.parameters())
+        if now != self.versions:
+            shift = self.shift if self.bias_param is None else self.bias_param
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().cosy_trunk_weight_pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out,
+                                                             _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
+            self.versions = now
+            self.counter[0] += 1
+        return self
+
+    ready = refresh
+
+    def out_size(self, H, W):
+        return _out(H, self.stride), _out(W, self.stride)
+
+
+# ---- launches ------------------------------------------------------------------------------------------------------------------------
+def _one_level(d, B, H, W):
+    if B * H * W > MAX_ROWS:
+        raise ValueError(f'{B * H * W} rows (cells of all maps) exceed the limit of 2^30 per launch')
+    d.n_levels = 1
+    d.row_start[0], d.row_start[1], d.H[0], d.W[0] = 0, B * H * W, H, W
+
+
+def trunk_dgrad(layer, g_rows, B, H, W, out, adds=(), y=None, store=_lib.HEAD_STORE_ROWS, stride=None):
+    """one cosy_trunk_dgrad call: g_rows on the layer's output grid -> dX on B maps of H x W cells.  adds: up to two (rule, rows, H, W);
+    y: the mask rows on the dX grid.  stride: the layer's own unless given (downsample.0 runs at stride 1 on its output grid)"""
+    d = _lib.HeadLayer()
+    d.x, d.w, d.out = _lib.ptr(g_rows), _lib.ptr(layer.w_t), _lib.ptr(out)
+    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_out, layer.c_in, 0, store, layer.c_in
+    _one_level(d, B, H, W)
+    adds = list(adds)
+    if len(adds) > 2:
+        raise ValueError(f'a data-gradient store takes at most two add operands, got {len(adds)}')
+    flat = []
+    for rule, rows, aH, aW in adds + [(_lib.TRUNK_ADD_NONE, None, 0, 0)] * (2 - len(adds)):
+        flat += [_lib.ptr(rows), rule, aH, aW]
+    _lib.check(_lib.lib().cosy_trunk_dgrad(ctypes.byref(d), layer.stride if stride is None else stride, *flat, _lib.ptr(y), _lib.stream()))
+    return out
+
+
+def trunk_wgrad(layer, x_rows, g_rows, B, H, W):
+    """one cosy_trunk_wgrad call: x_rows on B maps of H x W cells, g_rows on the output grid -> [dW (, db)] in the parameters' layout"""
+    d = _lib.HeadLayer()
+    d.x = _lib.ptr(x_rows)
+    d.dtype, d.ksize, d.c_in, d.c_out, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_in, layer.c_out, layer.c_out
+    _one_level(d, B, H, W)
+    Ho, Wo = layer.out_size(H, W)
+    T = B * Ho * Wo
+    out = [torch.empty_like(p) for p in layer.parameters()]
+    need = int(_lib.lib().cosy_head_wgrad_workspace_bytes(T, layer.ksize, layer.c_in, layer.c_out))
+    if T and not need:
+        raise ValueError(f'the weight gradient of {T} cells, c_in={layer.c_in}, c_out={layer.c_out} does not fit the library\'s limits')
+    ws = torch.empty(max(need // 4, 4), dtype=F32, device=layer.device)
+    _lib.check(_lib.lib().cosy_trunk_wgrad(ctypes.byref(d), layer.stride, _lib.ptr(g_rows), _lib.ptr(layer.scale), _lib.ptr(out[0]),
+                                           _lib.ptr(out[1]) if len(out) > 1 else None, _lib.ptr(ws), need, _lib.stream()))
+    return out
+
+
+def layer_dgrad(layer, grad, H, W, adds=(), y=None, stride=None):
+    """One layer's data gradient through the kernel, NCHW in and out (the tests' access).  grad (B,O,Ho,Wo) float32 at the layer's pre-activation
+    output; H, W: the dX grid; adds: (rule, (B,C,h,w) float32 map); y: (B,C,H,W) float32, the stored output of the layer below -> (B,C,H,W)"""
+    dev = grad.device
+    layer.ready(dev)
+    B, O, Ho, Wo = (int(v) for v in grad.shape)
+    rows = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().view(-1, int(t.shape[1]))
+    ops = [(rule, rows(t), int(t.shape[2]), int(t.shape[3])) for rule, t in adds]
+    out = torch.empty((B, layer.c_in, H, W), dtype=F32, device=dev)
+    with torch.cuda.device(dev):
+        trunk_dgrad(layer, rows(grad), B, H, W, out, ops, None if y is None else rows(y), _lib.HEAD_STORE_NCHW, stride)
+    return out
+
+
+def layer_wgrad(layer, x, grad):
+    """One layer's weight gradient through the kernel: x (B,C,H,W), grad (B,O,Ho,Wo) float32 -> [dW (, db)]"""
+    dev = x.device
+    layer.ready(dev)
+    B, C, H, W = (int(v) for v in x.shape)
+    rows = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().view(-1, int(t.shape[1]))
+    with torch.cuda.device(dev):
+        return trunk_wgrad(layer, rows(x), rows(grad), B, H, W)
+
+
+# ---- the node --------------------------------------------------------------------------------------------------------------------------
+def forward_keep(trunk, images):
+    """section 27's launches; the stages below train_from_stage and the stem run in the trunk's arena and keep nothing, the rows the backward
+    reads (x, a, b, out of every trainable block, the stage outputs, the laterals) are tensors of their own -> the four maps, keep"""
+    from .detector_trunk import _trunk_gemm
+    dev, B = images.device, int(images.shape[0])
+    fresh = lambda n, c: torch.empty((n, c), dtype=F32, device=dev)
+    x, H, W = trunk.stem_rows(images)
+    tfs = trunk.train_from_stage
+    if tfs == 1:
+        x = x.clone()
+    blocks_keep, feats, flip = {}, [], 0
+    for si, blocks in enumerate(trunk.stages):
+        for bi, blk in enumerate(blocks):
+            stage_out = f'stage{si}'
+            name = stage_out if bi == len(blocks) - 1 else f'x{flip}'
+            if si + 1 >= tfs:
+                kept = {}
+
+                def buf(slot, n, c, kept=kept):
+                    kept[slot] = fresh(n, c)
+                    return kept[slot]
+                out, Ho, Wo = blk.rows(x, B, H, W, buf, name)
+                blocks_keep[(si + 1, bi)] = dict(x=x, a=kept['a'], b=kept['b'], out=out, H=H, W=W, Ho=Ho, Wo=Wo)
+            else:
+                out, Ho, Wo = blk.rows(x, B, H, W, lambda slot, n, c: fresh(n, c) if slot == stage_out else trunk._buf(slot, n, c), name)
+            x, H, W = out, Ho, Wo
+            flip ^= 1
+        feats.append((x, H, W))
+    L, C = len(feats), trunk.outer[0].c_out
+    starts = [0]
+    for _, h, w in feats:
+        starts.append(starts[-1] + B * h * w)
+    if starts[-1] > MAX_ROWS:
+        raise ValueError(f'{starts[-1]} rows (cells of all levels) exceed the limit of 2^30 per launch')
+    inner = fresh(starts[-1], trunk.inner[0].c_out)
+    for l in range(L - 1, -1, -1):
+        rows, h, w = feats[l]
+        res, res_hw = (None, None) if l == L - 1 else (inner[starts[l + 1]:starts[l + 2]], feats[l + 1][1:])
+        _trunk_gemm(trunk.inner[l], rows, B, h, w, inner[starts[l]:starts[l + 1]], residual=res, res_hw=res_hw)
+    flat = torch.empty(C * starts[-1], dtype=F32, device=dev)
+    for l, (_, h, w) in enumerate(feats):
+        _gemm(trunk.outer[l], inner[starts[l]:starts[l + 1]], [(B, h, w)], _lib.HEAD_STORE_NCHW, flat[C * starts[l]:C * starts[l + 1]])
+    out = [flat[C * starts[l]:C * starts[l + 1]].view(B, C, h, w) for l, (_, h, w) in enumerate(feats)]
+    return out, dict(blocks=blocks_keep, feats=feats, inner=inner, starts=starts, B=B)
+
+
+def kept_bytes(keep):
+    """bytes of the rows a forward holds for its backward"""
+    seen, total = set(), 0
+    tensors = [keep['inner']] + [f[0] for f in keep['feats']] + [t for k in keep['blocks'].values() for t in (k['x'], k['a'], k['b'], k['out'])]
+    for t in tensors:
+        key = t.untyped_storage().data_ptr() if hasattr(t, 'untyped_storage') else t.data_ptr()
+        if key not in seen:
+            seen.add(key)
+            total += t.numel() * t.element_size()
+    return total
+
+
+def backward(trunk, keep, grads, rows_out=None, timer=None):
+    """section 29's chain.  grads: the NCHW gradients at the four maps (None: zeros).  -> {id(parameter): gradient}.  rows_out: a dict that
+    receives every gradient row buffer under the twin's names (the tests).  timer: a callable (group) -> context manager ('fpn', 'dgrad', 'wgrad')"""
+    B, feats, inner, starts, bk = keep['B'], keep['feats'], keep['inner'], keep['starts'], keep['blocks']
+    dev = inner.device
+    L, tfs = len(trunk.stages), trunk.train_from_stage
+    new = lambda n, c: torch.empty((n, c), dtype=F32, device=dev)
+    timed = timer if timer is not None else (lambda group: contextlib.nullcontext())
+    out = {}
+
+    def note(name, rows, h, w):
+        if rows_out is not None:
+            rows_out[name] = (rows, B, h, w)
+
+    def put(layer, grads_):
+        for p, g in zip(layer.parameters(), grads_):
+            out[id(p)] = g
+    C = trunk.outer[0].c_out
+    G = []
+    with timed('fpn'):
+        for l in range(L):
+            _, h, w = feats[l]
+            g = _grad_pack(_g(grads[l]), None, new(B * h * w, C), B, C, 0, h * w)
+            x_in = inner[starts[l]:starts[l + 1]]
+            put(trunk.outer[l], trunk_wgrad(trunk.outer[l], x_in, g, B, h, w))
+            adds = [] if l == 0 else [(NEAREST_T, G[l - 1], feats[l - 1][1], feats[l - 1][2])]
+            G.append(trunk_dgrad(trunk.outer[l], g, B, h, w, new(B * h * w, trunk.inner[l].c_out), adds))
+            note(f'fpn.G_inner.{l}', G[l], h, w)
+            put(trunk.inner[l], trunk_wgrad(trunk.inner[l], feats[l][0], G[l], B, h, w))
+
+    def lateral(s, masked):
+        rows, h, w = feats[s - 1]
+        with timed('fpn'):
+            r = trunk_dgrad(trunk.inner[s - 1], G[s - 1], B, h, w, new(B * h * w, trunk.inner[s - 1].c_in), y=rows if masked else None)
+        note(f'fpn.lateral_dx.{s - 1}', r, h, w)
+        return r
+    g3 = None
+    for s in range(L, tfs - 1, -1):
+        blocks = trunk.stages[s - 1]
+        if s == L:
+            g3 = lateral(s, True)
+        for i in range(len(blocks) - 1, -1, -1):
+            blk, k = blocks[i], bk[(s, i)]
+            H, W, Ho, Wo = k['H'], k['W'], k['Ho'], k['Wo']
+            name = f'body.layer{s}.{i}'
+            first = s == tfs and i == 0
+            with timed('dgrad'):
+                g2 = trunk_dgrad(blk.conv3, g3, B, Ho, Wo, new(B * Ho * Wo, blk.conv3.c_in), y=k['b'])
+                g1 = trunk_dgrad(blk.conv2, g2, B, H, W, new(B * H * W, blk.conv2.c_in), y=k['a'])
+            note(f'{name}.g3', g3, Ho, Wo), note(f'{name}.g2', g2, Ho, Wo), note(f'{name}.g1', g1, H, W)
+            with timed('wgrad'):
+                put(blk.conv3, trunk_wgrad(blk.conv3, k['b'], g3, B, Ho, Wo))
+                put(blk.conv2, trunk_wgrad(blk.conv2, k['a'], g2, B, H, W))
+                put(blk.conv1, trunk_wgrad(blk.conv1, k['x'], g1, B, H, W))
+                if blk.downsample is not None:
+                    put(blk.downsample, trunk_wgrad(blk.downsample, k['x'], g3, B, H, W))
+            if first:
+                break
+            tail = [(SAME, lateral(s - 1, False), H, W)] if i == 0 else []
+            with timed('dgrad'):
+                if blk.downsample is None:
+                    adds = [(SAME, g3, H, W)]
+                else:
+                    d = trunk_dgrad(blk.downsample, g3, B, Ho, Wo, new(B * Ho * Wo, blk.downsample.c_in), stride=1)
+                    note(f'{name}.down_dx', d, Ho, Wo)
+                    adds = [(EVEN if blk.conv2.stride == 2 else SAME, d, Ho, Wo)]
+                g3 = trunk_dgrad(blk.conv1, g1, B, H, W, new(B * H * W, blk.conv1.c_in), adds + tail, y=k['x'])
+    return out
+
+
+class TrunkFn(torch.autograd.Function):
+    """trunk(images) as one node: forward = section 27's launches, backward = section 29's"""
+
+    @staticmethod
+    def forward(ctx, trunk, images, *params):
+        out, keep = forward_keep(trunk, images)
+        ctx.trunk, ctx.keep, ctx.n = trunk, keep, len(params)
+        trunk.last_kept_bytes = kept_bytes(keep)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if torch.is_grad_enabled():
+            raise RuntimeError('DetectorTrunk: double backward is not built (the backward of the trunk\'s backward has no kernel); '
+                               'call backward() without create_graph')
+        trunk = ctx.trunk
+        rows_out = {} if trunk.keep_rows else None
+        with torch.cuda.device(ctx.keep['inner'].device):
+            got = backward(trunk, ctx.keep, grads, rows_out, trunk.timer)
+        if rows_out is not None:
+            trunk.last_rows = rows_out
+        return (None, None) + tuple(got.get(id(p)) for p in trunk.parameters())

@@ -1091,6 +1091,40 @@ int cosy_head_dgrad(const cosy_head_layer_t* layer, const float* y, cosy_stream_
 int cosy_head_wgrad(const cosy_head_layer_t* layer, const float* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace,
                     size_t workspace_bytes, cosy_stream_t stream);
 
+/* ---- the backward of the detector's trunk on the matrix pipe, float32 only ----  DESIGN.md section 29 holds the contract.
+ * A trunk layer is v = fmaf(conv_stride(x, W), scale, shift) [+ r], y = relu(v) as cosy_trunk_conv runs it; g is the gradient at v, float32
+ * rows (B Ho Wo, c_out) on the layer's OUTPUT grid, Ho = (H - 1) / stride + 1; every channel count is a multiple of 8.
+ * cosy_trunk_weight_pack: w (c_out, c_in, k, k) on the device in torchvision's layout, scale (c_out, or NULL: the FPN) and shift (c_out: the
+ *   FrozenBatchNorm shift, or the FPN's bias) -> fwd, the fragment order cosy_trunk_conv reads (the bytes of the host packing), fwd_bias (shift,
+ *   c_out rounded up to 64 floats, the pad +0.0) and bwd, the packing cosy_trunk_dgrad reads: ws = w scale[o] rounded ONCE to float32 (scale
+ *   NULL: ws = w), rows c, reduction o rounded up to 16 with zeros, taps in reverse order.  Sizes as cosy_head_weight_pack's.  One launch.
+ * cosy_trunk_dgrad: dX[(iy, ix)][c] = sum over o, (dy, dx) of ws[o][dy][dx][c] g[(y, x)][o] over the taps with iy = stride y + dy, ix =
+ *   stride x + dx and (y, x) inside the output map, in cosy_head_dgrad's summation order (accumulator +0.0, blocks of 16 o ascending, the live
+ *   taps in the packing's order inside a block, every term one fmaf).  layer->H / W / row_start describe the dX grid (the layer's INPUT maps),
+ *   layer->x = g on the output grid, c_in = the layer's output channels (the reduction), c_out = its input channels, w = bwd, dtype COSY_F32,
+ *   relu 0, bias unused.  stride 1 or 2 (2: one level, ksize 3: the four parity classes of (iy, ix) run as four row ranges, each with its 1,
+ *   2, 2 or 4 live taps; a 1x1 at stride 2 is refused: run it at stride 1 on its output grid and hand the rows in as an EVEN operand).
+ *   Store, per element, in this order: t = acc; for the operands add0, add1 with a rule other than COSY_TRUNK_ADD_NONE (rows of c_out float32
+ *   channels, one level): SAME: t = t + rows[cell]; EVEN: the rows live on the ((H - 1) / 2 + 1, (W - 1) / 2 + 1) grid (addK_H, addK_W must say
+ *   so), a cell with iy and ix even takes t = t + rows[(iy / 2, ix / 2)], every other cell is left untouched; NEAREST_T: the rows live on a finer
+ *   addK_H x addK_W grid, t = t + rows[(fy, fx)] for every finer cell whose cosy_trunk_conv nearest source (sy = (float)H / addK_H) is this
+ *   cell, (fy, fx) ascending; y != NULL: rows on the dX grid, t = y <= 0 ? +0.0 : t (a NaN y passes t); then COSY_HEAD_STORE_ROWS, or
+ *   COSY_HEAD_STORE_NCHW with n_split == c_out.  Every + is one rounded float32 add.
+ * cosy_trunk_wgrad: dw[o][c][tap] = scale[o] (sum over output cells of g[(y, x)][o] x[(stride y + dy, stride x + dx)][c]) in torchvision's
+ *   (c_out, c_in, k, k), x = +0.0 outside its map; db[o] = sum of g[.][o] (db NULL: none).  layer->x = the rows the layer read, H / W /
+ *   row_start their maps, c_in, c_out; the T = B Ho Wo output cells are cut into slabs of cosy_head_wgrad_slab_rows(T) and added in ascending
+ *   order, then multiplied by scale[o] as one rounded product (scale NULL: none).  workspace: cosy_head_wgrad_workspace_bytes(T, ksize,
+ *   c_in, c_out) bytes; a smaller one is refused.  T = 0 writes zeros.
+ * All: checked on the host before any launch (COSY_EINVAL, the message starts with the function's name); at most 2^30 rows; 16-byte aligned
+ * rows and packings.  No atomics: equal inputs give equal bits. */
+enum { COSY_TRUNK_ADD_NONE = 0, COSY_TRUNK_ADD_SAME = 1, COSY_TRUNK_ADD_EVEN = 2, COSY_TRUNK_ADD_NEAREST_T = 3 };
+int cosy_trunk_weight_pack(const float* w, const float* scale, const float* shift, int ksize, int c_in, int c_out, float* fwd, float* fwd_bias,
+                           float* bwd, cosy_stream_t stream);
+int cosy_trunk_dgrad(const cosy_head_layer_t* layer, int stride, const float* add0, int rule0, int add0_H, int add0_W, const float* add1,
+                     int rule1, int add1_H, int add1_W, const float* y, cosy_stream_t stream);
+int cosy_trunk_wgrad(const cosy_head_layer_t* layer, int stride, const float* g, const float* scale, float* dw, float* db, void* workspace,
+                     size_t workspace_bytes, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
