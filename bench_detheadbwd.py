@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the detector heads' training step (forward + backward of cosypose_amd.detector_heads with trainable=True, csrc/kernels_dethead.hip
-and csrc/kernels_detheadbwd.hip) on one GPU, float32, at bench_dethead.py's shapes: 8 frames padded to 800x1088, five FPN levels, C = 256,
+and csrc/kernels_detbwd.hip) on one GPU, float32, at bench_dethead.py's shapes: 8 frames padded to 800x1088, five FPN levels, C = 256,
 A = 3; the box head on 8 x 1000 rows of (256,7,7), hidden 1024, 22 classes; the mask head on 800 rows of (256,14,14).  Prints one JSON line.
 bench.py (the flagship workload) is a different script and is not affected.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the detector trunk's training step (forward + backward of cosypose_amd.DetectorTrunk with trainable=True, csrc/kernels_dettrunk.hip
-and csrc/kernels_dettrunkbwd.hip) on one GPU, float32, at bench_dettrunk.py's shape: 8 frames padded to 800x1088 through ResNet-50 + FPN, with
+and csrc/kernels_detbwd.hip) on one GPU, float32, at bench_dettrunk.py's shape: 8 frames padded to 800x1088 through ResNet-50 + FPN, with
 gradients arriving at the four maps.  Prints one JSON line.  bench.py (the flagship workload) is a different script and is not affected.
 
     timeout -k 10 900 python bench_dettrunkbwd.py --out profiles/dettrunkbwd_bench.json

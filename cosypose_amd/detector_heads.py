@@ -1,7 +1,7 @@
 """The detector's heads on the matrix pipe: Mask R-CNN's RPN head, box head + predictor and mask head + predictor (torchvision 0.4.2), the
 convolutions and linears between the FPN and detector.detections_from_heads.  By default inference only (HIP: csrc/kernels_dethead.hip, cosy_head_pack and
 cosy_head_conv).  DetectorHeads(..., trainable=True) are float32 heads with parameters and a backward on the same matrix pipe, behind autograd
-(HIP: csrc/kernels_detheadbwd.hip); the trunk's backward is detector_trunk_backward.py (section 29).
+(HIP: csrc/kernels_detbwd.hip, which the trunk's backward, detector_trunk_backward.py (section 29), runs too).
 
 Every layer is one implicit GEMM over ROWS: a row is one cell (level, image, y, x) with its channels contiguous in the storage type (float32,
 float16 or bfloat16; a linear layer's row is its input vector).  The heads' inputs arrive as contiguous NCHW float32 (what the FPN and
@@ -134,13 +134,30 @@ def transposed_weight(kind, weight):
     raise ValueError(f'kind must be conv, linear or deconv, got {kind}')
 
 
-class TrainableLayer:
+class PackedOnDevice:
+    """What a trainable layer of the heads and one of the trunk share: parameters() on self.device, and w / bias / w_t that _pack() writes from
+    them on the device."""
+
+    def refresh(self, dev=None):
+        """pack on the device when a parameter's _version (or its storage) has moved since the last pack, and not otherwise"""
+        if dev is not None and torch.device(dev) != self.device:
+            raise ValueError(f'the input lives on {dev}, the parameters on {self.device}: build the {self.owner} with device={dev!s}')
+        now = tuple((p._version, p.data_ptr()) for p in self.parameters())
+        if now != self.versions:
+            with torch.cuda.device(self.device):
+                self._pack()
+            self.versions = now
+            self.counter[0] += 1
+        return self
+
+
+class TrainableLayer(PackedOnDevice):
     """A layer of trainable heads, float32: its parameters are torch.nn.Parameters on the device in torchvision's layout
     (one (weight, bias) pair, or the two siblings of one GEMM); w / bias (what cosy_head_conv reads) and w_t (the transposed, tap-flipped
     packing the data gradient reads) are written by cosy_head_weight_pack on the device, when a parameter has moved since the last pack.
     kind, ksize, relu, c_in, c_out, n_out as HeadLayer; grad_ksize: 3, 1, or 2 for the deconvolution; n_grad: the outputs o of the gradient
     rows (deconv: C_o, else c_out)."""
-    dtype = torch.float32
+    dtype, owner = torch.float32, 'heads'
 
     def __init__(self, kind, pairs, relu, device, counter=None):
         if device is None or torch.device(device).type != 'cuda':
@@ -192,20 +209,11 @@ class TrainableLayer:
     def parameters(self):
         return [p for pair in self.pairs for p in pair]
 
-    def refresh(self, dev=None):
-        """pack on the device when a parameter's _version (or its storage) has moved since the last pack, and not otherwise"""
-        if dev is not None and torch.device(dev) != self.device:
-            raise ValueError(f'the input lives on {dev}, the parameters on {self.device}: build the heads with device={dev!s}')
-        now = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        if now != self.versions:
-            (w0, b0), (w1, b1) = self.pairs[0], (self.pairs[1] if len(self.pairs) == 2 else (None, None))
-            n0 = int(w0.shape[1] if self.kind == 'deconv' else w0.shape[0])
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().cosy_head_weight_pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0,
-                                                            _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
-            self.versions = now
-            self.counter[0] += 1
-        return self
+    def _pack(self):
+        (w0, b0), (w1, b1) = self.pairs[0], (self.pairs[1] if len(self.pairs) == 2 else (None, None))
+        n0 = int(w0.shape[1] if self.kind == 'deconv' else w0.shape[0])
+        _lib.check(_lib.lib().cosy_head_weight_pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0,
+                                                    _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
 
     @classmethod
     def conv(cls, weight, bias=None, relu=False, device=None, counter=None):
@@ -270,12 +278,8 @@ def _pack(x, rows, B, C, HW, dtype):
         _lib.check(_lib.lib().cosy_head_pack(_lib.ptr(x), rows.data_ptr(), B, C, HW, _DTYPES[dtype], _lib.stream()))
 
 
-def _gemm(layer, x_rows, maps, store, out, out1=None, n_split=None):
-    """one launch of layer over x_rows; maps: [(images, H, W)] per level, in row order"""
-    d = _lib.HeadLayer()
-    d.x, d.w, d.bias, d.out, d.out1 = _lib.ptr(x_rows), _lib.ptr(layer.w), _lib.ptr(layer.bias), _lib.ptr(out), _lib.ptr(out1)
-    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[layer.dtype], layer.ksize, layer.c_in, layer.c_out, int(layer.relu), store
-    d.n_split = layer.c_out if n_split is None else n_split
+def _describe(d, maps):
+    """the maps of a launch in its descriptor; maps: [(images, H, W)] per level, in row order -> the rows they hold"""
     d.n_levels = len(maps)
     row = 0
     for l, (n, H, W) in enumerate(maps):
@@ -284,7 +288,16 @@ def _gemm(layer, x_rows, maps, store, out, out1=None, n_split=None):
         if row > MAX_ROWS:
             raise ValueError(f'{row} rows (cells of all maps) exceed the limit of 2^30 per launch')
     d.row_start[len(maps)] = row
-    if row:
+    return row
+
+
+def _gemm(layer, x_rows, maps, store, out, out1=None, n_split=None):
+    """one launch of layer over x_rows; maps: [(images, H, W)] per level, in row order"""
+    d = _lib.HeadLayer()
+    d.x, d.w, d.bias, d.out, d.out1 = _lib.ptr(x_rows), _lib.ptr(layer.w), _lib.ptr(layer.bias), _lib.ptr(out), _lib.ptr(out1)
+    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[layer.dtype], layer.ksize, layer.c_in, layer.c_out, int(layer.relu), store
+    d.n_split = layer.c_out if n_split is None else n_split
+    if _describe(d, maps):
         _lib.check(_lib.lib().cosy_head_conv(ctypes.byref(d), _lib.stream()))
     return out
 
@@ -323,18 +336,6 @@ def wgrad_slab_rows(M):
     return int(_lib.lib().cosy_head_wgrad_slab_rows(int(M)))
 
 
-def _describe(d, maps):
-    d.n_levels = len(maps)
-    row = 0
-    for l, (n, H, W) in enumerate(maps):
-        d.row_start[l], d.H[l], d.W[l] = row, H, W
-        row += n * H * W
-        if row > MAX_ROWS:
-            raise ValueError(f'{row} rows (cells of all maps) exceed the limit of 2^30 per launch')
-    d.row_start[len(maps)] = row
-    return row
-
-
 def _grad_pack(g0, g1, rows, B, n0, n1, HW):
     """NCHW float32 gradients of a sibling pair (or of one tensor, n1 = 0; None: zeros) -> rows (B HW, pad8(n0 + n1)), one launch"""
     for g, n in ((g0, n0), (g1, n1)):
@@ -357,18 +358,21 @@ def _dgrad(layer, g_rows, maps, store, out, y=None):
     return out
 
 
+def _wgrad_buffers(layer, M, ksize, c_out):
+    """what a weight gradient over M cells writes: the gradients in the parameters' layout, the slabs' workspace and its bytes"""
+    need = int(_lib.lib().cosy_head_wgrad_workspace_bytes(M, ksize, layer.c_in, c_out))
+    if M and not need:
+        raise ValueError(f'the weight gradient of {M} cells, c_in={layer.c_in}, c_out={c_out} does not fit the library\'s limits')
+    return [torch.empty_like(p) for p in layer.parameters()], torch.empty(max(need // 4, 4), dtype=torch.float32, device=layer.device), need
+
+
 def _wgrad(layer, x_rows, g_rows, maps):
     """-> [dW, db] per parameter pair of layer, float32 in the parameters' own layout; maps: those of x_rows"""
     d = _lib.HeadLayer()
     d.x = _lib.ptr(x_rows)
     d.dtype, d.ksize, d.c_in, d.c_out = _DTYPES[torch.float32], layer.grad_ksize, layer.c_in, layer.n_grad
     d.n_split = getattr(layer, 'n_split', layer.n_grad)
-    M = _describe(d, maps)
-    out = [torch.empty_like(p) for p in layer.parameters()]
-    need = int(_lib.lib().cosy_head_wgrad_workspace_bytes(M, layer.grad_ksize, layer.c_in, layer.n_grad))
-    if M and not need:
-        raise ValueError(f'the weight gradient of {M} rows, c_in={layer.c_in}, c_out={layer.n_grad} does not fit the library\'s limits')
-    ws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=layer.device)
+    out, ws, need = _wgrad_buffers(layer, _describe(d, maps), layer.grad_ksize, layer.n_grad)
     _lib.check(_lib.lib().cosy_head_wgrad(ctypes.byref(d), _lib.ptr(g_rows), *[_lib.ptr(t) for t in (out + [None, None])[:4]], _lib.ptr(ws), need, _lib.stream()))
     return out
 

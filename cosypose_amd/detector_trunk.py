@@ -17,7 +17,7 @@ import re
 import torch
 
 from . import _lib
-from .detector_heads import HeadLayer, _check_input, _dtype, _gemm, _pack, _ready, MAX_ROWS
+from .detector_heads import HeadLayer, _check_input, _describe, _dtype, _gemm, _pack, _ready, MAX_ROWS
 
 _DTYPES = _lib.DTYPES
 STEM_ROW = 152                                # 7 x 7 x 3 = 147 taps x channels of the stem, padded to a multiple of 8
@@ -86,10 +86,8 @@ def _trunk_gemm(layer, x_rows, B, H, W, out, store=_lib.HEAD_STORE_ROWS, residua
     d = _lib.HeadLayer()
     d.x, d.w, d.bias, d.out, d.out1 = _lib.ptr(x_rows), _lib.ptr(layer.w), _lib.ptr(layer.bias), _lib.ptr(out), None
     d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[layer.dtype], layer.ksize, layer.c_in, layer.c_out, int(layer.relu), store
-    d.n_split, d.n_levels = layer.c_out, 1
-    if B * H * W > MAX_ROWS:
-        raise ValueError(f'{B * H * W} rows (cells of all maps) exceed the limit of 2^30 per launch')
-    d.row_start[0], d.row_start[1], d.H[0], d.W[0] = 0, B * H * W, H, W
+    d.n_split = layer.c_out
+    _describe(d, [(B, H, W)])
     rh, rw = res_hw if residual is not None else (0, 0)
     if B:
         _lib.check(_lib.lib().cosy_trunk_conv(ctypes.byref(d), layer.stride, _lib.ptr(layer.scale), _lib.ptr(residual), rh, rw, _lib.stream()))

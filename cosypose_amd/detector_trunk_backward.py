@@ -1,5 +1,5 @@
 """The backward of the detector's trunk on the matrix pipe, float32 only: the data and weight gradients of the ResNet
-bottlenecks and the FPN as GEMMs (HIP: csrc/kernels_dettrunkbwd.hip -- cosy_trunk_weight_pack, cosy_trunk_dgrad, cosy_trunk_wgrad), the
+bottlenecks and the FPN as GEMMs (HIP: csrc/kernels_detbwd.hip, the heads' gradient kernels -- cosy_trunk_weight_pack, cosy_trunk_dgrad, cosy_trunk_wgrad), the
 trainable layer that holds a trunk parameter, and the autograd node behind DetectorTrunk(trainable=True).
 
 A trunk layer is v = fmaf(conv_stride(x, W), scale, shift) [+ r], y = relu(v).  Its gradient rows g are the gradient at v, float32 rows on
@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .detector_heads import MAX_ROWS, _g, _grad_pack, _gemm
+from .detector_heads import MAX_ROWS, PackedOnDevice, _describe, _g, _grad_pack, _gemm, _wgrad_buffers
 
 F32 = torch.float32
 SAME, EVEN, NEAREST_T = _lib.TRUNK_ADD_SAME, _lib.TRUNK_ADD_EVEN, _lib.TRUNK_ADD_NEAREST_T
@@ -23,12 +23,12 @@ def _out(n, stride):
     return (n - 1) // stride + 1
 
 
-class TrainableTrunkLayer:
+class TrainableTrunkLayer(PackedOnDevice):
     """A trainable convolution of the trunk: weight is a torch.nn.Parameter (O,C,k,k) on the device under torchvision's name; a layer followed
     by FrozenBatchNorm keeps its scale and shift as constants, an FPN layer has a bias Parameter and no scale.  w / bias (what cosy_trunk_conv
     and cosy_head_conv read, the host packing's bytes) and w_t (the transposed, tap-flipped packing of ws = w scale[o]) are written by
     cosy_trunk_weight_pack when a parameter's _version or storage has moved since the last pack."""
-    kind, dtype = 'conv', F32
+    kind, dtype, owner = 'conv', F32, 'trunk'
 
     def __init__(self, name, weight, bn=None, bias=None, stride=1, relu=False, device=None, counter=None):
         from .detector_trunk import frozen_bn
@@ -71,40 +71,25 @@ class TrainableTrunkLayer:
     def parameters(self):
         return [self.weight] + ([self.bias_param] if self.bias_param is not None else [])
 
-    def refresh(self, dev=None):
-        if dev is not None and torch.device(dev) != self.device:
-            raise ValueError(f'the input lives on {dev}, the parameters on {self.device}: build the trunk with device={dev!s}')
-        now = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        if now != self.versions:
-            shift = self.shift if self.bias_param is None else self.bias_param
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().cosy_trunk_weight_pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out,
-                                                             _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
-            self.versions = now
-            self.counter[0] += 1
-        return self
+    def _pack(self):
+        shift = self.shift if self.bias_param is None else self.bias_param
+        _lib.check(_lib.lib().cosy_trunk_weight_pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out,
+                                                     _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
 
-    ready = refresh
+    ready = PackedOnDevice.refresh
 
     def out_size(self, H, W):
         return _out(H, self.stride), _out(W, self.stride)
 
 
 # ---- launches ------------------------------------------------------------------------------------------------------------------------
-def _one_level(d, B, H, W):
-    if B * H * W > MAX_ROWS:
-        raise ValueError(f'{B * H * W} rows (cells of all maps) exceed the limit of 2^30 per launch')
-    d.n_levels = 1
-    d.row_start[0], d.row_start[1], d.H[0], d.W[0] = 0, B * H * W, H, W
-
-
 def trunk_dgrad(layer, g_rows, B, H, W, out, adds=(), y=None, store=_lib.HEAD_STORE_ROWS, stride=None):
     """one cosy_trunk_dgrad call: g_rows on the layer's output grid -> dX on B maps of H x W cells.  adds: up to two (rule, rows, H, W);
     y: the mask rows on the dX grid.  stride: the layer's own unless given (downsample.0 runs at stride 1 on its output grid)"""
     d = _lib.HeadLayer()
     d.x, d.w, d.out = _lib.ptr(g_rows), _lib.ptr(layer.w_t), _lib.ptr(out)
     d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_out, layer.c_in, 0, store, layer.c_in
-    _one_level(d, B, H, W)
+    _describe(d, [(B, H, W)])
     adds = list(adds)
     if len(adds) > 2:
         raise ValueError(f'a data-gradient store takes at most two add operands, got {len(adds)}')
@@ -120,14 +105,9 @@ def trunk_wgrad(layer, x_rows, g_rows, B, H, W):
     d = _lib.HeadLayer()
     d.x = _lib.ptr(x_rows)
     d.dtype, d.ksize, d.c_in, d.c_out, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_in, layer.c_out, layer.c_out
-    _one_level(d, B, H, W)
+    _describe(d, [(B, H, W)])
     Ho, Wo = layer.out_size(H, W)
-    T = B * Ho * Wo
-    out = [torch.empty_like(p) for p in layer.parameters()]
-    need = int(_lib.lib().cosy_head_wgrad_workspace_bytes(T, layer.ksize, layer.c_in, layer.c_out))
-    if T and not need:
-        raise ValueError(f'the weight gradient of {T} cells, c_in={layer.c_in}, c_out={layer.c_out} does not fit the library\'s limits')
-    ws = torch.empty(max(need // 4, 4), dtype=F32, device=layer.device)
+    out, ws, need = _wgrad_buffers(layer, B * Ho * Wo, layer.ksize, layer.c_out)
     _lib.check(_lib.lib().cosy_trunk_wgrad(ctypes.byref(d), layer.stride, _lib.ptr(g_rows), _lib.ptr(layer.scale), _lib.ptr(out[0]),
                                            _lib.ptr(out[1]) if len(out) > 1 else None, _lib.ptr(ws), need, _lib.stream()))
     return out

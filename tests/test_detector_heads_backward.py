@@ -1,4 +1,4 @@
-"""The backward of the detector's heads on the GPU (csrc/kernels_detheadbwd.hip behind cosypose_amd/detector_heads.py)
+"""The backward of the detector's heads on the GPU (csrc/kernels_detbwd.hip behind cosypose_amd/detector_heads.py)
 against the CPU twin tests/detheadbwd_ref.py, which test_detector_heads_backward_host.py holds against torch.autograd in float64.
 
 Criteria.  Data gradient: BIT-equal to the twin's fmaf chain (the forward GEMM's order over the transposed, flipped weight).  Weight and bias

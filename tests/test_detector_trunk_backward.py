@@ -1,4 +1,4 @@
-"""The backward of the detector's trunk on the GPU (csrc/kernels_dettrunkbwd.hip behind cosypose_amd/detector_trunk_backward.py, DESIGN.md
+"""The backward of the detector's trunk on the GPU (csrc/kernels_detbwd.hip behind cosypose_amd/detector_trunk_backward.py, DESIGN.md
 section 29) against the CPU twin tests/dettrunkbwd_ref.py, which test_detector_trunk_backward_host.py holds against torch.autograd in float64.
 
 Criteria.  Data gradient, with its add operands and its mask: BIT-equal to the twin's fmaf chain.  Weight gradient against the twin's float64 sums
@@ -141,6 +141,30 @@ def test_the_device_weight_pack_writes_the_host_packings_bytes():
         tl = trainable(layer).refresh()
         assert np.array_equal(bits(host(tl.w)), bits(ref.pack_fwd(layer))) and np.array_equal(bits(host(tl.w_t)), bits(ref.pack_bwd(layer))), c[0]
         assert np.array_equal(bits(host(tl.bias)), bits(ref.pack_bias(layer))), c[0]
+
+
+# (name, ksize, c_in, c_out, (maps, H, W)): 3x3 with a partial channel group and every border tap; a 1x1 over 515 = 2 SLAB + 3 cells (three slabs,
+# the last partial) whose second four-tile channel group is partial; a 3x3 whose maps are all border.  c_out % 8 == 0: both sides take it
+SHARED = [('3x3 40->24 on 2 maps of 5x7', 3, 40, 24, (2, 5, 7)), ('1x1 88->24 on 1x515', 1, 88, 24, (1, 1, 515)), ('3x3 8->24 on 2 maps of 1x2', 3, 8, 24, (2, 1, 2))]
+
+
+@pytest.mark.parametrize('c', SHARED, ids=lambda c: c[0].replace(' ', '_'))
+def test_the_heads_and_the_trunks_entry_points_are_one_function(c):
+    """cosy_head_weight_pack / _wgrad / _dgrad and cosy_trunk_weight_pack / _wgrad / _dgrad (stride 1, no scale, no add operand) end in the same
+    kernels of csrc/kernels_detbwd.hip: the same parameters, x and g give the same BITS on both sides."""
+    from cosypose_amd import TrainableLayer, layer_backward
+    name, k, C, O, (B, H, W) = c
+    rng = np.random.RandomState(28 + C)
+    w, b = torch.from_numpy(rng.randn(O, C, k, k).astype(np.float32)), torch.from_numpy(rng.randn(O).astype(np.float32))
+    x, g = dev(rng.randn(B, C, H, W).astype(np.float32)), dev(rng.randn(B, O, H, W).astype(np.float32))
+    head = TrainableLayer.conv(w, b, device='cuda')
+    trunk = TrainableTrunkLayer('shared', w, bias=b, stride=1, device='cuda')
+    dx, (dw, db) = layer_backward(head, x, g)
+    tw = layer_wgrad(trunk, x, g)
+    tx = layer_dgrad(trunk, g, H, W)
+    assert len(tw) == 2
+    for what, got, want in (('dW', tw[0], dw), ('db', tw[1], db), ('dX', tx, dx), ('w', trunk.w, head.w), ('bias', trunk.bias, head.bias), ('w_t', trunk.w_t, head.w_t)):
+        same_bits(f'{name} {what}', host(got), host(want))
 
 
 # ---- the whole trunk -----------------------------------------------------------------------------------------------------------------------
