@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libcosyhip.so')
 HEADER = os.path.normpath(os.path.join(HERE, '..', 'include', 'cosyhip.h'))     # the C ABI's one declaration (_lib.py binds from it)
-SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_dethead.hip', 'kernels_dettrunk.hip', 'kernels_detbwd.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
+SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_dethead.hip', 'kernels_dettrunk.hip', 'kernels_detbwd.hip', 'kernels_detbwd16.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
            'kernels_dw.hip', 'kernels_wave.hip', 'kernels_stem.hip', 'kernels_smx.hip', 'effnet.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # No packed-fp32 arithmetic (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) anywhere in the library.  Round 4: a wave's packed-fp32 results were WRONG while

@@ -1,0 +1,275 @@
+// The trunk's data gradient as a template over the type of its rows (DESIGN.md sections 29 and 30): the forward GEMM's chain over the rows g
+// with the transposed, tap-flipped weight, the parity classes of a stride-2 layer, and the store that adds up to two operands (SAME, EVEN,
+// NEAREST_T), applies the ReLU mask of the layer below and converts ONCE to the rows' type.  kernels_detbwd.hip instantiates it for float32 rows
+// (cosy_head_dgrad, cosy_trunk_dgrad: the instruction streams hipcc gave that file's own text of the kernel, kernel for kernel),
+// kernels_detbwd16.hip for bfloat16 rows (cosy_trunk_dgrad16).
+//   float32 rows: every term of a block is one fmaf, four v_mfma_f32_16x16x4_f32 per (block of 16 o, live tap).
+//   16-bit rows: one v_mfma_f32_16x16x32 per (block of 32 o, live tap); the products are exact in float32, the accumulation is float32.
+// Store, per element: t = acc; t = t + (float)operand, in the order given, every + one rounded float32 add; t = y <= 0 ? +0.0 : t (a NaN y
+// passes t); then one conversion to T (round to nearest even).  No atomics, no LDS: equal inputs give equal bits.
+#pragma once
+#include "dethead_device.h"
+
+namespace cosy {
+namespace detbwd {
+
+using namespace headgemm;
+
+// kernels_detbwd.hip: the weight gradient's slab rule (cosy_head_wgrad_slab_rows, cosy_head_wgrad_workspace_bytes) and its second pass, which
+// adds the slabs' float32 partial tiles in ascending order, multiplies by scale[o] once and writes torchvision's layout
+int wgrad_slab_rows_of(int M);
+long wgrad_slab_floats_of(int ksize, int c_in, int c_out);
+int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s);
+
+enum { ADD_NONE = 0, ADD_SAME = COSY_TRUNK_ADD_SAME, ADD_EVEN = COSY_TRUNK_ADD_EVEN, ADD_NEAREST_T = COSY_TRUNK_ADD_NEAREST_T };
+
+template <typename T> struct tadd_t {
+    const T* rows;                           // rows of c_out channels on maps of H x W per image
+    int rule, H, W;
+    float sy, sx;                            // NEAREST_T: (float)H_target / H, divided once on the host
+};
+template <typename T> struct tgrad_epi_t {
+    const T* y;                              // rows on the dX grid, or null
+    tadd_t<T> add[2];
+    int par_y, par_x;                        // stride 2: the parity class of (iy, ix) this launch owns
+};
+
+// the finer cells [lo, hi) of one axis whose section 27 source cell is `cell`: nearest_src is monotone, so they are one contiguous range
+__device__ __forceinline__ void nearest_range(int cell, float scale, int size, int fine, int& lo, int& hi) {
+    int f = (int)((long)cell * fine / size);
+    if (f > fine) f = fine;
+    while (f > 0 && nearest_src(f - 1, scale, size) >= cell) --f;
+    while (f < fine && nearest_src(f, scale, size) < cell) ++f;
+    lo = f;
+    while (f < fine && nearest_src(f, scale, size) == cell) ++f;
+    hi = f;
+}
+
+template <typename T, int MT, int NT, int STRIDE>
+__global__ __launch_bounds__(HEAD_THREADS) void dgrad_rows_kernel(const cosy_head_layer_t a, const int M, const int KBn, const int n_tiles, const int n_groups,
+                                                                  const tgrad_epi_t<T> e) {
+    typedef typename DT<T>::raw_t frag_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, g = lane >> 4;
+    const unsigned total = gridDim.x, q8 = total / 8, rem = total % 8, xcd = blockIdx.x % 8, slot = blockIdx.x / 8;      // dethead_device.h's XCD remap
+    const unsigned v = xcd * q8 + (xcd < rem ? xcd : rem) + slot;
+    const int row0 = (int)((v / n_groups) * (HEAD_THREADS / 64) + wave) * 16 * MT;
+    if (row0 >= M) return;                                     // wave-uniform
+    const int nt0 = (int)(v % n_groups) * NT;
+    const int O = a.c_in, N = a.c_out;                         // the reduction runs over the layer's outputs o; the result's columns are its inputs c
+    const T* __restrict__ x = (const T*)a.x;
+    const frag_t* __restrict__ w = (const frag_t*)a.w;
+    const int taps = a.ksize == 3 ? 9 : 1;
+    const long S = (long)taps * KBn;
+
+    // this lane's cell of the dX grid: pH, pW its map (0: no such row), pb the image, py, px the cell, prs the level's first row
+    int r[MT], py[MT], px[MT], pH[MT], pW[MT], pb[MT], prs[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        r[mt] = row0 + mt * 16 + j;
+        pH[mt] = 0; pW[mt] = 0; py[mt] = 0; px[mt] = 0; pb[mt] = 0; prs[mt] = 0;
+        if (r[mt] < M) {
+            if constexpr (STRIDE == 1) {
+                int l = 0;
+                while (l + 1 < a.n_levels && r[mt] >= a.row_start[l + 1]) ++l;
+                const int H = a.H[l], W = a.W[l], rr = r[mt] - a.row_start[l];
+                const int pix = rr % (H * W);
+                pH[mt] = H; pW[mt] = W; prs[mt] = a.row_start[l];
+                pb[mt] = rr / (H * W); py[mt] = pix / W; px[mt] = pix - py[mt] * W;
+            } else {                                           // one level; the rows are the cells of one parity class
+                const int H = a.H[0], W = a.W[0], nY = (H + 1 - e.par_y) / 2, nX = (W + 1 - e.par_x) / 2;
+                const int pix = r[mt] % (nY * nX), cy = pix / nX;
+                pH[mt] = H; pW[mt] = W;
+                pb[mt] = r[mt] / (nY * nX); py[mt] = 2 * cy + e.par_y; px[mt] = 2 * (pix - cy * nX) + e.par_x;
+            }
+        }
+    }
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kb = 0; kb < KBn; ++kb) {
+        for (int tap = 0; tap < taps; ++tap) {
+            const int ey = taps == 9 ? tap / 3 - 1 : 0, ex = taps == 9 ? tap - (tap / 3) * 3 - 1 : 0;      // g lives at the cell + (ey, ex)
+            if constexpr (STRIDE == 2)
+                if (((ey + e.par_y) & 1) || ((ex + e.par_x) & 1)) continue;                                // a dead tap of this class: no MFMA (wave-uniform)
+            const long s = (long)tap * KBn + kb;
+            frag_t xf[MT], wf[NT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                if constexpr (STRIDE == 1) {
+                    const bool in = (unsigned)(py[mt] + ey) < (unsigned)pH[mt] && (unsigned)(px[mt] + ex) < (unsigned)pW[mt];
+                    xf[mt] = load_x<T>(x, in ? (long)(r[mt] + ey * pW[mt] + ex) * O : -1, kb, g, O);
+                } else {
+                    const int Ho = (pH[mt] - 1) / 2 + 1, Wo = (pW[mt] - 1) / 2 + 1;
+                    const int oy = (py[mt] + ey) >> 1, ox = (px[mt] + ex) >> 1;                            // py + ey is even and >= 0 for a live tap
+                    const bool in = pH[mt] != 0 && oy < Ho && ox < Wo;
+                    xf[mt] = load_x<T>(x, in ? (((long)pb[mt] * Ho + oy) * Wo + ox) * O : -1, kb, g, O);
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) wf[nt] = nt0 + nt < n_tiles ? w[((long)(nt0 + nt) * S + s) * 64 + lane] : zero_frag<T>();
+            if constexpr (sizeof(T) == 4) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        if (nt0 + nt < n_tiles)                // wave-uniform
+#pragma unroll
+                            for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[nt][t], xf[mt][t], acc[mt][nt], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    if (nt0 + nt < n_tiles)                    // wave-uniform
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) mma(acc[mt][nt], wf[nt], xf[mt]);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (pH[mt] == 0) continue;
+        const int H = pH[mt], W = pW[mt], iy = py[mt], ix = px[mt];
+        const long cell = (long)prs[mt] + ((long)pb[mt] * H + iy) * W + ix;                                // the row of the dX grid
+        // the operands' rows of this cell: [lo, hi) ranges of the operand's grid, empty where the rule leaves the cell untouched
+        int ylo[2], yhi[2], xlo[2], xhi[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            ylo[k] = yhi[k] = xlo[k] = xhi[k] = 0;
+            const tadd_t<T>& ad = e.add[k];
+            if (ad.rule == ADD_SAME) { ylo[k] = iy; yhi[k] = iy + 1; xlo[k] = ix; xhi[k] = ix + 1; }
+            else if (ad.rule == ADD_EVEN) {
+                if (!(iy & 1) && !(ix & 1)) { ylo[k] = iy >> 1; yhi[k] = ylo[k] + 1; xlo[k] = ix >> 1; xhi[k] = xlo[k] + 1; }
+            } else if (ad.rule == ADD_NEAREST_T) {
+                nearest_range(iy, ad.sy, H, ad.H, ylo[k], yhi[k]);
+                nearest_range(ix, ad.sx, W, ad.W, xlo[k], xhi[k]);
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int col0 = (nt0 + nt) * 16 + 4 * g;
+            if (nt0 + nt >= n_tiles || col0 >= N) continue;
+            float t[4] = {acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const tadd_t<T>& ad = e.add[k];
+                if (ad.rule == ADD_NONE) continue;
+                for (int fy = ylo[k]; fy < yhi[k]; ++fy)
+                    for (int fx = xlo[k]; fx < xhi[k]; ++fx) {
+                        float rv[4];
+                        load4(ad.rows + (((long)pb[mt] * ad.H + fy) * ad.W + fx) * N + col0, rv);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) t[q] = t[q] + rv[q];
+                    }
+            }
+            if (e.y != nullptr) {
+                float yv[4];
+                load4(e.y + cell * N + col0, yv);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[q] = yv[q] <= 0.f ? 0.f : t[q];
+            }
+            if (a.store == COSY_HEAD_STORE_ROWS) {
+                put4((T*)a.out + cell * N + col0, t);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    ((float*)a.out)[(long)N * prs[mt] + (((long)pb[mt] * N + col0 + q) * H + iy) * W + ix] = t[q];
+            }
+        }
+    }
+}
+
+// fn: the entry point the caller called; its name opens every message
+template <typename T, int STRIDE> int launch_dgrad_rows(const char* fn, const cosy_head_layer_t& a, int M, const tgrad_epi_t<T>& e, hipStream_t s) {
+    const conv_grid_t c = conv_grid<T>(a, M);
+    COSY_REQUIRE(c.blocks <= 0x7fffffffL, "%s: %d rows x c_out=%d need more than 2^31 - 1 workgroups", fn, M, a.c_out);
+    const dim3 grid((unsigned)c.blocks), block(HEAD_THREADS);
+    if (c.big_m && c.big_n) hipLaunchKernelGGL((dgrad_rows_kernel<T, TILE_MT_BIG, TILE_NT_BIG, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_m) hipLaunchKernelGGL((dgrad_rows_kernel<T, TILE_MT_BIG, 1, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_n) hipLaunchKernelGGL((dgrad_rows_kernel<T, 1, TILE_NT_BIG, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else hipLaunchKernelGGL((dgrad_rows_kernel<T, 1, 1, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+// what every entry point asks of the layer's maps alike; -> the rows the levels hold, or -1 after set_error
+inline long check_levels(const char* fn, const cosy_head_layer_t& a) {
+    if (!(a.n_levels >= 1 && a.n_levels <= COSY_RPN_MAX_LEVELS)) { set_error("%s: n_levels=%d must lie in [1, %d]", fn, a.n_levels, COSY_RPN_MAX_LEVELS); return -1; }
+    if (a.row_start[0] != 0) { set_error("%s: row_start[0]=%d must be 0", fn, a.row_start[0]); return -1; }
+    for (int l = 0; l < a.n_levels; ++l) {
+        if (!(a.H[l] >= 1 && a.W[l] >= 1 && (long)a.H[l] * a.W[l] <= HEAD_MAX_ROWS)) { set_error("%s: level %d is %d x %d cells", fn, l, a.H[l], a.W[l]); return -1; }
+        const long n = (long)a.row_start[l + 1] - a.row_start[l];
+        if (!(n >= 0 && n % ((long)a.H[l] * a.W[l]) == 0)) {
+            set_error("%s: level %d owns %ld rows, not whole maps of %d x %d cells", fn, l, n, a.H[l], a.W[l]);
+            return -1;
+        }
+    }
+    const long M = a.row_start[a.n_levels];
+    if (M > HEAD_MAX_ROWS) { set_error("%s: %ld rows exceed 2^30", fn, M); return -1; }
+    return M;
+}
+
+// cosy_trunk_dgrad's contract (cosyhip.h) on rows of T, after the caller's check of the layer pointer and of dtype: the argument checks, the
+// operands' grids and the one launch (stride 1) or the four parity-class launches (stride 2)
+template <typename T> int run_trunk_dgrad(const char* fn, const cosy_head_layer_t& a, int stride, const T* add0, int rule0, int add0_H, int add0_W, const T* add1,
+                                          int rule1, int add1_H, int add1_W, const T* y, hipStream_t s) {
+    COSY_REQUIRE(a.ksize == 1 || a.ksize == 3, "%s: ksize=%d must be 1 or 3", fn, a.ksize);
+    COSY_REQUIRE(stride == 1 || stride == 2, "%s: stride=%d must be 1 or 2", fn, stride);
+    COSY_REQUIRE(!(stride == 2 && a.ksize == 1), "%s: a 1x1 at stride 2 is a stride-1 launch on its OUTPUT grid whose rows enter through "
+                 "COSY_TRUNK_ADD_EVEN, not a launch over the input grid", fn);
+    COSY_REQUIRE(a.c_in >= 8 && a.c_in % 8 == 0, "%s: the reduction length c_in=%d (the layer's output channels) must be a positive multiple of 8", fn, a.c_in);
+    COSY_REQUIRE(a.c_out >= 8 && a.c_out % 8 == 0, "%s: c_out=%d (the layer's input channels) must be a positive multiple of 8", fn, a.c_out);
+    COSY_REQUIRE(a.store == COSY_HEAD_STORE_ROWS || (sizeof(T) == 4 && a.store == COSY_HEAD_STORE_NCHW),
+                 sizeof(T) == 4 ? "%s: store=%d is not COSY_HEAD_STORE_ROWS or COSY_HEAD_STORE_NCHW" : "%s: store=%d is not COSY_HEAD_STORE_ROWS (16-bit rows have no NCHW store)",
+                 fn, a.store);
+    COSY_REQUIRE(a.relu == 0, "%s: relu=%d must be 0 (the mask is given by y)", fn, a.relu);
+    COSY_REQUIRE(a.store != COSY_HEAD_STORE_NCHW || a.n_split == a.c_out, "%s: an NCHW store takes n_split == c_out=%d", fn, a.c_out);
+    const long M_all = check_levels(fn, a);
+    if (M_all < 0) return COSY_EINVAL;
+    COSY_REQUIRE(stride == 1 || a.n_levels == 1, "%s: stride=2 takes one level, got n_levels=%d", fn, a.n_levels);
+    const int H = a.H[0], W = a.W[0];
+    const long B = M_all / ((long)H * W);                      // images of level 0 (the only level wherever B is used)
+    tgrad_epi_t<T> e;
+    e.y = y; e.par_y = 0; e.par_x = 0;
+    const T* rows[2] = {add0, add1};
+    const int rules[2] = {rule0, rule1}, aH[2] = {add0_H, add1_H}, aW[2] = {add0_W, add1_W};
+    for (int k = 0; k < 2; ++k) {
+        tadd_t<T>& ad = e.add[k];
+        ad.rows = rows[k]; ad.rule = rules[k]; ad.H = aH[k]; ad.W = aW[k]; ad.sy = 1.f; ad.sx = 1.f;
+        COSY_REQUIRE(ad.rule == ADD_NONE || ad.rule == ADD_SAME || ad.rule == ADD_EVEN || ad.rule == ADD_NEAREST_T,
+                     "%s: add operand %d: rule=%d is not COSY_TRUNK_ADD_NONE, _SAME, _EVEN or _NEAREST_T", fn, k, ad.rule);
+        if (ad.rule == ADD_NONE) { ad.rows = nullptr; ad.H = 1; ad.W = 1; continue; }
+        COSY_REQUIRE(a.n_levels == 1, "%s: an add operand takes one level, got n_levels=%d", fn, a.n_levels);
+        if (ad.rule == ADD_SAME) { ad.H = H; ad.W = W; }
+        if (ad.rule == ADD_EVEN)
+            COSY_REQUIRE(ad.H == (H - 1) / 2 + 1 && ad.W == (W - 1) / 2 + 1, "%s: add operand %d: an EVEN operand of %d x %d maps lives on %d x %d cells, got %d x %d",
+                         fn, k, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1, ad.H, ad.W);
+        if (ad.rule == ADD_NEAREST_T) {
+            COSY_REQUIRE(ad.H >= H && ad.W >= W && (long)ad.H * ad.W <= HEAD_MAX_ROWS, "%s: add operand %d: a NEAREST_T operand of %d x %d cells is coarser "
+                         "than the target's %d x %d (or too large)", fn, k, ad.H, ad.W, H, W);
+            COSY_REQUIRE(B * ad.H * ad.W <= HEAD_MAX_ROWS, "%s: add operand %d: its rows exceed 2^30", fn, k);
+            ad.sy = (float)H / (float)ad.H; ad.sx = (float)W / (float)ad.W;
+        }
+    }
+    if (M_all == 0) return COSY_OK;
+    COSY_REQUIRE(a.x != nullptr && a.w != nullptr && a.out != nullptr, "%s: null layer->x, w or out", fn);
+    for (int k = 0; k < 2; ++k) COSY_REQUIRE(e.add[k].rule == ADD_NONE || e.add[k].rows != nullptr, "%s: add operand %d: null rows with rule=%d", fn, k, e.add[k].rule);
+    COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)add0 & 15) == 0 &&
+                 ((uintptr_t)add1 & 15) == 0, "%s: x, w, out, y and the add operands must be 16-byte aligned", fn);
+    if (stride == 1) return launch_dgrad_rows<T, 1>(fn, a, (int)M_all, e, s);
+    for (int par = 0; par < 4; ++par) {                        // the four parity classes of (iy, ix): four row ranges, each with its fixed tap set
+        e.par_y = par >> 1; e.par_x = par & 1;
+        const long M = B * ((H + 1 - e.par_y) / 2) * ((W + 1 - e.par_x) / 2);
+        if (M == 0) continue;
+        const int rc = launch_dgrad_rows<T, 2>(fn, a, (int)M, e, s);
+        if (rc != COSY_OK) return rc;
+    }
+    return COSY_OK;
+}
+
+}  // namespace detbwd
+}  // namespace cosy

@@ -1,7 +1,7 @@
 // The backward of the detector on the matrix pipe, float32 only: the heads and the trunk (section 29) run ONE set of
 // gradient kernels.  A layer is v = conv_stride(x, W) [scale + shift] [+ r], y = act(v) (kernels_dethead.hip, kernels_dettrunk.hip); g is the
 // gradient at v, float32 rows on the layer's OUTPUT grid (heads: c_out rounded up to 8, the pad +0.0).
-//   * data gradient   dX[cell][c] = sum over (tap, o) of w[o][tap][c] g[cell - tap][o]: dgrad_kernel, the forward GEMM's chain (dethead_device.h:
+//   * data gradient   dX[cell][c] = sum over (tap, o) of w[o][tap][c] g[cell - tap][o]: detbwd_device.h's dgrad_rows_kernel<float>, the forward GEMM's chain (dethead_device.h:
 //     accumulator +0.0, blocks of 16 o ascending, the taps of the flipped packing ascending inside a block, every term one fmaf) over the rows g
 //     with the weight transposed and its taps flipped.  At stride 2 a launch owns ONE parity class of (iy, ix) and runs only that class's live
 //     taps (1, 2, 2 or 4 of 9).  Its store adds up to two operands (SAME, EVEN, NEAREST_T: the trunk's shortcuts and the FPN), applies the ReLU
@@ -14,12 +14,13 @@
 //   * grad_pack_kernel makes the rows g out of the losses' NCHW gradients; weight_pack_kernel makes both fragment-order weights (forward, and
 //     transposed + flipped [x scale[o], rounded once] for the data gradient) out of a parameter in torchvision's layout, on the device.
 // No atomics, no LDS: equal inputs give equal bits.
-#include "dethead_device.h"
+#include "detbwd_device.h"
 
 namespace cosy {
 namespace {
 
 using namespace headgemm;
+using namespace detbwd;                      // the data gradient: kernel, store rules and entry checks, one template over the type of the rows
 
 constexpr int WG_SLAB_MIN = 256;             // cells of a slab: at least this many, and at most WG_MAX_SLABS slabs
 constexpr int WG_MAX_SLABS = 16;
@@ -35,19 +36,6 @@ inline long wgrad_slab_floats(int ksize, int c_in, int c_out) {
     const long O16 = (c_out + 15) / 16 * 16, taps = ksize == 3 ? 9 : ksize == 2 ? 4 : 1;
     return O16 * taps * c_in + O16;
 }
-
-enum { ADD_NONE = 0, ADD_SAME = COSY_TRUNK_ADD_SAME, ADD_EVEN = COSY_TRUNK_ADD_EVEN, ADD_NEAREST_T = COSY_TRUNK_ADD_NEAREST_T };
-
-struct tadd_t {
-    const float* rows;                       // rows of c_out channels on maps of H x W per image
-    int rule, H, W;
-    float sy, sx;                            // NEAREST_T: (float)H_target / H, divided once on the host
-};
-struct tgrad_epi_t {
-    const float* y;                          // rows on the dX grid, or null
-    tadd_t add[2];
-    int par_y, par_x;                        // stride 2: the parity class of (iy, ix) this launch owns
-};
 
 // NCHW float32 (B, n0, HW) and (B, n1, HW) -> rows (B HW, GP): the columns of the first, then of the second, then +0.0.  A null tensor is zeros.
 __global__ __launch_bounds__(HEAD_THREADS) void head_grad_pack_kernel(const float* __restrict__ g0, const float* __restrict__ g1, float* __restrict__ rows,
@@ -105,147 +93,6 @@ __global__ __launch_bounds__(HEAD_THREADS) void weight_pack_kernel(const float* 
         float v = 0.f;
         if (o < O) v = o < n0 ? b0[o] : b1[o - n0];
         fwd_bias[n] = v;
-    }
-}
-
-// the finer cells [lo, hi) of one axis whose section 27 source cell is `cell`: nearest_src is monotone, so they are one contiguous range
-__device__ __forceinline__ void nearest_range(int cell, float scale, int size, int fine, int& lo, int& hi) {
-    int f = (int)((long)cell * fine / size);
-    if (f > fine) f = fine;
-    while (f > 0 && nearest_src(f - 1, scale, size) >= cell) --f;
-    while (f < fine && nearest_src(f, scale, size) < cell) ++f;
-    lo = f;
-    while (f < fine && nearest_src(f, scale, size) == cell) ++f;
-    hi = f;
-}
-
-template <int MT, int NT, int STRIDE>
-__global__ __launch_bounds__(HEAD_THREADS) void dgrad_kernel(const cosy_head_layer_t a, const int M, const int KBn, const int n_tiles, const int n_groups,
-                                                             const tgrad_epi_t e) {
-    typedef DT<float>::raw_t frag_t;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 15, g = lane >> 4;
-    const unsigned total = gridDim.x, q8 = total / 8, rem = total % 8, xcd = blockIdx.x % 8, slot = blockIdx.x / 8;      // dethead_device.h's XCD remap
-    const unsigned v = xcd * q8 + (xcd < rem ? xcd : rem) + slot;
-    const int row0 = (int)((v / n_groups) * (HEAD_THREADS / 64) + wave) * 16 * MT;
-    if (row0 >= M) return;                                     // wave-uniform
-    const int nt0 = (int)(v % n_groups) * NT;
-    const int O = a.c_in, N = a.c_out;                         // the reduction runs over the layer's outputs o; the result's columns are its inputs c
-    const float* __restrict__ x = (const float*)a.x;
-    const frag_t* __restrict__ w = (const frag_t*)a.w;
-    const int taps = a.ksize == 3 ? 9 : 1;
-    const long S = (long)taps * KBn;
-
-    // this lane's cell of the dX grid: pH, pW its map (0: no such row), pb the image, py, px the cell, prs the level's first row
-    int r[MT], py[MT], px[MT], pH[MT], pW[MT], pb[MT], prs[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        r[mt] = row0 + mt * 16 + j;
-        pH[mt] = 0; pW[mt] = 0; py[mt] = 0; px[mt] = 0; pb[mt] = 0; prs[mt] = 0;
-        if (r[mt] < M) {
-            if constexpr (STRIDE == 1) {
-                int l = 0;
-                while (l + 1 < a.n_levels && r[mt] >= a.row_start[l + 1]) ++l;
-                const int H = a.H[l], W = a.W[l], rr = r[mt] - a.row_start[l];
-                const int pix = rr % (H * W);
-                pH[mt] = H; pW[mt] = W; prs[mt] = a.row_start[l];
-                pb[mt] = rr / (H * W); py[mt] = pix / W; px[mt] = pix - py[mt] * W;
-            } else {                                           // one level; the rows are the cells of one parity class
-                const int H = a.H[0], W = a.W[0], nY = (H + 1 - e.par_y) / 2, nX = (W + 1 - e.par_x) / 2;
-                const int pix = r[mt] % (nY * nX), cy = pix / nX;
-                pH[mt] = H; pW[mt] = W;
-                pb[mt] = r[mt] / (nY * nX); py[mt] = 2 * cy + e.par_y; px[mt] = 2 * (pix - cy * nX) + e.par_x;
-            }
-        }
-    }
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kb = 0; kb < KBn; ++kb) {
-        for (int tap = 0; tap < taps; ++tap) {
-            const int ey = taps == 9 ? tap / 3 - 1 : 0, ex = taps == 9 ? tap - (tap / 3) * 3 - 1 : 0;      // g lives at the cell + (ey, ex)
-            if constexpr (STRIDE == 2)
-                if (((ey + e.par_y) & 1) || ((ex + e.par_x) & 1)) continue;                                // a dead tap of this class: no MFMA (wave-uniform)
-            const long s = (long)tap * KBn + kb;
-            frag_t xf[MT], wf[NT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                if constexpr (STRIDE == 1) {
-                    const bool in = (unsigned)(py[mt] + ey) < (unsigned)pH[mt] && (unsigned)(px[mt] + ex) < (unsigned)pW[mt];
-                    xf[mt] = load_x<float>(x, in ? (long)(r[mt] + ey * pW[mt] + ex) * O : -1, kb, g, O);
-                } else {
-                    const int Ho = (pH[mt] - 1) / 2 + 1, Wo = (pW[mt] - 1) / 2 + 1;
-                    const int oy = (py[mt] + ey) >> 1, ox = (px[mt] + ex) >> 1;                            // py + ey is even and >= 0 for a live tap
-                    const bool in = pH[mt] != 0 && oy < Ho && ox < Wo;
-                    xf[mt] = load_x<float>(x, in ? (((long)pb[mt] * Ho + oy) * Wo + ox) * O : -1, kb, g, O);
-                }
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wf[nt] = nt0 + nt < n_tiles ? w[((long)(nt0 + nt) * S + s) * 64 + lane] : zero_frag<float>();
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    if (nt0 + nt < n_tiles)                    // wave-uniform
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[nt][t], xf[mt][t], acc[mt][nt], 0, 0, 0);
-        }
-    }
-
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        if (pH[mt] == 0) continue;
-        const int H = pH[mt], W = pW[mt], iy = py[mt], ix = px[mt];
-        const long cell = (long)prs[mt] + ((long)pb[mt] * H + iy) * W + ix;                                // the row of the dX grid
-        // the operands' rows of this cell: [lo, hi) ranges of the operand's grid, empty where the rule leaves the cell untouched
-        int ylo[2], yhi[2], xlo[2], xhi[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            ylo[k] = yhi[k] = xlo[k] = xhi[k] = 0;
-            const tadd_t& ad = e.add[k];
-            if (ad.rule == ADD_SAME) { ylo[k] = iy; yhi[k] = iy + 1; xlo[k] = ix; xhi[k] = ix + 1; }
-            else if (ad.rule == ADD_EVEN) {
-                if (!(iy & 1) && !(ix & 1)) { ylo[k] = iy >> 1; yhi[k] = ylo[k] + 1; xlo[k] = ix >> 1; xhi[k] = xlo[k] + 1; }
-            } else if (ad.rule == ADD_NEAREST_T) {
-                nearest_range(iy, ad.sy, H, ad.H, ylo[k], yhi[k]);
-                nearest_range(ix, ad.sx, W, ad.W, xlo[k], xhi[k]);
-            }
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col0 = (nt0 + nt) * 16 + 4 * g;
-            if (nt0 + nt >= n_tiles || col0 >= N) continue;
-            float t[4] = {acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]};
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const tadd_t& ad = e.add[k];
-                if (ad.rule == ADD_NONE) continue;
-                for (int fy = ylo[k]; fy < yhi[k]; ++fy)
-                    for (int fx = xlo[k]; fx < xhi[k]; ++fx) {
-                        float rv[4];
-                        load4(ad.rows + (((long)pb[mt] * ad.H + fy) * ad.W + fx) * N + col0, rv);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) t[q] = t[q] + rv[q];
-                    }
-            }
-            if (e.y != nullptr) {
-                float yv[4];
-                load4(e.y + cell * N + col0, yv);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) t[q] = yv[q] <= 0.f ? 0.f : t[q];
-            }
-            if (a.store == COSY_HEAD_STORE_ROWS) {
-                put4((float*)a.out + cell * N + col0, t);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    ((float*)a.out)[(long)N * prs[mt] + (((long)pb[mt] * N + col0 + q) * H + iy) * W + ix] = t[q];
-            }
-        }
     }
 }
 
@@ -388,19 +235,6 @@ __global__ __launch_bounds__(HEAD_THREADS) void wgrad_combine_kernel(const float
     else dw1[((long)(o - n_split) * C + c) * T + t] = acc;
 }
 
-// fn: the entry point the caller called; its name opens every message
-template <int STRIDE> int launch_dgrad(const char* fn, const cosy_head_layer_t& a, int M, const tgrad_epi_t& e, hipStream_t s) {
-    const conv_grid_t c = conv_grid<float>(a, M);
-    COSY_REQUIRE(c.blocks <= 0x7fffffffL, "%s: %d rows x c_out=%d need more than 2^31 - 1 workgroups", fn, M, a.c_out);
-    const dim3 grid((unsigned)c.blocks), block(HEAD_THREADS);
-    if (c.big_m && c.big_n) hipLaunchKernelGGL((dgrad_kernel<TILE_MT_BIG, TILE_NT_BIG, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
-    else if (c.big_m) hipLaunchKernelGGL((dgrad_kernel<TILE_MT_BIG, 1, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
-    else if (c.big_n) hipLaunchKernelGGL((dgrad_kernel<1, TILE_NT_BIG, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
-    else hipLaunchKernelGGL((dgrad_kernel<1, 1, STRIDE>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
-    COSY_CHECK_HIP(hipGetLastError());
-    return COSY_OK;
-}
-
 // ConvTranspose2d(2, 2): M rows of the (H / 2, W / 2) maps, the four taps of the forward GEMM
 int launch_deconv_dgrad(const cosy_head_layer_t& a, int M, const float* y, hipStream_t s) {
     const conv_grid_t c = conv_grid<float>(a, M);
@@ -413,23 +247,6 @@ int launch_deconv_dgrad(const cosy_head_layer_t& a, int M, const float* y, hipSt
     else hipLaunchKernelGGL((conv_gemm_kernel<float, 1, 1, DeconvGradPolicy>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
-}
-
-// what every entry point asks of the layer's maps alike; -> the rows the levels hold, or -1 after set_error
-long check_levels(const char* fn, const cosy_head_layer_t& a) {
-    if (!(a.n_levels >= 1 && a.n_levels <= COSY_RPN_MAX_LEVELS)) { set_error("%s: n_levels=%d must lie in [1, %d]", fn, a.n_levels, COSY_RPN_MAX_LEVELS); return -1; }
-    if (a.row_start[0] != 0) { set_error("%s: row_start[0]=%d must be 0", fn, a.row_start[0]); return -1; }
-    for (int l = 0; l < a.n_levels; ++l) {
-        if (!(a.H[l] >= 1 && a.W[l] >= 1 && (long)a.H[l] * a.W[l] <= HEAD_MAX_ROWS)) { set_error("%s: level %d is %d x %d cells", fn, l, a.H[l], a.W[l]); return -1; }
-        const long n = (long)a.row_start[l + 1] - a.row_start[l];
-        if (!(n >= 0 && n % ((long)a.H[l] * a.W[l]) == 0)) {
-            set_error("%s: level %d owns %ld rows, not whole maps of %d x %d cells", fn, l, n, a.H[l], a.W[l]);
-            return -1;
-        }
-    }
-    const long M = a.row_start[a.n_levels];
-    if (M > HEAD_MAX_ROWS) { set_error("%s: %ld rows exceed 2^30", fn, M); return -1; }
-    return M;
 }
 
 // One weight gradient, planned and launched, after the caller's own argument checks: M OUTPUT cells (the k dimension) of a layer a.c_in ->
@@ -493,6 +310,20 @@ int run_weight_pack(const char* fn, const float* w0, const float* b0, const floa
 }
 
 }  // namespace
+
+// The slab rule and the second pass do not depend on the type of the rows: kernels_detbwd16.hip (section 30) reaches them here (host code only;
+// declared in detbwd_device.h).  One scale, no sibling: the trunk's form.
+namespace detbwd {
+int wgrad_slab_rows_of(int M) { return wgrad_slab_rows(M); }
+long wgrad_slab_floats_of(int ksize, int c_in, int c_out) { return wgrad_slab_floats(ksize, c_in, c_out); }
+int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s) {
+    const long n_out = (long)c_out * (ksize == 3 ? 9 : 1) * c_in + c_out;
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(cdiv(n_out, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, partial, nslab, slab_floats, ksize, c_in, c_out, c_out, scale,
+                       dw, db, (float*)nullptr, (float*)nullptr);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+}  // namespace detbwd
 }  // namespace cosy
 
 using namespace cosy;
@@ -570,8 +401,8 @@ int cosy_head_dgrad(const cosy_head_layer_t* layer, const float* y, cosy_stream_
     COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)y & 15) == 0,
                  "cosy_head_dgrad: x, w, out and y must be 16-byte aligned");
     if (a.ksize == 2) return launch_deconv_dgrad(a, (int)M, y, s);
-    const tadd_t none{nullptr, ADD_NONE, 1, 1, 1.f, 1.f};
-    return launch_dgrad<1>("cosy_head_dgrad", a, (int)M, tgrad_epi_t{y, {none, none}, 0, 0}, s);
+    const tadd_t<float> none{nullptr, ADD_NONE, 1, 1, 1.f, 1.f};
+    return launch_dgrad_rows<float, 1>("cosy_head_dgrad", a, (int)M, tgrad_epi_t<float>{y, {none, none}, 0, 0}, s);
 }
 
 int cosy_trunk_dgrad(const cosy_head_layer_t* layer, int stride, const float* add0, int rule0, int add0_H, int add0_W, const float* add1, int rule1, int add1_H,
@@ -580,57 +411,7 @@ int cosy_trunk_dgrad(const cosy_head_layer_t* layer, int stride, const float* ad
     COSY_REQUIRE_PTR("cosy_trunk_dgrad", layer);
     const cosy_head_layer_t& a = *layer;
     COSY_REQUIRE(a.dtype == COSY_F32, "cosy_trunk_dgrad: dtype=%d is not COSY_F32 (training is float32 only)", a.dtype);
-    COSY_REQUIRE(a.ksize == 1 || a.ksize == 3, "cosy_trunk_dgrad: ksize=%d must be 1 or 3", a.ksize);
-    COSY_REQUIRE(stride == 1 || stride == 2, "cosy_trunk_dgrad: stride=%d must be 1 or 2", stride);
-    COSY_REQUIRE(!(stride == 2 && a.ksize == 1), "cosy_trunk_dgrad: a 1x1 at stride 2 is a stride-1 launch on its OUTPUT grid whose rows enter through "
-                 "COSY_TRUNK_ADD_EVEN, not a launch over the input grid");
-    COSY_REQUIRE(a.c_in >= 8 && a.c_in % 8 == 0, "cosy_trunk_dgrad: the reduction length c_in=%d (the layer's output channels) must be a positive multiple of 8", a.c_in);
-    COSY_REQUIRE(a.c_out >= 8 && a.c_out % 8 == 0, "cosy_trunk_dgrad: c_out=%d (the layer's input channels) must be a positive multiple of 8", a.c_out);
-    COSY_REQUIRE(a.store == COSY_HEAD_STORE_ROWS || a.store == COSY_HEAD_STORE_NCHW, "cosy_trunk_dgrad: store=%d is not COSY_HEAD_STORE_ROWS or COSY_HEAD_STORE_NCHW", a.store);
-    COSY_REQUIRE(a.relu == 0, "cosy_trunk_dgrad: relu=%d must be 0 (the mask is given by y)", a.relu);
-    COSY_REQUIRE(a.store != COSY_HEAD_STORE_NCHW || a.n_split == a.c_out, "cosy_trunk_dgrad: an NCHW store takes n_split == c_out=%d", a.c_out);
-    const long M_all = check_levels("cosy_trunk_dgrad", a);
-    if (M_all < 0) return COSY_EINVAL;
-    COSY_REQUIRE(stride == 1 || a.n_levels == 1, "cosy_trunk_dgrad: stride=2 takes one level, got n_levels=%d", a.n_levels);
-    const int H = a.H[0], W = a.W[0];
-    const long B = M_all / ((long)H * W);                      // images of level 0 (the only level wherever B is used)
-    tgrad_epi_t e;
-    e.y = y; e.par_y = 0; e.par_x = 0;
-    const float* rows[2] = {add0, add1};
-    const int rules[2] = {rule0, rule1}, aH[2] = {add0_H, add1_H}, aW[2] = {add0_W, add1_W};
-    for (int k = 0; k < 2; ++k) {
-        tadd_t& ad = e.add[k];
-        ad.rows = rows[k]; ad.rule = rules[k]; ad.H = aH[k]; ad.W = aW[k]; ad.sy = 1.f; ad.sx = 1.f;
-        COSY_REQUIRE(ad.rule == ADD_NONE || ad.rule == ADD_SAME || ad.rule == ADD_EVEN || ad.rule == ADD_NEAREST_T,
-                     "cosy_trunk_dgrad: add operand %d: rule=%d is not COSY_TRUNK_ADD_NONE, _SAME, _EVEN or _NEAREST_T", k, ad.rule);
-        if (ad.rule == ADD_NONE) { ad.rows = nullptr; ad.H = 1; ad.W = 1; continue; }
-        COSY_REQUIRE(a.n_levels == 1, "cosy_trunk_dgrad: an add operand takes one level, got n_levels=%d", a.n_levels);
-        if (ad.rule == ADD_SAME) { ad.H = H; ad.W = W; }
-        if (ad.rule == ADD_EVEN)
-            COSY_REQUIRE(ad.H == (H - 1) / 2 + 1 && ad.W == (W - 1) / 2 + 1, "cosy_trunk_dgrad: add operand %d: an EVEN operand of %d x %d maps lives on %d x %d cells, got %d x %d",
-                         k, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1, ad.H, ad.W);
-        if (ad.rule == ADD_NEAREST_T) {
-            COSY_REQUIRE(ad.H >= H && ad.W >= W && (long)ad.H * ad.W <= HEAD_MAX_ROWS, "cosy_trunk_dgrad: add operand %d: a NEAREST_T operand of %d x %d cells is coarser "
-                         "than the target's %d x %d (or too large)", k, ad.H, ad.W, H, W);
-            COSY_REQUIRE(B * ad.H * ad.W <= HEAD_MAX_ROWS, "cosy_trunk_dgrad: add operand %d: its rows exceed 2^30", k);
-            ad.sy = (float)H / (float)ad.H; ad.sx = (float)W / (float)ad.W;
-        }
-    }
-    if (M_all == 0) return COSY_OK;
-    COSY_REQUIRE_PTR("cosy_trunk_dgrad", a.x); COSY_REQUIRE_PTR("cosy_trunk_dgrad", a.w); COSY_REQUIRE_PTR("cosy_trunk_dgrad", a.out);
-    for (int k = 0; k < 2; ++k)
-        COSY_REQUIRE(e.add[k].rule == ADD_NONE || e.add[k].rows != nullptr, "cosy_trunk_dgrad: add operand %d: null rows with rule=%d", k, e.add[k].rule);
-    COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)add0 & 15) == 0 &&
-                 ((uintptr_t)add1 & 15) == 0, "cosy_trunk_dgrad: x, w, out, y and the add operands must be 16-byte aligned");
-    if (stride == 1) return launch_dgrad<1>("cosy_trunk_dgrad", a, (int)M_all, e, s);
-    for (int par = 0; par < 4; ++par) {                        // the four parity classes of (iy, ix): four row ranges, each with its fixed tap set
-        e.par_y = par >> 1; e.par_x = par & 1;
-        const long M = B * ((H + 1 - e.par_y) / 2) * ((W + 1 - e.par_x) / 2);
-        if (M == 0) continue;
-        const int rc = launch_dgrad<2>("cosy_trunk_dgrad", a, (int)M, e, s);
-        if (rc != COSY_OK) return rc;
-    }
-    return COSY_OK;
+    return run_trunk_dgrad<float>("cosy_trunk_dgrad", a, stride, add0, rule0, add0_H, add0_W, add1, rule1, add1_H, add1_W, y, s);
 }
 
 int cosy_head_wgrad(const cosy_head_layer_t* layer, const float* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes,

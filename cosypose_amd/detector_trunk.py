@@ -1,6 +1,7 @@
 """The detector's trunk on the matrix pipe: torchvision 0.4.2's ResNet-50 body with FrozenBatchNorm2d and its FeaturePyramidNetwork, the part
 of Mask R-CNN between detector_input and DetectorHeads, and `Detector`, the reference's interface over the whole chain.  Inference only by
-default; trainable=True (float32) makes the trunk an autograd node with parameters (detector_trunk_backward.py).
+default; trainable=True makes the trunk an autograd node with float32 parameters (detector_trunk_backward.py), on
+float32 rows or with train_dtype=torch.bfloat16 on bfloat16 rows and packed weights (section 30).
 DESIGN.md section 27 states the contract; HIP: csrc/kernels_dettrunk.hip (cosy_trunk_conv, cosy_trunk_stem_pack, cosy_trunk_maxpool) and the
 GEMM it shares with the heads (csrc/dethead_device.h).
 
@@ -223,23 +224,29 @@ class DetectorTrunk:
             if lat.c_in != width or lay.c_in != lat.c_out or lay.c_out != outer[0].c_out or lat.c_out != inner[0].c_out:
                 raise ValueError(f'{lat.name}: the FPN\'s widths do not match the stage ({width}) or one another')
         self._arena = {}
-        self.trainable, self.train_from_stage = False, None
+        self.trainable, self.train_from_stage, self.train_dtype = False, None, None
         self.keep_rows, self.timer, self.last_rows, self.last_kept_bytes = False, None, None, 0
 
     # ---- construction ----
     @classmethod
-    def from_state_dict(cls, sd, dtype=torch.float32, device=None, prefix='backbone.', trainable=False, train_from_stage=2):
+    def from_state_dict(cls, sd, dtype=torch.float32, device=None, prefix='backbone.', trainable=False, train_from_stage=2, train_dtype=None):
         """torchvision 0.4.2's keys under `prefix`: body.conv1 / bn1, body.layer{s}.{i}.conv{1,2,3} / bn{1,2,3} / downsample.{0,1}, fpn.inner_blocks.{l},
         fpn.layer_blocks.{l}.  Block counts and widths are the keys' and the shapes'; num_batches_tracked and every other key are ignored; a
         missing key is a KeyError naming it.
-        trainable (float32 only): the conv weights of body.layer{train_from_stage}.. and the FPN's weights and biases are
+        trainable (float32 parameters): the conv weights of body.layer{train_from_stage}.. and the FPN's weights and biases are
         torch.nn.Parameters on the device under torchvision's names; the stem, the stages below and every FrozenBatchNorm stay constants.
-        train_from_stage = stages + 1 trains the FPN alone; 0 (the stem and the pool) is refused: their backward is not built"""
+        train_from_stage = stages + 1 trains the FPN alone; 0 (the stem and the pool) is refused: their backward is not built.
+        dtype stays the type of the parameters: float32, the master weights.  train_dtype names the type of the rows and
+        of the packed weights: None or torch.float32: section 29's path; torch.bfloat16: bfloat16 rows kept for the backward, bfloat16 gradient
+        rows, the frozen stages packed once in bfloat16, float32 .grad; torch.float16 is refused (no loss scaler)"""
+        from .detector_trunk_backward import check_train_dtype
         dtype = _dtype(dtype)
+        row_dtype = check_train_dtype(trainable, train_dtype)
         kw = dict(dtype=dtype, device=device)
         if trainable:
             if dtype != torch.float32:
-                raise ValueError(f'a trainable trunk is float32 only (16-bit training and master weights are not built), got dtype={dtype}')
+                raise ValueError(f'a trainable trunk is float32 only (dtype is the type of the parameters, the master weights; 16-bit rows are '
+                                 f'train_dtype=torch.bfloat16), got dtype={dtype}')
             if isinstance(train_from_stage, bool) or not isinstance(train_from_stage, int):
                 raise ValueError(f'train_from_stage must be an int, got {train_from_stage!r}')
             if train_from_stage < 1:
@@ -250,7 +257,7 @@ class DetectorTrunk:
                 device = first.device if first is not None else None
             if device is None or torch.device(device).type != 'cuda':
                 raise ValueError(f'a trainable trunk lives on the ROCm device: give device=, got {device}')
-            kw['device'] = device
+            kw.update(device=device, dtype=row_dtype)
             from .detector_trunk_backward import TrainableTrunkLayer
             counter = [0]
 
@@ -268,12 +275,12 @@ class DetectorTrunk:
 
         def conv_bn(conv, norm, stride=1, relu=True, train=False):
             if train:
-                return TrainableTrunkLayer(prefix + conv, get(conv + '.weight'), bn=bn(norm), stride=stride, relu=relu, device=device, counter=counter)
+                return TrainableTrunkLayer(prefix + conv, get(conv + '.weight'), bn=bn(norm), stride=stride, relu=relu, device=device, counter=counter, dtype=row_dtype)
             return TrunkLayer(prefix + conv, get(conv + '.weight'), bn=bn(norm), stride=stride, relu=relu, **kw)
 
         def fpn_layer(key):
             if trainable:
-                return TrainableTrunkLayer(prefix + key, get(key + '.weight'), bias=get(key + '.bias'), device=device, counter=counter)
+                return TrainableTrunkLayer(prefix + key, get(key + '.weight'), bias=get(key + '.bias'), device=device, counter=counter, dtype=row_dtype)
             return TrunkLayer(prefix + key, get(key + '.weight'), bias=get(key + '.bias'), **kw)
         found = {}
         for k in sd:
@@ -303,20 +310,21 @@ class DetectorTrunk:
         for lay in outer:
             if lay.ksize != 3:
                 raise ValueError(f'{lay.name}: an FPN output block is a 3x3 convolution, got {lay.ksize}x{lay.ksize}')
-        trunk = cls(stem, stages, inner, outer, dtype)
+        trunk = cls(stem, stages, inner, outer, row_dtype if trainable else dtype)      # self.dtype: the rows' type
         if trainable:
+            trunk.train_dtype = row_dtype
             trunk._init_trainable(sd, prefix, train_from_stage, counter)
         return trunk
 
     @classmethod
-    def from_modules(cls, backbone, dtype=torch.float32, device=None, trainable=False, train_from_stage=2):
+    def from_modules(cls, backbone, dtype=torch.float32, device=None, trainable=False, train_from_stage=2, train_dtype=None):
         """the same from a module with torchvision's attribute names (body, fpn): its state_dict under no prefix (trainable: copies, never
         the module's own tensors)"""
         sd = backbone.state_dict()
         if device is None:
             first = next(iter(sd.values())).device
             device = first if first.type != 'cpu' else None
-        return cls.from_state_dict(sd, dtype, device, prefix='', trainable=trainable, train_from_stage=train_from_stage)
+        return cls.from_state_dict(sd, dtype, device, prefix='', trainable=trainable, train_from_stage=train_from_stage, train_dtype=train_dtype)
 
     # ---- the trainable trunk (DESIGN.md section 29) ----
     def _init_trainable(self, sd, prefix, train_from_stage, counter):
@@ -486,13 +494,18 @@ class Detector:
         self.min_size, self.max_size = int(min(input_resize)), int(max(input_resize))
 
     @classmethod
-    def from_state_dict(cls, sd, label_to_category_id, input_resize=(480, 640), dtype=torch.float32, device='cuda', trainable=False, train_from_stage=2):
+    def from_state_dict(cls, sd, label_to_category_id, input_resize=(480, 640), dtype=torch.float32, device='cuda', trainable=False, train_from_stage=2,
+                        train_dtype=None):
         """a reference detector checkpoint's state_dict as it is (backbone.*, rpn.head.*, roi_heads.*).  trainable: the trainable trunk
-         and the trainable heads (section 28), float32"""
+         and the trainable heads (section 28), float32 parameters.  train_dtype=torch.bfloat16: the trunk runs section
+        30's bfloat16 rows; its maps are float32 NCHW, so the float32 trainable heads follow it unchanged"""
         from .detector_heads import DetectorHeads
+        from .detector_trunk_backward import check_train_dtype
+        check_train_dtype(trainable, train_dtype)
         if trainable and dtype != torch.float32:
-            raise ValueError(f'a trainable detector is float32 only (16-bit training and master weights are not built), got dtype={dtype}')
-        trunk = DetectorTrunk.from_state_dict(sd, dtype, device, trainable=trainable, train_from_stage=train_from_stage)
+            raise ValueError(f'a trainable detector is float32 only (dtype is the type of the parameters; bfloat16 rows in the trunk are '
+                             f'train_dtype=torch.bfloat16), got dtype={dtype}')
+        trunk = DetectorTrunk.from_state_dict(sd, dtype, device, trainable=trainable, train_from_stage=train_from_stage, train_dtype=train_dtype)
         return cls(trunk, DetectorHeads.from_state_dict(sd, dtype, device, trainable=trainable), label_to_category_id, input_resize)
 
     # ---- training (trainable=True): the reference's train_detector.py loop on this library's kernels ----

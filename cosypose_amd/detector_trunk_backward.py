@@ -1,6 +1,8 @@
-"""The backward of the detector's trunk on the matrix pipe, float32 only: the data and weight gradients of the ResNet
+"""The backward of the detector's trunk on the matrix pipe: the data and weight gradients of the ResNet
 bottlenecks and the FPN as GEMMs (HIP: csrc/kernels_detbwd.hip, the heads' gradient kernels -- cosy_trunk_weight_pack, cosy_trunk_dgrad, cosy_trunk_wgrad), the
-trainable layer that holds a trunk parameter, and the autograd node behind DetectorTrunk(trainable=True).
+trainable layer that holds a trunk parameter, and the autograd node behind DetectorTrunk(trainable=True).  float32, or with
+train_dtype=torch.bfloat16 (section 30; csrc/kernels_detbwd16.hip -- cosy_trunk_weight_pack16, cosy_trunk_grad_pack16, cosy_trunk_dgrad16,
+cosy_trunk_wgrad16) bfloat16 rows and packed weights under float32 parameters, the master weights, and float32 gradients.
 
 A trunk layer is v = fmaf(conv_stride(x, W), scale, shift) [+ r], y = relu(v).  Its gradient rows g are the gradient at v, float32 rows on
 the layer's OUTPUT grid.  No scaled copy of g is stored: the data gradient reads ws = w scale[o] (packed once per weight version), the weight
@@ -15,7 +17,7 @@ import torch
 from . import _lib
 from .detector_heads import MAX_ROWS, PackedOnDevice, _describe, _g, _grad_pack, _gemm, _wgrad_buffers
 
-F32 = torch.float32
+F32, BF16 = torch.float32, torch.bfloat16
 SAME, EVEN, NEAREST_T = _lib.TRUNK_ADD_SAME, _lib.TRUNK_ADD_EVEN, _lib.TRUNK_ADD_NEAREST_T
 
 
@@ -23,14 +25,29 @@ def _out(n, stride):
     return (n - 1) // stride + 1
 
 
+def check_train_dtype(trainable, train_dtype):
+    """the train_dtype= keyword of the trainable trunk and detector -> the type of the rows and of the packed weights (None: not trainable)"""
+    if train_dtype is None:
+        return F32 if trainable else None
+    if not trainable:
+        raise ValueError(f'train_dtype={train_dtype} names the rows of a trainable trunk: give trainable=True with it')
+    if train_dtype == torch.float16:
+        raise ValueError('train_dtype=torch.float16: float16 training needs a loss scaler, which is not built; use torch.bfloat16 or torch.float32')
+    if train_dtype not in (F32, BF16):
+        raise ValueError(f'train_dtype must be None, torch.float32 or torch.bfloat16, got {train_dtype!r}')
+    return train_dtype
+
+
 class TrainableTrunkLayer(PackedOnDevice):
     """A trainable convolution of the trunk: weight is a torch.nn.Parameter (O,C,k,k) on the device under torchvision's name; a layer followed
     by FrozenBatchNorm keeps its scale and shift as constants, an FPN layer has a bias Parameter and no scale.  w / bias (what cosy_trunk_conv
     and cosy_head_conv read, the host packing's bytes) and w_t (the transposed, tap-flipped packing of ws = w scale[o]) are written by
-    cosy_trunk_weight_pack when a parameter's _version or storage has moved since the last pack."""
+    cosy_trunk_weight_pack when a parameter's _version or storage has moved since the last pack.  dtype: the type of the rows and of w / w_t
+    (the parameters are float32 whatever it is); torch.bfloat16 packs through cosy_trunk_weight_pack16: w holds the bytes of the host packing of
+    the weight rounded to bfloat16, w_t those of ws rounded once."""
     kind, dtype, owner = 'conv', F32, 'trunk'
 
-    def __init__(self, name, weight, bn=None, bias=None, stride=1, relu=False, device=None, counter=None):
+    def __init__(self, name, weight, bn=None, bias=None, stride=1, relu=False, device=None, counter=None, dtype=F32):
         from .detector_trunk import frozen_bn
         if device is None or torch.device(device).type != 'cuda':
             raise ValueError(f'{name}: a trainable trunk lives on the ROCm device: give device=, got {device}')
@@ -43,6 +60,9 @@ class TrainableTrunkLayer(PackedOnDevice):
             raise ValueError(f'{name}: stride must be 1 or 2, got {stride}')
         if C % 8 or O % 8:
             raise ValueError(f'{name}: {C} -> {O} channels: every channel count must be a multiple of 8')
+        if dtype not in (F32, BF16):
+            raise ValueError(f'{name}: the rows of a trainable trunk are float32 or bfloat16, got {dtype}')
+        self.dtype = dtype
         self.name, self.ksize, self.stride, self.relu = name, k, int(stride), bool(relu)
         self.c_in, self.c_out, self.n_out = C, O, O
         self.counter = counter if counter is not None else [0]
@@ -63,9 +83,10 @@ class TrainableTrunkLayer(PackedOnDevice):
                 raise ValueError(f'{name}.bias must be ({O}), got {tuple(b.shape)}')
             self.bias_param = torch.nn.Parameter(b.detach().to(device=dev, dtype=F32).contiguous().clone())
         taps = k * k
-        self.w = torch.empty(NP * taps * (-(-C // 16) * 16), dtype=F32, device=dev)
+        KB = 16 if dtype == F32 else 32
+        self.w = torch.empty(NP * taps * (-(-C // KB) * KB), dtype=dtype, device=dev)
         self.bias = torch.empty(NP, dtype=F32, device=dev)
-        self.w_t = torch.empty((-(-C // 64) * 64) * taps * (-(-O // 16) * 16), dtype=F32, device=dev)
+        self.w_t = torch.empty((-(-C // 64) * 64) * taps * (-(-O // KB) * KB), dtype=dtype, device=dev)
         self.versions = None
 
     def parameters(self):
@@ -73,8 +94,9 @@ class TrainableTrunkLayer(PackedOnDevice):
 
     def _pack(self):
         shift = self.shift if self.bias_param is None else self.bias_param
-        _lib.check(_lib.lib().cosy_trunk_weight_pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out,
-                                                     _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
+        pack = _lib.lib().cosy_trunk_weight_pack if self.dtype == F32 else _lib.lib().cosy_trunk_weight_pack16
+        _lib.check(pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out, _lib.ptr(self.w), _lib.ptr(self.bias),
+                        _lib.ptr(self.w_t), _lib.stream()))
 
     ready = PackedOnDevice.refresh
 
@@ -88,7 +110,7 @@ def trunk_dgrad(layer, g_rows, B, H, W, out, adds=(), y=None, store=_lib.HEAD_ST
     y: the mask rows on the dX grid.  stride: the layer's own unless given (downsample.0 runs at stride 1 on its output grid)"""
     d = _lib.HeadLayer()
     d.x, d.w, d.out = _lib.ptr(g_rows), _lib.ptr(layer.w_t), _lib.ptr(out)
-    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_out, layer.c_in, 0, store, layer.c_in
+    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store, d.n_split = _lib.DTYPES[layer.dtype], layer.ksize, layer.c_out, layer.c_in, 0, store, layer.c_in
     _describe(d, [(B, H, W)])
     adds = list(adds)
     if len(adds) > 2:
@@ -96,7 +118,8 @@ def trunk_dgrad(layer, g_rows, B, H, W, out, adds=(), y=None, store=_lib.HEAD_ST
     flat = []
     for rule, rows, aH, aW in adds + [(_lib.TRUNK_ADD_NONE, None, 0, 0)] * (2 - len(adds)):
         flat += [_lib.ptr(rows), rule, aH, aW]
-    _lib.check(_lib.lib().cosy_trunk_dgrad(ctypes.byref(d), layer.stride if stride is None else stride, *flat, _lib.ptr(y), _lib.stream()))
+    dgrad = _lib.lib().cosy_trunk_dgrad if layer.dtype == F32 else _lib.lib().cosy_trunk_dgrad16
+    _lib.check(dgrad(ctypes.byref(d), layer.stride if stride is None else stride, *flat, _lib.ptr(y), _lib.stream()))
     return out
 
 
@@ -104,13 +127,30 @@ def trunk_wgrad(layer, x_rows, g_rows, B, H, W):
     """one cosy_trunk_wgrad call: x_rows on B maps of H x W cells, g_rows on the output grid -> [dW (, db)] in the parameters' layout"""
     d = _lib.HeadLayer()
     d.x = _lib.ptr(x_rows)
-    d.dtype, d.ksize, d.c_in, d.c_out, d.n_split = _lib.COSY_F32, layer.ksize, layer.c_in, layer.c_out, layer.c_out
+    d.dtype, d.ksize, d.c_in, d.c_out, d.n_split = _lib.DTYPES[layer.dtype], layer.ksize, layer.c_in, layer.c_out, layer.c_out
     _describe(d, [(B, H, W)])
     Ho, Wo = layer.out_size(H, W)
     out, ws, need = _wgrad_buffers(layer, B * Ho * Wo, layer.ksize, layer.c_out)
-    _lib.check(_lib.lib().cosy_trunk_wgrad(ctypes.byref(d), layer.stride, _lib.ptr(g_rows), _lib.ptr(layer.scale), _lib.ptr(out[0]),
-                                           _lib.ptr(out[1]) if len(out) > 1 else None, _lib.ptr(ws), need, _lib.stream()))
+    wgrad = _lib.lib().cosy_trunk_wgrad if layer.dtype == F32 else _lib.lib().cosy_trunk_wgrad16
+    _lib.check(wgrad(ctypes.byref(d), layer.stride, _lib.ptr(g_rows), _lib.ptr(layer.scale), _lib.ptr(out[0]), _lib.ptr(out[1]) if len(out) > 1 else None,
+                     _lib.ptr(ws), need, _lib.stream()))
     return out
+
+
+def trunk_grad_pack(g, rows, B, C, HW):
+    """the NCHW float32 gradient of one map (None: zeros) -> the rows (B HW, C) of the rows' type, one launch"""
+    if rows.dtype == F32:
+        return _grad_pack(g, None, rows, B, C, 0, HW)
+    if g is not None and (g.dtype != F32 or g.numel() != B * C * HW or not g.is_cuda):
+        raise ValueError(f'a gradient of {B} x {C} x {HW} float32 values on the device was expected, got {tuple(g.shape)} {g.dtype} on {g.device}')
+    if B:
+        _lib.check(_lib.lib().cosy_trunk_grad_pack16(_lib.ptr(None if g is None else g.contiguous()), _lib.ptr(rows), B, C, HW, _lib.stream()))
+    return rows
+
+
+def _rows_of(t, dtype):
+    """(B,C,H,W) -> rows (B H W, C) of dtype (the tests' access: a bfloat16 layer rounds its operands to nearest even on the way in)"""
+    return t.detach().permute(0, 2, 3, 1).contiguous().view(-1, int(t.shape[1])).to(dtype)
 
 
 def layer_dgrad(layer, grad, H, W, adds=(), y=None, stride=None):
@@ -119,10 +159,14 @@ def layer_dgrad(layer, grad, H, W, adds=(), y=None, stride=None):
     dev = grad.device
     layer.ready(dev)
     B, O, Ho, Wo = (int(v) for v in grad.shape)
-    rows = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().view(-1, int(t.shape[1]))
+    rows = lambda t: _rows_of(t, layer.dtype)
     ops = [(rule, rows(t), int(t.shape[2]), int(t.shape[3])) for rule, t in adds]
-    out = torch.empty((B, layer.c_in, H, W), dtype=F32, device=dev)
     with torch.cuda.device(dev):
+        if layer.dtype != F32:                                  # 16-bit rows have the row store alone; the way out is exact
+            out = torch.empty((B * H * W, layer.c_in), dtype=layer.dtype, device=dev)
+            trunk_dgrad(layer, rows(grad), B, H, W, out, ops, None if y is None else rows(y), _lib.HEAD_STORE_ROWS, stride)
+            return out.view(B, H, W, layer.c_in).permute(0, 3, 1, 2).float().contiguous()
+        out = torch.empty((B, layer.c_in, H, W), dtype=F32, device=dev)
         trunk_dgrad(layer, rows(grad), B, H, W, out, ops, None if y is None else rows(y), _lib.HEAD_STORE_NCHW, stride)
     return out
 
@@ -132,9 +176,8 @@ def layer_wgrad(layer, x, grad):
     dev = x.device
     layer.ready(dev)
     B, C, H, W = (int(v) for v in x.shape)
-    rows = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().view(-1, int(t.shape[1]))
     with torch.cuda.device(dev):
-        return trunk_wgrad(layer, rows(x), rows(grad), B, H, W)
+        return trunk_wgrad(layer, _rows_of(x, layer.dtype), _rows_of(grad, layer.dtype), B, H, W)
 
 
 # ---- the node --------------------------------------------------------------------------------------------------------------------------
@@ -143,7 +186,7 @@ def forward_keep(trunk, images):
     reads (x, a, b, out of every trainable block, the stage outputs, the laterals) are tensors of their own -> the four maps, keep"""
     from .detector_trunk import _trunk_gemm
     dev, B = images.device, int(images.shape[0])
-    fresh = lambda n, c: torch.empty((n, c), dtype=F32, device=dev)
+    fresh = lambda n, c: torch.empty((n, c), dtype=trunk.dtype, device=dev)            # the rows' type: float32, or section 30's bfloat16
     x, H, W = trunk.stem_rows(images)
     tfs = trunk.train_from_stage
     if tfs == 1:
@@ -202,7 +245,7 @@ def backward(trunk, keep, grads, rows_out=None, timer=None):
     B, feats, inner, starts, bk = keep['B'], keep['feats'], keep['inner'], keep['starts'], keep['blocks']
     dev = inner.device
     L, tfs = len(trunk.stages), trunk.train_from_stage
-    new = lambda n, c: torch.empty((n, c), dtype=F32, device=dev)
+    new = lambda n, c: torch.empty((n, c), dtype=trunk.dtype, device=dev)
     timed = timer if timer is not None else (lambda group: contextlib.nullcontext())
     out = {}
 
@@ -218,7 +261,7 @@ def backward(trunk, keep, grads, rows_out=None, timer=None):
     with timed('fpn'):
         for l in range(L):
             _, h, w = feats[l]
-            g = _grad_pack(_g(grads[l]), None, new(B * h * w, C), B, C, 0, h * w)
+            g = trunk_grad_pack(_g(grads[l]), new(B * h * w, C), B, C, h * w)
             x_in = inner[starts[l]:starts[l + 1]]
             put(trunk.outer[l], trunk_wgrad(trunk.outer[l], x_in, g, B, h, w))
             adds = [] if l == 0 else [(NEAREST_T, G[l - 1], feats[l - 1][1], feats[l - 1][2])]

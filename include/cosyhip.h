@@ -1125,6 +1125,35 @@ int cosy_trunk_dgrad(const cosy_head_layer_t* layer, int stride, const float* ad
 int cosy_trunk_wgrad(const cosy_head_layer_t* layer, int stride, const float* g, const float* scale, float* dw, float* db, void* workspace,
                      size_t workspace_bytes, cosy_stream_t stream);
 
+/* ---- the backward of the detector's trunk on bfloat16 rows, float32 master weights ----  DESIGN.md section 30 holds the contract.
+ * The parameters, their gradients, scale, shift and every accumulation are float32; the rows (x, g, the add operands, y, dX) and both packed
+ * weights are bfloat16, every conversion rounds to nearest even.  Layers, grids, strides, rules and limits are those of the float32 entries
+ * above; dtype is COSY_BF16 (COSY_F32: the entries above; COSY_F16 is refused: float16 training needs a loss scaler, which is not built).
+ * cosy_trunk_weight_pack16: w, scale (or NULL), shift float32 on the device -> fwd, the fragment order cosy_trunk_conv reads at COSY_BF16: the
+ *   bytes of the host packing of w rounded to bfloat16; fwd_bias, float32 as cosy_trunk_weight_pack's; bwd, the packing cosy_trunk_dgrad16 reads:
+ *   ws = bf16(fl32(w scale[o])) (ONE float32 product, then one rounding; scale NULL: ws = bf16(w)), rows c, reduction o in blocks of 32 (eight
+ *   elements per lane, rounded up with zeros), taps in reverse order.  fwd: c_out rounded up to 64 x taps x c_in rounded up to 32 elements;
+ *   bwd: c_in rounded up to 64 x taps x c_out rounded up to 32.  One launch.
+ * cosy_trunk_grad_pack16: contiguous NCHW float32 (B, C, HW) -> bfloat16 rows (B HW, C), C a multiple of 8.  A NULL g is a tensor of zeros.
+ * cosy_trunk_dgrad16: cosy_trunk_dgrad on bfloat16 rows: layer->x = g, w = bwd, out, add0, add1 and y are bfloat16.  Accumulator +0.0 float32,
+ *   blocks of 32 o ascending, the live taps in the packing's order inside a block, one v_mfma_f32_16x16x32_bf16 per (block, tap): the products
+ *   are exact in float32, the order of the 32 additions inside the instruction is the hardware's and the same on every call.  Store, per
+ *   element: t = acc; t = t + (float)operand for add0, add1 under their rules (SAME, EVEN, NEAREST_T as above, an EVEN cell that takes nothing
+ *   is left untouched), every + one rounded float32 add; y != NULL: t = y <= 0 ? +0.0 : t (a NaN y passes t); then ONE conversion to bfloat16.
+ *   store: COSY_HEAD_STORE_ROWS only.
+ * cosy_trunk_wgrad16: cosy_trunk_wgrad with layer->x and g bfloat16 rows; dw, db, scale and the workspace float32.  The cells are the k
+ *   dimension of v_mfma_f32_16x16x32_bf16, 32 per instruction; a cell past its slab, a tap outside the map feed +0.0.  Slabs
+ *   (cosy_head_wgrad_slab_rows), workspace (cosy_head_wgrad_workspace_bytes), the ascending second pass and the one scale[o] product are
+ *   cosy_trunk_wgrad's.  x and g 16-byte aligned.
+ * All: checked on the host before any launch (COSY_EINVAL, the message starts with the function's name).  No atomics: equal inputs give equal bits. */
+int cosy_trunk_weight_pack16(const float* w, const float* scale, const float* shift, int ksize, int c_in, int c_out, void* fwd, float* fwd_bias,
+                             void* bwd, cosy_stream_t stream);
+int cosy_trunk_grad_pack16(const float* g, void* rows, int B, int C, int HW, cosy_stream_t stream);
+int cosy_trunk_dgrad16(const cosy_head_layer_t* layer, int stride, const void* add0, int rule0, int add0_H, int add0_W, const void* add1,
+                       int rule1, int add1_H, int add1_W, const void* y, cosy_stream_t stream);
+int cosy_trunk_wgrad16(const cosy_head_layer_t* layer, int stride, const void* g, const float* scale, float* dw, float* db, void* workspace,
+                       size_t workspace_bytes, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
