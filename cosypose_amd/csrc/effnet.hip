@@ -98,6 +98,10 @@ struct Block {
     int x_perm_lp;        // x_chunk and the front is the fp32-FMA form: log2 of its pixels per lane -- the rows of the input are stored permuted (PwArgs::out_perm_*); else 0
     ActLayout out;        // how the block's output is stored: what the next block's front wants (x_chunk / x_perm_lp) and this stage's pixel order
     float *se_wr_p, *se_br_p, *se_we_p;   // zero-padded copies for the batched form: (CseP, Cmid), (CseP), (Cmid, CseP)
+    // Order in which each launch of the block walks the samples (plan_traversal; job_order.h): 1 = last sample first.  rev_exp: the expand GEMM of an
+    // unfused block; rev_front: the front kernel -- a fused front, block 0's stem front, or the unfused depthwise kernel; rev_proj: the project GEMM;
+    // rev_torow: the re-ordering copy behind it (to_rowmajor)
+    bool rev_exp, rev_front, rev_proj, rev_torow;
 };
 
 }  // namespace cosy
@@ -119,6 +123,8 @@ struct cosy_net {
     unsigned wave_mask;   // bit i: ... the wave-autonomous front kernel (mbconv_wave_kernel); both only where the shape is built
     int se_batch_from;    // blocks >= this run the batched squeeze-excite kernels
     unsigned se_fuse_mask; // bit i: block i may compute its squeeze-excite gate in the project GEMM's prologue (Block::se_fused)
+    int traversal;        // cosy_effnet_b3_set_traversal: 0 = every launch walks the samples forward, 1 = serpentine (plan_traversal)
+    bool rev_head;        // the head GEMM walks its tiles backward
     int probe_layer;      // test probe (cosy_effnet_b3_set_probe): -2 = off
     float* probe_out;
     // activation workspace, max_batch samples: the block inputs / outputs ping-pong between act[0] and act[1]
@@ -134,6 +140,12 @@ struct cosy_net {
     cosy_prof_rec_t* prof_rec;
 };
 enum { PROF_SEGS = 24, PROF_SLOTS = 1024 };
+// The sample order of a new engine (cosy_effnet_b3_set_traversal).  Serpentine: ten alternating same-call pairs of the headline benchmark gave
+// 68,859 -> 69,459 pose-iterations/s (+0.87 %; the mode-0 runs lie within +-0.26 % of each other, every mode-1 run above every mode-0 run) and no
+// benched shape lost: profiles/r07_traversal.txt
+#ifndef COSY_TRAVERSAL_DEFAULT      // (an A/B build of the other default: -DCOSY_TRAVERSAL_DEFAULT=0)
+#define COSY_TRAVERSAL_DEFAULT 1
+#endif
 
 namespace cosy {
 
@@ -187,6 +199,7 @@ static FrontProps front_props(const cosy_net* n, const Block& b) {
 
 static void plan_pixel_order(cosy_net* n);
 static void plan_channel_layout(cosy_net* n);
+static void plan_traversal(cosy_net* n);
 // Walks the parameter blob and lays the packed weights out in `bump`: the sizing pass and the fill pass run the same lines, the fill pass also
 // runs the writers (Bump::put).  Returns the number of blob floats consumed.
 static long build_weights(cosy_net* n, const float* p, Bump& bump) {
@@ -321,6 +334,7 @@ static long build_weights(cosy_net* n, const float* p, Bump& bump) {
     n->Hf = h; n->Wf = w_;
     plan_pixel_order(n);
     plan_channel_layout(n);
+    plan_traversal(n);
     mk_pw(n->head, p, HEAD_IN, HEAD_C, p + (size_t)HEAD_C * HEAD_IN, n->Hf * n->Wf, false);
     p += (size_t)HEAD_C * HEAD_IN + 4 * HEAD_C;
     n->fc_w = put_copy(p, N_POSE * HEAD_C);
@@ -379,6 +393,28 @@ static void plan_channel_layout(cosy_net* n) {
     }
 }
 
+// The order in which every launch walks the samples (Block::rev_*, cosy_net::rev_head).  Mode 0: all forward.  Mode 1, serpentine: a launch that reads a
+// large activation walks opposite to the launch that wrote it, so that it begins with the bytes written last -- what is left of them in the last-level
+// cache -- instead of streaming behind its producer at a distance of the whole tensor (job_order.h).  cosy_crop_pack* writes the network input forward,
+// and so does the stem kernel of the probe / taps path; hence the stem front, every fused front and the depthwise kernels of blocks 0 / 1 run backward and
+// their project GEMMs forward.  An unfused block with an expand GEMM has three large launches, not two: its expand GEMM runs opposite to the block
+// before's project GEMM, its depthwise kernel opposite to that, and the order of every launch behind it flips; the re-ordering copy of a column-major
+// stage counts like any launch.  The head GEMM runs opposite to block 25's last launch.  The squeeze-excite, pooling and fc9 launches read kilobytes and
+// keep their order.  The order of a launch never changes what a job computes: both modes give the same bits (tests/test_traversal_order.py).
+static void plan_traversal(cosy_net* n) {
+    bool cur = false;      // is the tensor the next launch reads written last sample first?
+    for (int i = 0; i < 26; ++i) {
+        Block& b = n->blk[i];
+        b.rev_exp = b.rev_front = b.rev_proj = b.rev_torow = false;
+        if (!n->traversal) continue;
+        if (b.front == Front::Unfused && b.d.e != 1) cur = b.rev_exp = !cur;
+        cur = b.rev_front = !cur;
+        cur = b.rev_proj = !cur;
+        if (b.to_rowmajor) cur = b.rev_torow = !cur;
+    }
+    n->rev_head = n->traversal && !cur;
+}
+
 // One set of activation buffers for max_batch samples, each as large as its largest user among the stem tensor and the 26 blocks.
 static void layout_workspace(cosy_net* n, Bump& b) {
     const size_t e = n->esz, B = n->maxB;
@@ -414,6 +450,7 @@ static int launch_front(const cosy_net* n, const Block& b, const void* in, int B
     f.X = in; f.Wp = b.exp_wp_fused; f.D = n->D; f.partial = n->partial; f.zeros = n->zeros;
     f.B = B; f.H = b.H; f.W = b.W; f.Cin = b.d.cin; f.Cmid = b.cmid; f.Ho = b.Ho; f.Wo = b.Wo; f.k = b.d.k; f.s = b.d.s; f.pad_lo = b.pad_lo;
     f.x_colmajor = b.in_col; f.d_colmajor = b.out_col; f.x_chunked = b.x_chunk; f.x_perm = b.x_perm_lp > 0;
+    f.rev = b.rev_front;
     auto bn_and_taps = [&] { f.s0 = b.exp.scale; f.b0 = b.exp.bias; f.dww = b.dw_w; f.s1 = b.dw_scale; f.b1 = b.dw_bias; f.wparams = b.wave_params; };
     switch (b.front) {
     case Front::Unfused: break;
@@ -480,7 +517,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
         if (stem_x) {
             StemFrontArgs f{};
             f.X = stem_x; f.Wp = n->stemf_w; f.params = n->stemf_params; f.D = n->D; f.partial = n->partial; f.dump = n->dump; f.zeros = n->zeros;
-            f.B = B; f.H = n->H; f.W = n->W;
+            f.B = B; f.H = n->H; f.W = n->W; f.rev = b.rev_front;
             if ((rc = launch_stem_front(f, n->dtype, &se_tiles, s))) return rc;
             d_chunked = true;
             snprintf(kn, sizeof(kn), "stem_front_kernel<%s, %d>", dt_name(n->dtype), n->W / 64);
@@ -496,7 +533,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
             if (b.d.e != 1) {
                 PwArgs a{};
                 a.A = in; a.Wp = b.exp.Wp; a.out = n->E; a.scale = b.exp.scale; a.bias = b.exp.bias;
-                a.M = B * b.H * b.W; a.K = b.d.cin; a.N = b.cmid; a.HW = b.H * b.W; a.silu = 1; a.zeros = n->zeros;
+                a.M = B * b.H * b.W; a.K = b.d.cin; a.N = b.cmid; a.HW = b.H * b.W; a.silu = 1; a.zeros = n->zeros; a.rev = b.rev_exp;
                 if ((rc = launch_pw_gemm(a, b.exp.cfg, n->dtype, s))) return rc;
                 pw_name(b.exp, a);
                 if ((rc = mark(kn, i, pw_bytes(a), 2.0 * a.M * a.K * a.N, ((double)a.M * a.K + (double)a.K * a.N) * esz_d))) return rc;
@@ -504,7 +541,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
             }
             DwArgs d{};
             d.in = src; d.w = b.dw_w; d.scale = b.dw_scale; d.bias = b.dw_bias; d.out = n->D; d.partial = n->partial;
-            d.B = B; d.H = b.H; d.W = b.W; d.C = b.cmid; d.Ho = b.Ho; d.Wo = b.Wo; d.k = b.d.k; d.s = b.d.s; d.pad_lo = b.pad_lo; d.zeros = n->zeros;
+            d.B = B; d.H = b.H; d.W = b.W; d.C = b.cmid; d.Ho = b.Ho; d.Wo = b.Wo; d.k = b.d.k; d.s = b.d.s; d.pad_lo = b.pad_lo; d.zeros = n->zeros; d.rev = b.rev_front;
             if ((rc = launch_dwconv(d, n->dtype, s))) return rc;
             snprintf(kn, sizeof(kn), "dwconv_kernel<%s, %d, %d>", dt_name(n->dtype), b.d.k, b.d.s);
             if ((rc = mark(kn, i, ((double)B * b.H * b.W * b.cmid + (double)B * b.Ho * b.Wo * b.cmid) * esz_d + (double)B * se_tiles * b.cmid * 4,
@@ -531,7 +568,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
         a.res = b.skip ? in : nullptr; a.gate = n->gate; a.se_fused = b.se_fused ? &se : nullptr;
         a.res_chunked = b.x_chunk; a.out_chunked = b.out.chunked; a.out_perm_lw = b.out.perm_lw; a.out_perm_lp = b.out.perm_lp;
         a.M = B * b.Ho * b.Wo; a.K = b.cmid; a.N = b.d.cout; a.HW = b.Ho * b.Wo; a.silu = 0; a.zeros = n->zeros;
-        a.a_chunked = d_chunked;
+        a.a_chunked = d_chunked; a.rev = b.rev_proj;
         if ((rc = probe(100 + i, n->D, b.Ho * b.Wo, b.cmid, ActLayout{d_chunked, b.out_col ? b.Ho : 0, 0, 0}))) return rc;
         if ((rc = launch_pw_gemm(a, b.proj.cfg, n->dtype, s))) return rc;
         if (n->probe_layer == 200 + i && n->probe_out)      // behind the GEMM: with the squeeze-excite in its prologue that is where the gate is written
@@ -539,7 +576,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
         pw_name(b.proj, a);
         if ((rc = mark(kn, i, pw_bytes(a), 2.0 * a.M * a.K * a.N, ((double)a.K * a.N + (double)a.M * a.N * (a.res ? 2 : 1)) * esz_d))) return rc;
         if (b.to_rowmajor) {
-            if ((rc = launch_pixels_to_rowmajor(n->E, out, B, b.Ho, b.Wo, b.d.cout, n->dtype, s))) return rc;
+            if ((rc = launch_pixels_to_rowmajor(n->E, out, B, b.Ho, b.Wo, b.d.cout, n->dtype, s, b.rev_torow))) return rc;
             if ((rc = mark("pixels_to_rowmajor_kernel", i, 2.0 * B * b.Ho * b.Wo * b.d.cout * esz_d, 0.0, 0.0))) return rc;
         }
         return probe(i, out, b.Ho * b.Wo, b.d.cout, b.out);
@@ -567,7 +604,7 @@ static int net_forward(cosy_net* n, int B, float* feat, float* pose, float* taps
     }
     PwArgs a{};
     a.A = n->act[cur]; a.Wp = n->head.Wp; a.out = n->Hd; a.scale = n->head.scale; a.bias = n->head.bias;
-    a.M = B * n->Hf * n->Wf; a.K = HEAD_IN; a.N = HEAD_C; a.HW = n->Hf * n->Wf; a.silu = 1; a.zeros = n->zeros;
+    a.M = B * n->Hf * n->Wf; a.K = HEAD_IN; a.N = HEAD_C; a.HW = n->Hf * n->Wf; a.silu = 1; a.zeros = n->zeros; a.rev = n->rev_head;
     if ((rc = launch_pw_gemm(a, n->head.cfg, n->dtype, s))) return rc;
     pw_name(n->head, a);
     if ((rc = mark(kn, 26, pw_bytes(a), 2.0 * a.M * a.K * a.N, ((double)a.M * a.K + (double)a.K * a.N) * esz_d))) return rc;
@@ -619,6 +656,7 @@ int cosy_effnet_b3_create(const float* host_params, size_t n_floats, int dtype, 
     n->Hs = out_dim(H, 3, 2); n->Ws = out_dim(W, 3, 2);
     {   // schedule knobs: fixed in the shipping build, env-overridable only under -DCOSY_TUNE (cosy_common.h)
         n->fuse = tune_int("COSY_FUSE", 1);
+        n->traversal = tune_int("COSY_TRAVERSAL", COSY_TRAVERSAL_DEFAULT) ? 1 : 0;
         // measured (256 crops): batched from block 19: +1.5 %, from 9: another +1.1 % over one-workgroup-per-sample everywhere; the early
         // blocks (Cmid <= 288, Cse <= 12) stay on se_kernel: two dependent launches cost what its one does
         n->se_batch_from = tune_int("COSY_SE_BATCH_FROM", 9);
@@ -692,6 +730,14 @@ int cosy_effnet_b3_set_profiling(cosy_net_t* n, int enable) {
     }
     n->prof_on = enable ? 1 : 0;
     n->prof_seg = 0;
+    return COSY_OK;
+}
+
+int cosy_effnet_b3_set_traversal(cosy_net_t* n, int mode) {
+    COSY_REQUIRE(n, "set_traversal: null net");
+    COSY_REQUIRE(mode == 0 || mode == 1, "set_traversal: bad mode %d (0 = forward, 1 = serpentine)", mode);
+    n->traversal = mode;
+    plan_traversal(n);
     return COSY_OK;
 }
 

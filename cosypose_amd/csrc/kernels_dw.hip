@@ -56,6 +56,7 @@ struct DwKArgs {
     const void* in; const float* w; const float* scale; const float* bias; void* out; float* partial;
     int H, W, C, Ho, Wo, lo, CGB, TH, TW, THin, TWin, ntx, n_tiles, n_chunks, n_jobs, dbg;
     const void* zeros;  // >= 16 zero bytes in global memory
+    int rev;            // DwArgs::rev
 };
 
 
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwKArgs a) {
     const int tid = threadIdx.x, nthr = blockDim.x;
     // XCD-aware decode: all channel chunks of one (sample, spatial tile) job run on the same XCD (id % 8), so the
     // 128-byte lines they share are fetched into / written back from ONE L2 (the per-XCD L2s are not coherent).
-    const int id = blockIdx.x, xcd = id & 7, jj = id >> 3;
+    const JobId jid = job_decode(blockIdx.x, gridDim.x, a.rev);
+    const int xcd = jid.xcd, jj = jid.jj;
     const int job = (jj / a.n_chunks) * 8 + xcd, chunk = jj % a.n_chunks;
     if (job >= a.n_jobs) return;
     const int tile_id = job % a.n_tiles, b = job / a.n_tiles;
@@ -194,7 +196,7 @@ static int launch_dw_t(const DwArgs& a, hipStream_t s) {
     k.in = a.in; k.w = a.w; k.scale = a.scale; k.bias = a.bias; k.out = a.out; k.partial = a.partial;
     k.H = a.H; k.W = a.W; k.C = a.C; k.Ho = a.Ho; k.Wo = a.Wo; k.lo = a.pad_lo;
     k.CGB = p.CGB; k.TH = p.TH; k.TW = p.TW; k.THin = p.THin; k.TWin = p.TWin; k.ntx = p.ntx; k.n_tiles = p.ntx * p.nty;
-    k.n_chunks = p.n_chunks; k.n_jobs = k.n_tiles * a.B; k.zeros = a.zeros;
+    k.n_chunks = p.n_chunks; k.n_jobs = k.n_tiles * a.B; k.zeros = a.zeros; k.rev = a.rev != 0;
     static const int dbg = tune_int("COSY_DW_DBG", 0);   // phase knock-out, timing experiments only
     k.dbg = dbg;
     dim3 grid((unsigned)cdiv(k.n_jobs, 8) * 8 * p.n_chunks), block(p.threads);

@@ -56,6 +56,7 @@ struct PwArgs {
                          //    32-byte pixels like a matrix-pipe front's segment (FuseArgs::x_perm); rows per sample in row-major order (HW a multiple of 2^lw)
     const struct SeArgs* se_fused;   // non-null: NO squeeze-excite launch ran -- every workgroup computes the gates of the samples under its
                                      // m-tile in its prologue from the squeeze partial sums (se_fused->gate == gate, written for probes)
+    int rev;             // 1: the launch walks its tiles in the opposite order (job_order.h; effnet.hip: plan_traversal)
 };
 int launch_pw_gemm(const PwArgs& a, PwCfg cfg, int dtype, hipStream_t s);
 void pw_kernel_name(const PwArgs& a, PwCfg c, int dtype, char* buf, size_t n);
@@ -70,6 +71,7 @@ struct DwArgs {
     float* partial;      // (B, n_tiles, C) per-tile sums of the activated output (SE squeeze)
     int B, H, W, C, Ho, Wo, k, s, pad_lo;
     const void* zeros;   // >= 16 zero bytes (global), source of the padding for the LDS-DMA staging
+    int rev;             // 1: the launch walks its jobs in the opposite order (job_order.h)
 };
 int dw_num_tiles(int C, int Ho, int Wo, int k);
 int launch_dwconv(const DwArgs& a, int dtype, hipStream_t s);
@@ -95,6 +97,7 @@ struct FuseArgs {
     int x_colmajor, d_colmajor;
     int x_chunked;       // wave kernel only: X is laid out [sample][ceil(Cin/16)][H*W][16] (PwArgs::out_chunked of the block before)
     int x_perm;          // ... with the pixels of a row permuted for a lane's run of P pixels (PwArgs::out_perm_lw / out_perm_lp)
+    int rev;             // every front kernel: 1 = the launch walks its jobs in the opposite order (job_order.h)
 };
 // tiled variant (LDS tile per workgroup) for high-resolution blocks whose row width the wave kernel is not built for
 bool tile_supported(int Cin, int Cmid, int k, int s, int dtype);
@@ -138,6 +141,7 @@ struct StemFrontArgs {
     void* dump;             // stem_front_dump_bytes() of scratch (finished rows outside a job's band land there)
     const void* zeros;      // the zero page: must lie behind X, within 4 GB of it (the padding taps are fetched from it by offset)
     int B, H, W;
+    int rev;                // 1: the launch walks its workgroups in the opposite order (job_order.h)
 };
 bool stem_front_supported(int dtype, int H, int W);
 int stem_front_tiles(int H);                 // upper bound of the squeeze partial-sum tiles per sample a launch writes
@@ -177,6 +181,6 @@ struct ActLayout { int chunked = 0, colH = 0, perm_lw = 0, perm_lp = 0; };
 int launch_nhwc_to_nchw(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* out, hipStream_t s, const ActLayout& l);
 int launch_taps(const void* act /*(B,HW,C)*/, int B, int HW, int C, int dtype, float* taps /*(B,9,16)*/, int tap_index, hipStream_t s, const ActLayout& l);
 // out (B, H*W, C) row-major pixels <- in (B, W*H, C) column-major pixels: the exit of a resolution stage that is stored transposed
-int launch_pixels_to_rowmajor(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s);
+int launch_pixels_to_rowmajor(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s, int rev = 0);      // rev: job_order.h
 
 }  // namespace cosy

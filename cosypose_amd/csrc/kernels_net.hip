@@ -139,6 +139,7 @@ struct PwKArgs {
     // expand FC stored (Cse, K) + bias (K); se_wr == nullptr: the gate rows are read from `gate` (a squeeze-excite kernel wrote them)
     const float* se_partial; const float* se_wr; const float* se_br; const float* se_we; const float* se_be; float* gate_out;
     int se_tiles, Cse; float inv_hw;
+    int rev;              // PwArgs::rev
 };
 
 // ------------------------------------------------------------------------------------------
@@ -191,7 +192,8 @@ __global__ __launch_bounds__(NWV * 64, pw_bound_waves(NI, MI, NWV)) void pw_gemm
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kgp = KG == 1 ? 0 : wave / GW, wq = KG == 1 ? wave : wave % GW;      // K-group, wave inside the group (constants for the plain tiles)
     const int wm = wq / WN, wn = wq % WN;
-    const int id = blockIdx.x, xcd = id & 7, jj = id >> 3;
+    const JobId jid = job_decode(blockIdx.x, gridDim.x, a.rev);
+    const int xcd = jid.xcd, jj = jid.jj;
     const int mt = (jj / a.NT) * 8 + xcd, nt = jj % a.NT;
     if (mt >= a.MT) return;
     const int m0 = mt * BM, n0 = nt * BN;
@@ -672,7 +674,7 @@ static int launch_pw_t(const PwArgs& a, PwCfg c, int dtype, hipStream_t s) {
     PwKArgs k;
     k.a_chunked = a.a_chunked; k.out_chunked = a.out_chunked; k.res_chunked = a.res_chunked; k.out_perm_lw = a.out_chunked ? a.out_perm_lw : 0; k.out_perm_lp = a.out_perm_lp;
     k.A = a.A; k.Wp = a.Wp; k.out = a.out; k.scale = a.scale; k.bias = a.bias; k.res = a.res; k.gate = a.gate;
-    k.M = a.M; k.K = a.K; k.N = a.N; k.HW = a.HW; k.silu = a.silu;
+    k.M = a.M; k.K = a.K; k.N = a.N; k.HW = a.HW; k.silu = a.silu; k.rev = a.rev != 0;
     k.MT = cdiv(a.M, pw_bm(c)); k.NT = cdiv(a.N, pw_bn(c));
     k.nkb_total = pw_nkb_total(a.K, dtype); k.nkb_valid = cdiv(a.K, pw_kb(dtype));
     const int grid = cdiv(k.MT, 8) * 8 * k.NT;
@@ -772,6 +774,7 @@ struct FuseKArgs {
     void* D; float* partial; const void* zeros;
     int H, W, Cin, Cmid, Ho, Wo, lo, TH, TW, THin, TWin, MB, ntx, n_tiles, nkb_total, dbg;
     unsigned rcp_tw;   // ceil(2^16 / TWin): p / TWin == (p * rcp_tw) >> 16 for the tile's pixel range (checked on the host)
+    int rev;           // FuseArgs::rev
 };
 
 // T = storage type of X/D (and of the MFMA operands), ET = element type of the LDS tile of expanded activations
@@ -792,7 +795,7 @@ __global__ __launch_bounds__(384) void mbconv_tile_kernel(FuseKArgs a) {
     float* red = wl + KS * KS * CC;
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthr >> 6;
-    const int job = blockIdx.x, tile_id = job % a.n_tiles, b = job / a.n_tiles;
+    const int job = job_linear(blockIdx.x, gridDim.x, a.rev), tile_id = job % a.n_tiles, b = job / a.n_tiles;
     const int tx = tile_id % a.ntx, ty = tile_id / a.ntx;
     const int oy0 = ty * a.TH, ox0 = tx * a.TW;
     const int iy0 = oy0 * S - a.lo, ix0 = ox0 * S - a.lo;
@@ -955,6 +958,7 @@ static int launch_tile_t(const FuseArgs& a, hipStream_t s) {
     k.TH = p.TH; k.TW = p.TW; k.THin = p.THin; k.TWin = p.TWin; k.MB = p.MB; k.ntx = p.ntx; k.n_tiles = p.ntx * p.nty;
     k.nkb_total = pw_nkb_total(a.Cin, sizeof(T) == 4 ? COSY_F32 : COSY_BF16);   // k-block geometry depends on the element size only
     k.rcp_tw = (65536u + p.TWin - 1) / p.TWin;
+    k.rev = a.rev != 0;
     static const int dbg = tune_int("COSY_FUSE_DBG", 0);   // phase knock-out, timing experiments only
     k.dbg = dbg;
     for (int q = 0; q < p.MB * 16; ++q)
@@ -1008,6 +1012,7 @@ struct FuseSKArgs {
     unsigned rcp_w;   // ceil(2^16 / W): p / W == (p * rcp_w) >> 16 for p < MBr*16 (checked on the host)
     int xpose;        // the depthwise phase walks the TRANSPOSED map (7x10 maps: 10 rows of 7 pixels): Ho / Wo / THin / TWin are the walked
                       // dimensions, the taps arrive as w[kx][ky]; H / W stay the stored map (the expansion decodes pixels with them)
+    int rev;          // FuseArgs::rev
 };
 
 template <typename T, int KS, int S, int R, int KBN, int MPW, bool ROWMAP = false>
@@ -1029,7 +1034,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float* red = (float*)(Pl + 2 * PBYTES);
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthr >> 6;
-    const int b = blockIdx.x / a.ncg, cg = blockIdx.x - b * a.ncg;
+    const int job = job_linear(blockIdx.x, gridDim.x, a.rev), b = job / a.ncg, cg = job - b * a.ncg;
     const int nchunks = a.Cmid / CC;
     const int ch0 = cg * a.cpw, ch1 = min(nchunks, ch0 + a.cpw);
     const int prow = lane & 15, kg = lane >> 4;
@@ -1282,6 +1287,7 @@ static int launch_fuse_small_t(const FuseArgs& a, hipStream_t s) {
     k.THin = p.THin; k.TWin = p.TWin; k.nkb_total = pw_nkb_total(a.Cin, COSY_BF16); k.MBr = p.MBr; k.ncg = p.ncg; k.cpw = p.cpw;
     k.xpose = p.xpose; k.Ho = p.Ho; k.Wo = p.Wo;       // walked dimensions (== a.Ho / a.Wo unless transposed)
     k.rcp_w = (65536u + a.W - 1) / a.W;
+    k.rev = a.rev != 0;
     static const int dbg = tune_int("COSY_SMALL_DBG", 0);   // timing experiments only
     k.dbg = dbg;
     for (int q = 0; q < p.MBr * 16; ++q)

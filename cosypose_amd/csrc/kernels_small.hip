@@ -303,8 +303,8 @@ int launch_taps(const void* act, int B, int HW, int C, int dtype, float* taps, i
 // exit of a resolution stage stored column-major (240x320 crops: the 30x40 and 15x20 maps, whose columns fill the wave kernel's lanes): one
 // copy puts the last block's output back into row-major order for the kernels behind it.  16 bytes per thread, destination-contiguous.
 // ==========================================================================================
-__global__ __launch_bounds__(256) void pixels_to_rowmajor_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int H, int W, int C16, long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;     // destination index in (b, y, x, c16)
+__global__ __launch_bounds__(256) void pixels_to_rowmajor_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int H, int W, int C16, long n, int rev) {
+    const long i = (long)job_linear(blockIdx.x, gridDim.x, rev) * 256 + threadIdx.x;     // destination index in (b, y, x, c16)
     if (i >= n) return;
     const int c = (int)(i % C16);
     long r = i / C16;
@@ -313,13 +313,13 @@ __global__ __launch_bounds__(256) void pixels_to_rowmajor_kernel(const uint4* __
     const long b = r / H;
     out[i] = in[((b * W + x) * H + y) * C16 + c];
 }
-int launch_pixels_to_rowmajor(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s) {
+int launch_pixels_to_rowmajor(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s, int rev) {
     if (B == 0) return COSY_OK;
     const int esz = dtype == COSY_F32 ? 4 : 2;
     if ((C * esz) % 16 != 0) { set_error("pixels_to_rowmajor: %d channels of %d bytes are not whole 16-byte pieces", C, esz); return COSY_EINVAL; }
     const int C16 = C * esz / 16;
     const long n = (long)B * H * W * C16;
-    hipLaunchKernelGGL(pixels_to_rowmajor_kernel, dim3((unsigned)cdiv(n, 256l)), dim3(256), 0, s, (const uint4*)in, (uint4*)out, H, W, C16, n);
+    hipLaunchKernelGGL(pixels_to_rowmajor_kernel, dim3((unsigned)cdiv(n, 256l)), dim3(256), 0, s, (const uint4*)in, (uint4*)out, H, W, C16, n, rev != 0);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }

@@ -43,6 +43,7 @@ struct SmxKArgs {
     // the 10 columns are the walk rows); cv = valid pixels of a walk row (8, or 7: the eighth is expanded from a clamped address, zeroed as a tap operand, left out of
     // the squeeze sums and not stored); HW = pixels of the map
     int HW, Wm, tr, cv;
+    int rev;      // FuseArgs::rev
 };
 enum { SMX_HDR = 1024 };       // bytes of a chunk's parameter header [b0 * log2 e 48][s1 48][b1 48] fp32 (padded to one DMA instruction)
 constexpr int smx_pbytes(int ks) { return SMX_HDR + 3 * ks * 2 * 512; }   // + [tile 3][ky][operand 2][lane 64] 8-byte Toeplitz fragments
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256 * SPW) __attribute__((amdgpu_waves_per_eu(SPW =
     char* Wl = smem + SPW * EHB;                   // shared by the workgroup's samples
     char* Pl = Wl + NI * NF * 1024;                // (shared)
     float* red = (float*)(Pl + 2 * PBYTES) + sp * NSEG * CC;        // per sample: [NSEG segments][48]
-    const int grp = blockIdx.x / a.ncg, cg = blockIdx.x - grp * a.ncg;
+    const int job = job_linear(blockIdx.x, gridDim.x, a.rev), grp = job / a.ncg, cg = job - grp * a.ncg;
     const int bs = grp * SPW + sp;                 // this wave's sample
     const bool valid = SPW == 1 || bs < a.B;       // (wave-uniform) false: the missing partner of an odd batch's last sample
     const int b = SPW == 1 ? bs : min(bs, a.B - 1);
@@ -362,6 +363,7 @@ static int launch_smx_t(const FuseArgs& a, int dtype, hipStream_t s) {
     k.B = a.B; k.Cin = a.Cin; k.Cmid = a.Cmid; k.nkb_total = (cdiv(a.Cin, 32) + 1) & ~1;
     k.HW = a.H * a.W; k.Wm = a.W; k.tr = small_mx_transposed(a.H, a.W); k.cv = a.H * a.W == 64 ? 8 : 7;
     k.ncg = 0;      // (launch_smx_ks)
+    k.rev = a.rev != 0;
     k.dbg = tune_int("COSY_SMALL_DBG", 0);
     const int kbn = cdiv(a.Cin, 32);
     if (a.k == 3 && kbn == 8) return launch_smx_k<T, 3, 8>(k, dtype, s);

@@ -76,6 +76,7 @@ struct StemFrontKArgs {
     void* dump;               // >= 128 * 32 bytes: where the finished rows outside a job's band go
     long zrel;                // zero page - X, in bytes (0 <= zrel < 2^32 - 2^24: checked by the launcher)
     int B, H, W, Hs, Ws, rsplit, rows_per, n_tiles;
+    int rev;                  // StemFrontArgs::rev
 };
 
 enum { SF_KBN = 3, SF_PF = (4 + 9) * 16 };
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(192, 2) void stem_front_kernel(StemFrontKArgs a) {
     // A workgroup = the THREE chunk jobs of one (sample, half, band): they read the same input rows at the same time, so the CU's L1 serves two
     // of the three (as four unrelated jobs per workgroup the kernel moved 12x the input through L2 -> L1: 427 us against 362 for the two kernels
     // it replaces).  XCD-aware order (block id % 8 = XCD): the workgroups of one sample stay on one XCD.
-    const int id = blockIdx.x, xcd = id & 7, g = id >> 3;
+    const JobId jid = job_decode(blockIdx.x, gridDim.x, a.rev);
+    const int xcd = jid.xcd, g = jid.jj;
     const int wps = 2 * a.rsplit;               // workgroups per sample
     const int b = (g / wps) * 8 + xcd, jrem = g % wps;
     const int ch = wave, seg = jrem & 1, band = jrem >> 1;
@@ -327,7 +329,7 @@ int launch_stem_front(const StemFrontArgs& f, int dtype, int* n_tiles_out, hipSt
     StemFrontKArgs k;
     k.X = f.X; k.Wp = f.Wp; k.params = f.params; k.D = f.D; k.partial = f.partial; k.dump = f.dump;
     k.B = f.B; k.H = f.H; k.W = f.W; k.Hs = f.H / 2; k.Ws = f.W / 2;
-    k.rsplit = rsplit; k.rows_per = cdiv(k.Hs, k.rsplit); k.n_tiles = 2 * rsplit;
+    k.rsplit = rsplit; k.rows_per = cdiv(k.Hs, k.rsplit); k.n_tiles = 2 * rsplit; k.rev = f.rev != 0;
     k.zrel = (long)((const char*)f.zeros - (const char*)f.X);
     COSY_REQUIRE(k.zrel >= 0 && k.zrel < ((long)1 << 32) - ((long)1 << 24) && (long)f.B * f.H * f.W * 16 <= k.zrel,
                  "stem_front: the zero page must lie behind the input, within 4 GB of its start (zrel %ld)", k.zrel);

@@ -51,6 +51,7 @@ struct WaveKArgs {
     // -DCOSY_TUNE only (null in the shipping library): s_memtime stamps of one job in every `stamp_stride`-th workgroup (wave 0), see WAVE_STAMP
     unsigned long long* stamps; int stamp_stride, stamp_slots;
     int wpb;                 // jobs (waves) per workgroup
+    int rev;                 // FuseArgs::rev: the workgroups of an XCD take their runs of wpb jobs in the opposite order
 };
 // Timeline of a job (-DCOSY_WAVE_STAMPS build only): the shader clock (s_memtime) at the job's start, behind its prologue, at the start of every
 // input row (scalar bookkeeping: sum / min / max of the row-to-row intervals) and at its end -> 8 words per recorded job.  A first version with
@@ -339,7 +340,8 @@ __global__ __launch_bounds__(256, MINW) void mbconv_wave_kernel(WaveKArgs a) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = lane & 15, kg = lane >> 4;
     // XCD-aware job order: the chunks of one sample run on one XCD (block id % 8), 4 jobs (waves) per block
-    const int id = blockIdx.x, xcd = id & 7, sidx = (id >> 3) * a.wpb + wave;
+    const JobId jid = job_decode(blockIdx.x, gridDim.x, a.rev);
+    const int xcd = jid.xcd, sidx = jid.jj * a.wpb + wave;
     // a job = (sample, chunk, row band); the jobs of one sample stay on one XCD
     const int jps = a.nchunks * a.rsplit;
     const int b = (sidx / jps) * 8 + xcd, jrem = sidx % jps;
@@ -1253,7 +1255,7 @@ static int launch_wave_t(const FuseArgs& a, int* n_tiles_out, hipStream_t s) {
         k.H = a.W; k.W = a.H; k.Ho = a.Wo; k.Wo = a.Ho;
         k.xs_pix = x_dy; k.xs_row = x_dx; k.ds_pix = d_dy; k.ds_row = d_dx;
     }
-    k.nkb_total = (p.kbn + 1) & ~1; k.nchunks = a.Cmid / (16 * p.ni); k.rsplit = 1; k.rows_per = a.Ho;
+    k.nkb_total = (p.kbn + 1) & ~1; k.nchunks = a.Cmid / (16 * p.ni); k.rsplit = 1; k.rows_per = a.Ho; k.rev = a.rev != 0;
     const int ks_ = a.k, st_ = a.s, kbn_ = p.kbn, ppl_ = p.ppl, ni_ = p.ni;
     const bool fw_ = p.fullw;
 #define X(KS, S, KBN, PPL, NI, FW, MW, RSP) \

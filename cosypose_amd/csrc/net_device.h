@@ -1,6 +1,7 @@
 // Device-side helpers shared by the backbone kernel files (gfx950, wave64).
 #pragma once
 #include "kernels_net.h"
+#include "job_order.h"      // the order in which a launch walks its jobs: job_decode / job_linear
 
 namespace cosy {
 

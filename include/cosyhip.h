@@ -123,6 +123,13 @@ typedef struct {
 int cosy_effnet_b3_set_profiling(cosy_net_t* net, int enable);
 int cosy_effnet_b3_profile_read(cosy_net_t* net, cosy_prof_rec_t* recs, int cap, int* n_out);
 
+/* ---- sample order of the backbone's launches (tests and A/B timing) --------------------------
+ * mode 0: every launch walks the samples of the batch forward.  mode 1 (serpentine): a launch that reads a large
+ * activation walks them in the opposite order to the launch that wrote it, so that it starts with what was written
+ * last; a new net starts in mode 1.  The order changes no arithmetic: both modes return the same bits.  Takes effect from
+ * the next cosy_effnet_b3_forward on this net; any other mode returns COSY_EINVAL. */
+int cosy_effnet_b3_set_traversal(cosy_net_t* net, int mode);
+
 /* ---- geometry ---------------------------------------------------------------------------
  * PosePredictor.crop_inputs without the pixel work (cosypose/models/pose.py:45-67):
  * project_points_robust + boxes_from_uv (cosypose/lib3d/camera_geometry.py:18-42), deepim_boxes
