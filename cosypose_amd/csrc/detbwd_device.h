@@ -2,7 +2,7 @@
 // with the transposed, tap-flipped weight, the parity classes of a stride-2 layer, and the store that adds up to two operands (SAME, EVEN,
 // NEAREST_T), applies the ReLU mask of the layer below and converts ONCE to the rows' type.  kernels_detbwd.hip instantiates it for float32 rows
 // (cosy_head_dgrad, cosy_trunk_dgrad: the instruction streams hipcc gave that file's own text of the kernel, kernel for kernel),
-// kernels_detbwd16.hip for bfloat16 rows (cosy_trunk_dgrad16).
+// kernels_detbwd16.hip for bfloat16 rows (cosy_trunk_dgrad16, and cosy_head_dgrad16, whose NCHW store writes the accumulator as float32).
 //   float32 rows: every term of a block is one fmaf, four v_mfma_f32_16x16x4_f32 per (block of 16 o, live tap).
 //   16-bit rows: one v_mfma_f32_16x16x32 per (block of 32 o, live tap); the products are exact in float32, the accumulation is float32.
 // Store, per element: t = acc; t = t + (float)operand, in the order given, every + one rounded float32 add; t = y <= 0 ? +0.0 : t (a NaN y
@@ -20,6 +20,26 @@ using namespace headgemm;
 int wgrad_slab_rows_of(int M);
 long wgrad_slab_floats_of(int ksize, int c_in, int c_out);
 int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s);
+// the heads' form: outputs [0, n_split) to dw0 / db0 (db0 null: no bias gradient), the rest to dw1 / db1; ksize 2: (C, O, 2, 2)
+int wgrad_combine_split(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, int n_split, const float* scale, float* dw0, float* db0,
+                        float* dw1, float* db1, hipStream_t s);
+
+// the element (o, tap, c) of a layer's weight in torchvision's layout; o runs over the first tensor's outputs, then the second's.
+// ksize 1 / 3: (O, C, k, k) or (O, C); ksize 2: ConvTranspose2d's (C, O, 2, 2)
+__device__ __forceinline__ float weight_at(const float* __restrict__ w0, const float* __restrict__ w1, int ksize, int C, int n0, int n1, int o, int tap, int c) {
+    if (ksize == 2) return w0[((long)c * n0 + o) * 4 + tap];
+    const int T = ksize == 3 ? 9 : 1;
+    return o < n0 ? w0[((long)o * C + c) * T + tap] : w1[((long)(o - n0) * C + c) * T + tap];
+}
+
+// ConvTranspose2d(2, 2)'s data gradient on rows of T: dethead_device.h's DeconvGradPolicy (conv_gemm_kernel's four stride-2 taps) with the mask
+// rows y in the rows' type
+template <typename T> struct grad_epi_of { const T* y; };
+template <typename T> struct DeconvGradPolicyOf {
+    static constexpr int STRIDE = 2;
+    static constexpr bool TRUNK = false, GRAD = true, TAPS2 = true;
+    typedef grad_epi_of<T> epi_t;
+};
 
 enum { ADD_NONE = 0, ADD_SAME = COSY_TRUNK_ADD_SAME, ADD_EVEN = COSY_TRUNK_ADD_EVEN, ADD_NEAREST_T = COSY_TRUNK_ADD_NEAREST_T };
 

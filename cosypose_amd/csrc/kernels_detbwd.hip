@@ -51,14 +51,6 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_grad_pack_kernel(const floa
     rows[i] = v;
 }
 
-// the element (o, tap, c) of a layer's weight in torchvision's layout; o runs over the first tensor's outputs, then the second's.
-// ksize 1 / 3: (O, C, k, k) or (O, C); ksize 2: ConvTranspose2d's (C, O, 2, 2)
-__device__ __forceinline__ float weight_at(const float* __restrict__ w0, const float* __restrict__ w1, int ksize, int C, int n0, int n1, int o, int tap, int c) {
-    if (ksize == 2) return w0[((long)c * n0 + o) * 4 + tap];
-    const int T = ksize == 3 ? 9 : 1;
-    return o < n0 ? w0[((long)o * C + c) * T + tap] : w1[((long)(o - n0) * C + c) * T + tap];
-}
-
 // fragment order of cosy_head_conv, float32: element [nt][tap][kb][lane][e] holds W[16 nt + (lane & 15)][tap][16 kb + 4 (lane >> 4) + e].
 // forward: W = the layer's (rows o; ksize 2: rows (o, dy, dx), one tap), the host packing's bytes, and the bias or shift padded like it;
 // backward: W = ws = w scale[o] rounded once (scale null: w), rows c, reduction o, taps flipped (ksize 3) or (dy, dx) (ksize 2).
@@ -312,16 +304,20 @@ int run_weight_pack(const char* fn, const float* w0, const float* b0, const floa
 }  // namespace
 
 // The slab rule and the second pass do not depend on the type of the rows: kernels_detbwd16.hip (section 30) reaches them here (host code only;
-// declared in detbwd_device.h).  One scale, no sibling: the trunk's form.
+// declared in detbwd_device.h).  wgrad_combine: one scale, no sibling, the trunk's form; wgrad_combine_split: the heads'.
 namespace detbwd {
 int wgrad_slab_rows_of(int M) { return wgrad_slab_rows(M); }
 long wgrad_slab_floats_of(int ksize, int c_in, int c_out) { return wgrad_slab_floats(ksize, c_in, c_out); }
-int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s) {
-    const long n_out = (long)c_out * (ksize == 3 ? 9 : 1) * c_in + c_out;
-    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(cdiv(n_out, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, partial, nslab, slab_floats, ksize, c_in, c_out, c_out, scale,
-                       dw, db, (float*)nullptr, (float*)nullptr);
+int wgrad_combine_split(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, int n_split, const float* scale, float* dw0, float* db0,
+                        float* dw1, float* db1, hipStream_t s) {
+    const long n_out = (long)c_out * (ksize == 3 ? 9 : ksize == 2 ? 4 : 1) * c_in + c_out;
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(cdiv(n_out, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, partial, nslab, slab_floats, ksize, c_in, c_out, n_split, scale,
+                       dw0, db0, dw1, db1);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
+}
+int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s) {
+    return wgrad_combine_split(partial, nslab, slab_floats, ksize, c_in, c_out, c_out, scale, dw, db, nullptr, nullptr, s);
 }
 }  // namespace detbwd
 }  // namespace cosy

@@ -1,9 +1,12 @@
-// The backward of the detector's trunk on bfloat16 rows.  The parameters stay float32 (the master weights); the rows the
-// forward keeps, the gradient rows and both packed weights are bfloat16, every accumulation is float32.
-//   * weight_pack16_kernel: a float32 parameter in torchvision's layout -> fwd, the bytes of the host packing of bf16(w) that cosy_trunk_conv reads
-//     at COSY_BF16, fwd_bias, and bwd, the transposed, tap-flipped packing of ws = bf16(fl32(w scale[o])) in the same 16-bit fragment order.
-//   * grad_pack16_kernel: the losses' NCHW float32 gradients -> bfloat16 rows.
-//   * the data gradient is detbwd_device.h's kernel on bfloat16 rows: one v_mfma_f32_16x16x32_bf16 per (block of 32 o, live tap).
+// The backward of the detector's trunk and heads (section 32) on bfloat16 rows: ONE set of kernels, as kernels_detbwd.hip
+// is for float32.  The parameters stay float32 (the master weights); the rows the forward keeps, the gradient rows and both packed weights are
+// bfloat16, every accumulation is float32.
+//   * weight_pack16_kernel: float32 parameters in torchvision's layout (one layer, or two siblings of one GEMM, or ConvTranspose2d(2, 2)) -> fwd,
+//     the bytes of the host packing of bf16(w) that cosy_head_conv / cosy_trunk_conv read at COSY_BF16, fwd_bias, and bwd, the transposed,
+//     tap-flipped packing of ws = bf16(fl32(w scale[o])) (the heads: no scale) in the same 16-bit fragment order.
+//   * grad_pack16_kernel: the losses' NCHW float32 gradients (one tensor, or a sibling pair) -> bfloat16 rows, the pad columns +0.0.
+//   * the data gradient is detbwd_device.h's kernel on bfloat16 rows: one v_mfma_f32_16x16x32_bf16 per (block of 32 o, live tap); the heads' first
+//     layers store its accumulator as float32 NCHW; the deconvolution's is dethead_device.h's conv_gemm_kernel under DeconvGradPolicyOf<bf16_t>.
 //   * wgrad16_kernel: dW[o][tap][c] = sum over OUTPUT cells of g[cell][o] x[cell + tap][c] with the CELLS as the k dimension of
 //     v_mfma_f32_16x16x32_bf16.  The instruction wants eight consecutive cells of ONE channel per lane for both operands; the rows are stored
 //     cell-major.  A wave loads whole row segments (16 bytes: eight channels of one cell per lane), lays 32 cells x 16 channels images in LDS and
@@ -48,15 +51,20 @@ __device__ __forceinline__ bf16x8 image_frag(const unsigned char* image, int rd)
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// [nt][tap][kb][lane][e] holds W[16 nt + (lane & 15)][tap][32 kb + 8 (lane >> 4) + e]: the 16-bit fragment order of cosy_head_conv
-__global__ __launch_bounds__(HEAD_THREADS) void weight_pack16_kernel(const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                     int taps, int C, int O, bf16_t* __restrict__ fwd, float* __restrict__ fwd_bias,
-                                                                     bf16_t* __restrict__ bwd, long n_fwd, long n_bwd, int n_bias) {
+// [nt][tap][kb][lane][e] holds W[16 nt + (lane & 15)][tap][32 kb + 8 (lane >> 4) + e]: the 16-bit fragment order of cosy_head_conv.  The rules are
+// kernels_detbwd.hip's weight_pack_kernel's (siblings w0 then w1; ksize 2: forward rows (o, dy, dx) with one tap, backward taps (dy, dx)); the
+// trunk's layers are the case n1 = 0, b0 = shift.  scale: one float32 product, then ONE rounding to bfloat16
+__global__ __launch_bounds__(HEAD_THREADS) void weight_pack16_kernel(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
+                                                                     const float* __restrict__ b1, const float* __restrict__ scale, int ksize, int C, int n0, int n1,
+                                                                     bf16_t* __restrict__ fwd, float* __restrict__ fwd_bias, bf16_t* __restrict__ bwd, long n_fwd,
+                                                                     long n_bwd, int n_bias) {
     const long i = (long)blockIdx.x * HEAD_THREADS + threadIdx.x;
+    const int O = n0 + n1;
     if (i < n_fwd + n_bwd) {
         const bool back = i >= n_fwd;
         const long k = back ? i - n_fwd : i;
-        const int N = back ? C : O, K = back ? O : C;          // rows and reduction length of this packing
+        const int taps = back ? (ksize == 3 ? 9 : ksize == 2 ? 4 : 1) : (ksize == 3 ? 9 : 1);
+        const int N = back ? C : (ksize == 2 ? 4 * O : O), K = back ? O : C;           // rows and reduction length of this packing
         const int KBn = (K + 31) / 32;
         const int e = (int)(k & 7), lane = (int)((k >> 3) & 63);
         const long s = k >> 9;
@@ -64,47 +72,63 @@ __global__ __launch_bounds__(HEAD_THREADS) void weight_pack16_kernel(const float
         const int n = 16 * nt + (lane & 15), r = 32 * kb + 8 * (lane >> 4) + e;
         float v = 0.f;
         if (n < N && r < K) {
-            if (!back) v = w[((long)n * C + r) * taps + tap];
+            if (!back) v = ksize == 2 ? weight_at(w0, w1, 2, C, n0, n1, n >> 2, n & 3, r) : weight_at(w0, w1, ksize, C, n0, n1, n, tap, r);
             else {
-                v = w[((long)r * C + n) * taps + (taps - 1 - tap)];
+                v = weight_at(w0, w1, ksize, C, n0, n1, r, ksize == 3 ? 8 - tap : tap, n);
                 if (scale != nullptr) v = v * scale[r];
             }
         }
         (back ? bwd : fwd)[k] = (bf16_t)v;
     } else if (i < n_fwd + n_bwd + n_bias) {
         const int n = (int)(i - n_fwd - n_bwd);
-        fwd_bias[n] = n < O ? shift[n] : 0.f;
+        const int o = ksize == 2 ? n >> 2 : n;
+        float v = 0.f;
+        if (o < O) v = o < n0 ? b0[o] : b1[o - n0];
+        fwd_bias[n] = v;
     }
 }
 
-// one thread: eight channels of one cell; neighbouring threads take neighbouring cells of the same channels
-__global__ __launch_bounds__(HEAD_THREADS) void grad_pack16_kernel(const float* __restrict__ g, bf16_t* __restrict__ rows, int C, int HW, long total) {
+// NCHW float32 (B, n0, HW) and (B, n1, HW) -> bfloat16 rows (B HW, GP): the columns of the first, then of the second, then +0.0; a null tensor is
+// zeros.  One thread: eight columns of one cell; neighbouring threads take neighbouring cells of the same columns
+__global__ __launch_bounds__(HEAD_THREADS) void grad_pack16_kernel(const float* __restrict__ g0, const float* __restrict__ g1, bf16_t* __restrict__ rows, int n0,
+                                                                   int n1, int GP, int HW, long total) {
     const long i = (long)blockIdx.x * HEAD_THREADS + threadIdx.x;
     if (i >= total) return;
-    const int C8 = C / 8;
+    const int G8 = GP / 8;
     const long pix = i % HW, bc = i / HW;
-    const long b = bc / C8;
-    const int c0 = (int)(bc - b * C8) * 8;
+    const long b = bc / G8;
+    const int c0 = (int)(bc - b * G8) * 8;
     float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = g != nullptr ? g[(b * C + c0 + e) * HW + pix] : 0.f;
-    store8(rows + (b * HW + pix) * C + c0, v);
+    for (int e = 0; e < 8; ++e) {
+        const int col = c0 + e;
+        v[e] = 0.f;
+        if (col < n0) { if (g0 != nullptr) v[e] = g0[(b * n0 + col) * HW + pix]; }
+        else if (col < n0 + n1) { if (g1 != nullptr) v[e] = g1[(b * n1 + (col - n0)) * HW + pix]; }
+    }
+    store8(rows + (b * HW + pix) * GP + c0, v);
 }
 
-// MODE 0: 1x1; 1: 3x3, pad 1.  A wave owns 16 outputs o x 16 CT channels c x all taps of one slab of the M OUTPUT cells, as kernels_detbwd.hip's
-// wgrad_kernel does, and writes the same partial tile.  A k-step is 32 cells: the wave stages g (32 cells x its 16 o) and, per tap or channel
-// tile, x (32 cells x 16 c) as images, then reads every image back as an operand: A = g^T (row o), B = x (column c).  The bias gradient is the
-// product against a column of ones, taken by the waves of channel group 0.
+// MODE 0: 1x1 (and linear); 1: 3x3, pad 1; 2: ConvTranspose2d(2, 2), stride 1 only.  A wave owns 16 outputs o x 16 CT channels c x all taps of one
+// slab of the M cells of the k dimension, as kernels_detbwd.hip's wgrad_kernel does, and writes the same partial tile.  A k-step is 32 cells:
+// the wave stages g (32 cells x its 16 o) and, per tap or channel tile, x (32 cells x 16 c) as images, then reads every image back as an operand:
+// A = g^T (row o), B = x (column c).  MODE 2: the k dimension is the cells of x on (H, W); g lives on (2H, 2W) and is staged once per tap (dy, dx),
+// the cell (2y + dy, 2x + dx) of g against the cell (y, x) of x, four channel tiles of x.  The bias gradient is the product against a column of
+// ones (MODE 2: one per tap, so every row of g is counted once), taken by the waves of channel group 0.  GP: the columns of a row of g (the heads
+// round c_out up to 8, the pad columns hold +0.0; the trunk: c_out).
 template <int MODE, int STRIDE>
-__global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_layer_t a, const bf16_t* __restrict__ g, const int M, const int slab, const int n_waves,
-                                                               const int c_groups, const int want_db, float* __restrict__ partial, const long slab_floats) {
-    constexpr int TAPS = MODE == 0 ? 1 : 9, CT = MODE == 0 ? 4 : 1, IMAGES = 1 + TAPS * CT;
+__global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_layer_t a, const bf16_t* __restrict__ g, const int GP, const int M, const int slab,
+                                                               const int n_waves, const int c_groups, const int want_db, float* __restrict__ partial,
+                                                               const long slab_floats) {
+    static_assert(STRIDE == 1 || (STRIDE == 2 && MODE != 2), "stride 2: 1x1 and 3x3 only");
+    constexpr int TAPS = MODE == 0 ? 1 : MODE == 1 ? 9 : 4, CT = MODE == 1 ? 1 : 4;
+    constexpr int GI = MODE == 2 ? 4 : 1, XI = MODE == 1 ? 9 : 4, IMAGES = GI + XI;         // images of g and of x per k-step
     __shared__ __attribute__((aligned(16))) unsigned char lds[HEAD_THREADS / 64][IMAGES * WG_IMAGE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wv = blockIdx.x * (HEAD_THREADS / 64) + wave;
     if (wv >= n_waves) return;                                 // wave-uniform: the waves that stay have EXEC all ones
     unsigned char* const img_g = lds[wave];
-    unsigned char* const img_x = img_g + WG_IMAGE;
+    unsigned char* const img_x = img_g + GI * WG_IMAGE;
     const int ot = wv / c_groups, cg = wv - ot * c_groups;
     const int j = lane & 15, kq = lane >> 4;
     const int C = a.c_in, O = a.c_out;
@@ -126,16 +150,27 @@ __global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_l
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // one k-step's rows, loaded one step ahead of their use: gv = g (this lane's cell, eight of the wave's 16 o), xv = x per channel tile or tap
-    bf16x8 gv, xv[TAPS * CT];
+    // one k-step's rows, loaded one step ahead of their use: gv = g (this lane's cell, eight of the wave's 16 o; MODE 2: per tap), xv = x per
+    // channel tile or tap
+    bf16x8 gv[GI], xv[XI];
     auto load_step = [&](const long k0) {
         {
             const long cell = k0 + sc;
             const int o = ot * 16 + 8 * sh;
-            gv = zero;
-            if (cell < k_end && o < O) gv = *(const bf16x8*)(g + cell * O + o);
+            const bool in = cell < k_end && o < GP;
+#pragma unroll
+            for (int t = 0; t < GI; ++t) gv[t] = zero;
+            if constexpr (MODE != 2) {
+                if (in) gv[0] = *(const bf16x8*)(g + cell * GP + o);
+            } else if (in) {
+                const int H = a.H[0], W = a.W[0];              // the layer's INPUT map; g lives on (2H, 2W)
+                const long b = cell / ((long)H * W);
+                const int pix = (int)(cell - b * H * W), py = pix / W, px = pix - py * W;
+#pragma unroll
+                for (int t = 0; t < GI; ++t) gv[t] = *(const bf16x8*)(g + ((b * 2 * H + 2 * py + (t >> 1)) * 2 * W + 2 * px + (t & 1)) * GP + o);
+            }
         }
-        if constexpr (MODE == 0) {                             // four loads: eight lanes read the 128 contiguous bytes of one cell's 64 channels
+        if constexpr (MODE != 1) {                             // four loads: eight lanes read the 128 contiguous bytes of one cell's 64 channels
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const long cell = k0 + 8 * i + (lane >> 3);
@@ -185,8 +220,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_l
 
     if (k_begin < k_end) load_step(k_begin);
     for (long k0 = k_begin; k0 < k_end; k0 += WG_CELLS) {
-        *(bf16x8*)(img_g + wr) = gv;
-        if constexpr (MODE == 0) {
+#pragma unroll
+        for (int t = 0; t < GI; ++t) *(bf16x8*)(img_g + t * WG_IMAGE + wr) = gv[t];
+        if constexpr (MODE != 1) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) *(bf16x8*)(img_x + ((lane & 7) >> 1) * WG_IMAGE + image_off(8 * i + (lane >> 3)) + 16 * (lane & 1)) = xv[i];
         } else {
@@ -195,13 +231,28 @@ __global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_l
         }
         wave_sync();
         if (k0 + WG_CELLS < k_end) load_step(k0 + WG_CELLS);  // wave-uniform; the next step's rows are in flight under this step's reads and MFMAs
-        const bf16x8 af = image_frag(img_g, rd);
+        if constexpr (MODE != 2) {
+            const bf16x8 af = image_frag(img_g, rd);
 #pragma unroll
-        for (int t = 0; t < TAPS * CT; ++t) {
-            const bf16x8 bf = image_frag(img_x + t * WG_IMAGE, rd);
-            if constexpr (MODE == 0) mma(acc[0][t], af, bf); else mma(acc[t][0], af, bf);
+            for (int t = 0; t < TAPS * CT; ++t) {
+                const bf16x8 bf = image_frag(img_x + t * WG_IMAGE, rd);
+                if constexpr (MODE == 0) mma(acc[0][t], af, bf); else mma(acc[t][0], af, bf);
+            }
+            if (bias_wave) mma(accb, af, ones);                // wave-uniform
+        } else {
+            bf16x8 af[TAPS];
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) af[t] = image_frag(img_g + t * WG_IMAGE, rd);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const bf16x8 bf = image_frag(img_x + ct * WG_IMAGE, rd);
+#pragma unroll
+                for (int t = 0; t < TAPS; ++t) mma(acc[t][ct], af[t], bf);
+            }
+            if (bias_wave)                                     // wave-uniform; the taps ascending
+#pragma unroll
+                for (int t = 0; t < TAPS; ++t) mma(accb, af[t], ones);
         }
-        if (bias_wave) mma(accb, af, ones);                    // wave-uniform
         wave_sync();
     }
 
@@ -221,6 +272,97 @@ __global__ __launch_bounds__(HEAD_THREADS) void wgrad16_kernel(const cosy_head_l
         for (int q = 0; q < 4; ++q) out[O16 * TAPS * C + ot * 16 + 4 * kq + q] = accb[q];
 }
 
+// the weight gradient of M cells (the k dimension) of a.c_in -> a.c_out on bfloat16 rows, after the caller's own argument checks: kernels_detbwd.hip's
+// plan (slabs, workspace, M == 0) with wgrad16_kernel; outputs [0, n_split) to dw0 / db0 (db0 null: none), the rest to dw1 / db1
+int run_wgrad16(const char* fn, const cosy_head_layer_t& a, int stride, long M, int GP, const bf16_t* g, const float* scale, int n_split, float* dw0, float* db0,
+                float* dw1, float* db1, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const int T = a.ksize == 3 ? 9 : a.ksize == 2 ? 4 : 1;
+    if (M == 0) {
+        const long nw0 = (long)n_split * T * a.c_in, nw1 = (long)(a.c_out - n_split) * T * a.c_in;
+        COSY_CHECK_HIP(hipMemsetAsync(dw0, 0, nw0 * sizeof(float), s));
+        if (db0 != nullptr) COSY_CHECK_HIP(hipMemsetAsync(db0, 0, (size_t)n_split * sizeof(float), s));
+        if (nw1) {
+            COSY_CHECK_HIP(hipMemsetAsync(dw1, 0, nw1 * sizeof(float), s));
+            COSY_CHECK_HIP(hipMemsetAsync(db1, 0, (size_t)(a.c_out - n_split) * sizeof(float), s));
+        }
+        return COSY_OK;
+    }
+    COSY_REQUIRE(a.x != nullptr, "%s: null layer->x", fn);
+    COSY_REQUIRE(g != nullptr, "%s: null g", fn);
+    COSY_REQUIRE(workspace != nullptr, "%s: null workspace", fn);
+    COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)g & 15) == 0, "%s: the rows x and g must be 16-byte aligned", fn);
+    const int slab = wgrad_slab_rows_of((int)M), nslab = cdiv(M, slab);
+    const long slab_floats = wgrad_slab_floats_of(a.ksize, a.c_in, a.c_out);
+    const size_t need = (size_t)nslab * (size_t)slab_floats * sizeof(float);
+    COSY_REQUIRE(workspace_bytes >= need, "%s: workspace_bytes=%zu is less than the %zu bytes that %ld cells of c_in=%d, c_out=%d need "
+                 "(cosy_head_wgrad_workspace_bytes)", fn, workspace_bytes, need, M, a.c_in, a.c_out);
+    const int o_tiles = cdiv(a.c_out, 16), c_groups = cdiv(a.c_in, a.ksize == 3 ? 16 : 64);
+    const long n_waves = (long)o_tiles * c_groups;
+    COSY_REQUIRE(n_waves <= 0x7fffffffL, "%s: c_out=%d x c_in=%d need more than 2^31 - 1 waves", fn, a.c_out, a.c_in);
+    const dim3 grid((unsigned)cdiv(n_waves, HEAD_THREADS / 64), (unsigned)nslab), block(HEAD_THREADS);
+    float* partial = (float*)workspace;
+    const int want_db = db0 != nullptr;
+#define COSY_WGRAD16_LAUNCH(MODE, STRIDE) \
+    hipLaunchKernelGGL((wgrad16_kernel<MODE, STRIDE>), grid, block, 0, s, a, g, GP, (int)M, slab, (int)n_waves, c_groups, want_db, partial, slab_floats)
+    if (a.ksize == 2) COSY_WGRAD16_LAUNCH(2, 1);
+    else if (a.ksize == 1 && stride == 1) COSY_WGRAD16_LAUNCH(0, 1);
+    else if (a.ksize == 1) COSY_WGRAD16_LAUNCH(0, 2);
+    else if (stride == 1) COSY_WGRAD16_LAUNCH(1, 1);
+    else COSY_WGRAD16_LAUNCH(1, 2);
+#undef COSY_WGRAD16_LAUNCH
+    COSY_CHECK_HIP(hipGetLastError());
+    return wgrad_combine_split(partial, nslab, slab_floats, a.ksize, a.c_in, a.c_out, n_split, scale, dw0, db0, dw1, db1, s);
+}
+
+// the one pack launch, after the caller's own argument checks: n0 (+ n1 sibling) outputs of c_in channels
+int run_weight_pack16(const char* fn, const float* w0, const float* b0, const float* w1, const float* b1, const float* scale, int ksize, int c_in, int n0, int n1,
+                      void* fwd, float* fwd_bias, void* bwd, hipStream_t s) {
+    COSY_REQUIRE(((uintptr_t)w0 & 3) == 0 && ((uintptr_t)b0 & 3) == 0 && ((uintptr_t)w1 & 3) == 0 && ((uintptr_t)b1 & 3) == 0 && ((uintptr_t)scale & 3) == 0 &&
+                 ((uintptr_t)fwd & 15) == 0 && ((uintptr_t)bwd & 15) == 0 && ((uintptr_t)fwd_bias & 3) == 0,
+                 "%s: the parameters, scale and fwd_bias must be 4-byte, fwd and bwd 16-byte aligned", fn);
+    const long O = (long)n0 + n1, Nf = ksize == 2 ? 4 * O : O, Tf = ksize == 3 ? 9 : 1, Tb = ksize == 3 ? 9 : ksize == 2 ? 4 : 1;
+    const long NPf = (Nf + 63) / 64 * 64, NPb = ((long)c_in + 63) / 64 * 64;
+    const long n_fwd = NPf * Tf * ((c_in + 31) / 32 * 32), n_bwd = NPb * Tb * ((O + 31) / 32 * 32);
+    const long total = n_fwd + n_bwd + NPf;
+    COSY_REQUIRE(total <= (1L << 36), "%s: %ld packed elements exceed 2^36", fn, total);
+    hipLaunchKernelGGL(weight_pack16_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, w0, b0, w1, b1, scale, ksize, c_in, n0, n1, (bf16_t*)fwd,
+                       fwd_bias, (bf16_t*)bwd, n_fwd, n_bwd, (int)NPf);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+int run_grad_pack16(const char* fn, const float* g0, const float* g1, void* rows, int B, int n0, int n1, int GP, int HW, hipStream_t s) {
+    COSY_REQUIRE((long)B * HW <= HEAD_MAX_ROWS, "%s: B HW = %ld rows exceed 2^30", fn, (long)B * HW);
+    if (B == 0) return COSY_OK;
+    COSY_REQUIRE(rows != nullptr, "%s: null rows", fn);
+    COSY_REQUIRE(((uintptr_t)rows & 15) == 0 && ((uintptr_t)g0 & 3) == 0 && ((uintptr_t)g1 & 3) == 0, "%s: rows must be 16-byte, g 4-byte aligned", fn);
+    const long total = (long)B * HW * (GP / 8);
+    COSY_REQUIRE(cdiv(total, HEAD_THREADS) <= 0x7fffffffL && total <= (1L << 35), "%s: %ld elements exceed 2^38", fn, total * 8);
+    hipLaunchKernelGGL(grad_pack16_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, g0, g1, (bf16_t*)rows, n0, n1, GP, HW, total);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+// ConvTranspose2d(2, 2): M rows of the (H / 2, W / 2) maps, the four taps of the forward GEMM (kernels_detbwd.hip's launch_deconv_dgrad on bfloat16 rows)
+int launch_deconv_dgrad16(const cosy_head_layer_t& a, int M, const bf16_t* y, hipStream_t s) {
+    typedef DeconvGradPolicyOf<bf16_t> P;
+    const conv_grid_t c = conv_grid<bf16_t>(a, M);
+    COSY_REQUIRE(c.blocks <= 0x7fffffffL, "cosy_head_dgrad16: %d rows x c_out=%d need more than 2^31 - 1 workgroups", M, a.c_out);
+    const dim3 grid((unsigned)c.blocks), block(HEAD_THREADS);
+    const grad_epi_of<bf16_t> e{y};
+    if (c.big_m && c.big_n) hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, TILE_MT_BIG, TILE_NT_BIG, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_m) hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, TILE_MT_BIG, 1, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_n) hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, 1, TILE_NT_BIG, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, 1, 1, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
+
+inline int pad8(int n) { return (n + 7) / 8 * 8; }
+
+#define COSY_REQUIRE_BF16(fn, dtype, other) \
+    COSY_REQUIRE((dtype) == COSY_BF16, fn ": dtype=%d is not COSY_BF16 (float32 rows: " other "; float16 training needs a loss scaler, which is not built)", (dtype))
+
 }  // namespace
 }  // namespace cosy
 
@@ -235,31 +377,83 @@ int cosy_trunk_weight_pack16(const float* w, const float* scale, const float* sh
     COSY_REQUIRE(c_out >= 8 && c_out % 8 == 0 && c_out <= (1 << 22), "cosy_trunk_weight_pack16: c_out=%d must be a positive multiple of 8", c_out);
     COSY_REQUIRE_PTR("cosy_trunk_weight_pack16", w); COSY_REQUIRE_PTR("cosy_trunk_weight_pack16", shift);
     COSY_REQUIRE_PTR("cosy_trunk_weight_pack16", fwd); COSY_REQUIRE_PTR("cosy_trunk_weight_pack16", fwd_bias); COSY_REQUIRE_PTR("cosy_trunk_weight_pack16", bwd);
-    COSY_REQUIRE(((uintptr_t)w & 3) == 0 && ((uintptr_t)scale & 3) == 0 && ((uintptr_t)shift & 3) == 0 && ((uintptr_t)fwd & 15) == 0 && ((uintptr_t)bwd & 15) == 0 &&
-                 ((uintptr_t)fwd_bias & 3) == 0, "cosy_trunk_weight_pack16: w, scale, shift and fwd_bias must be 4-byte, fwd and bwd 16-byte aligned");
-    const long taps = ksize == 3 ? 9 : 1;
-    const long NPf = ((long)c_out + 63) / 64 * 64, NPb = ((long)c_in + 63) / 64 * 64;
-    const long n_fwd = NPf * taps * ((c_in + 31) / 32 * 32), n_bwd = NPb * taps * ((c_out + 31) / 32 * 32);
-    const long total = n_fwd + n_bwd + NPf;
-    COSY_REQUIRE(total <= (1L << 36), "cosy_trunk_weight_pack16: %ld packed elements exceed 2^36", total);
-    hipLaunchKernelGGL(weight_pack16_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, (hipStream_t)stream, w, scale, shift, (int)taps, c_in, c_out,
-                       (bf16_t*)fwd, fwd_bias, (bf16_t*)bwd, n_fwd, n_bwd, (int)NPf);
-    COSY_CHECK_HIP(hipGetLastError());
-    return COSY_OK;
+    return run_weight_pack16("cosy_trunk_weight_pack16", w, shift, nullptr, nullptr, scale, ksize, c_in, c_out, 0, fwd, fwd_bias, bwd, (hipStream_t)stream);
 }
 
 int cosy_trunk_grad_pack16(const float* g, void* rows, int B, int C, int HW, cosy_stream_t stream) {
     COSY_REQUIRE(B >= 0 && HW >= 1, "cosy_trunk_grad_pack16: B=%d must be >= 0 and HW=%d >= 1", B, HW);
     COSY_REQUIRE(C >= 8 && C % 8 == 0 && C <= (1 << 20), "cosy_trunk_grad_pack16: C=%d must be a positive multiple of 8", C);
-    COSY_REQUIRE((long)B * HW <= HEAD_MAX_ROWS, "cosy_trunk_grad_pack16: B HW = %ld rows exceed 2^30", (long)B * HW);
-    if (B == 0) return COSY_OK;
-    COSY_REQUIRE_PTR("cosy_trunk_grad_pack16", rows);
-    COSY_REQUIRE(((uintptr_t)rows & 15) == 0 && ((uintptr_t)g & 3) == 0, "cosy_trunk_grad_pack16: rows must be 16-byte, g 4-byte aligned");
-    const long total = (long)B * HW * (C / 8);
-    COSY_REQUIRE(cdiv(total, HEAD_THREADS) <= 0x7fffffffL && total <= (1L << 38), "cosy_trunk_grad_pack16: %ld elements exceed 2^38", total * 8);
-    hipLaunchKernelGGL(grad_pack16_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, (hipStream_t)stream, g, (bf16_t*)rows, C, HW, total);
-    COSY_CHECK_HIP(hipGetLastError());
-    return COSY_OK;
+    return run_grad_pack16("cosy_trunk_grad_pack16", g, nullptr, rows, B, C, 0, C, HW, (hipStream_t)stream);
+}
+
+int cosy_head_weight_pack16(const float* w0, const float* b0, const float* w1, const float* b1, int ksize, int c_in, int n0, int n1, void* fwd, float* fwd_bias,
+                            void* bwd, cosy_stream_t stream) {
+    COSY_REQUIRE(ksize == 1 || ksize == 2 || ksize == 3, "cosy_head_weight_pack16: ksize=%d must be 1, 3 or 2 (ConvTranspose2d(2, 2))", ksize);
+    COSY_REQUIRE(c_in >= 8 && c_in % 8 == 0 && c_in <= (1 << 24), "cosy_head_weight_pack16: the reduction length c_in=%d must be a positive multiple of 8", c_in);
+    COSY_REQUIRE(n0 >= 1 && n1 >= 0 && (long)n0 + n1 <= (1 << 22), "cosy_head_weight_pack16: n0=%d must be >= 1 and n1=%d >= 0", n0, n1);
+    COSY_REQUIRE(ksize != 2 || (n1 == 0 && n0 % 8 == 0), "cosy_head_weight_pack16: a deconvolution has no sibling and n0=%d a multiple of 8", n0);
+    COSY_REQUIRE_PTR("cosy_head_weight_pack16", w0); COSY_REQUIRE_PTR("cosy_head_weight_pack16", b0);
+    COSY_REQUIRE_PTR("cosy_head_weight_pack16", fwd); COSY_REQUIRE_PTR("cosy_head_weight_pack16", fwd_bias); COSY_REQUIRE_PTR("cosy_head_weight_pack16", bwd);
+    COSY_REQUIRE(n1 == 0 || (w1 != nullptr && b1 != nullptr), "cosy_head_weight_pack16: null w1 or b1 with n1=%d", n1);
+    return run_weight_pack16("cosy_head_weight_pack16", w0, b0, w1, b1, nullptr, ksize, c_in, n0, n1, fwd, fwd_bias, bwd, (hipStream_t)stream);
+}
+
+int cosy_head_grad_pack16(const float* g0, const float* g1, void* rows, int B, int n0, int n1, int HW, cosy_stream_t stream) {
+    COSY_REQUIRE(B >= 0 && HW >= 1, "cosy_head_grad_pack16: B=%d must be >= 0 and HW=%d >= 1", B, HW);
+    COSY_REQUIRE(n0 >= 0 && n1 >= 0 && n0 + n1 >= 1 && n0 + n1 <= (1 << 20), "cosy_head_grad_pack16: n0=%d and n1=%d must be >= 0 and hold 1 to 2^20 columns", n0, n1);
+    return run_grad_pack16("cosy_head_grad_pack16", g0, g1, rows, B, n0, n1, pad8(n0 + n1), HW, (hipStream_t)stream);
+}
+
+int cosy_head_dgrad16(const cosy_head_layer_t* layer, const void* y, cosy_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    COSY_REQUIRE_PTR("cosy_head_dgrad16", layer);
+    const cosy_head_layer_t& a = *layer;
+    COSY_REQUIRE_BF16("cosy_head_dgrad16", a.dtype, "cosy_head_dgrad");
+    COSY_REQUIRE(a.ksize == 1 || a.ksize == 2 || a.ksize == 3, "cosy_head_dgrad16: ksize=%d must be 1, 3 or 2 (ConvTranspose2d(2, 2))", a.ksize);
+    COSY_REQUIRE(a.c_in >= 8 && a.c_in % 8 == 0, "cosy_head_dgrad16: the reduction length c_in=%d must be a positive multiple of 8", a.c_in);
+    COSY_REQUIRE(a.c_out >= 8 && a.c_out % 8 == 0, "cosy_head_dgrad16: c_out=%d (the layer's input channels) must be a positive multiple of 8", a.c_out);
+    COSY_REQUIRE(a.store == COSY_HEAD_STORE_ROWS || a.store == COSY_HEAD_STORE_NCHW, "cosy_head_dgrad16: store=%d is not COSY_HEAD_STORE_ROWS or COSY_HEAD_STORE_NCHW", a.store);
+    COSY_REQUIRE(a.relu == 0, "cosy_head_dgrad16: relu=%d must be 0 (the mask is given by y)", a.relu);
+    COSY_REQUIRE(a.store != COSY_HEAD_STORE_NCHW || (a.n_split == a.c_out && y == nullptr), "cosy_head_dgrad16: an NCHW store takes n_split == c_out=%d and no y", a.c_out);
+    const long rows_in = check_levels("cosy_head_dgrad16", a);
+    if (rows_in < 0) return COSY_EINVAL;
+    long M = rows_in;
+    if (a.ksize == 2) {
+        COSY_REQUIRE(a.n_levels == 1 && a.H[0] % 2 == 0 && a.W[0] % 2 == 0, "cosy_head_dgrad16: ksize 2 takes one level of even maps, got %d levels of %d x %d",
+                     a.n_levels, a.H[0], a.W[0]);
+        M = rows_in / 4;
+    }
+    if (M == 0) return COSY_OK;
+    COSY_REQUIRE_PTR("cosy_head_dgrad16", a.x); COSY_REQUIRE_PTR("cosy_head_dgrad16", a.w); COSY_REQUIRE_PTR("cosy_head_dgrad16", a.out);
+    COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)y & 15) == 0,
+                 "cosy_head_dgrad16: x, w, out and y must be 16-byte aligned");
+    if (a.ksize == 2) return launch_deconv_dgrad16(a, (int)M, (const bf16_t*)y, s);
+    const tadd_t<bf16_t> none{nullptr, ADD_NONE, 1, 1, 1.f, 1.f};
+    return launch_dgrad_rows<bf16_t, 1>("cosy_head_dgrad16", a, (int)M, tgrad_epi_t<bf16_t>{(const bf16_t*)y, {none, none}, 0, 0}, s);
+}
+
+int cosy_head_wgrad16(const cosy_head_layer_t* layer, const void* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes,
+                      cosy_stream_t stream) {
+    COSY_REQUIRE_PTR("cosy_head_wgrad16", layer);
+    const cosy_head_layer_t& a = *layer;
+    COSY_REQUIRE_BF16("cosy_head_wgrad16", a.dtype, "cosy_head_wgrad");
+    COSY_REQUIRE(a.ksize == 1 || a.ksize == 2 || a.ksize == 3, "cosy_head_wgrad16: ksize=%d must be 1, 3 or 2 (ConvTranspose2d(2, 2))", a.ksize);
+    COSY_REQUIRE(a.c_in >= 8 && a.c_in % 8 == 0, "cosy_head_wgrad16: c_in=%d must be a positive multiple of 8", a.c_in);
+    COSY_REQUIRE(a.c_out >= 1 && a.c_out <= (1 << 22), "cosy_head_wgrad16: c_out=%d must lie in [1, 2^22]", a.c_out);
+    COSY_REQUIRE(a.n_split >= 1 && a.n_split <= a.c_out, "cosy_head_wgrad16: n_split=%d must lie in [1, c_out=%d]", a.n_split, a.c_out);
+    COSY_REQUIRE(a.ksize != 2 || (a.n_levels == 1 && a.n_split == a.c_out && a.c_out % 8 == 0),
+                 "cosy_head_wgrad16: ksize 2 takes one level, no sibling and c_out=%d a multiple of 8", a.c_out);
+    const long M = check_levels("cosy_head_wgrad16", a);
+    if (M < 0) return COSY_EINVAL;
+    COSY_REQUIRE(a.ksize != 2 || 4 * M <= HEAD_MAX_ROWS, "cosy_head_wgrad16: 4 x %ld gradient rows exceed 2^30", M);
+    COSY_REQUIRE_PTR("cosy_head_wgrad16", dw0); COSY_REQUIRE_PTR("cosy_head_wgrad16", db0);
+    COSY_REQUIRE(a.n_split == a.c_out || (dw1 != nullptr && db1 != nullptr), "cosy_head_wgrad16: null dw1 or db1 with n_split=%d < c_out=%d", a.n_split, a.c_out);
+    COSY_REQUIRE(((uintptr_t)dw0 & 3) == 0 && ((uintptr_t)db0 & 3) == 0 && ((uintptr_t)dw1 & 3) == 0 && ((uintptr_t)db1 & 3) == 0 && ((uintptr_t)workspace & 3) == 0,
+                 "cosy_head_wgrad16: dw0, db0, dw1, db1 and workspace must be 4-byte aligned");
+    const int T = a.ksize == 3 ? 9 : a.ksize == 2 ? 4 : 1;
+    COSY_REQUIRE((long)a.c_out * T * a.c_in + a.c_out <= (1L << 36), "cosy_head_wgrad16: c_out=%d x c_in=%d weights exceed 2^36", a.c_out, a.c_in);
+    return run_wgrad16("cosy_head_wgrad16", a, 1, M, pad8(a.c_out), (const bf16_t*)g, nullptr, a.n_split, dw0, db0, dw1, db1, workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 int cosy_trunk_dgrad16(const cosy_head_layer_t* layer, int stride, const void* add0, int rule0, int add0_H, int add0_W, const void* add1, int rule1, int add1_H,
@@ -290,37 +484,8 @@ int cosy_trunk_wgrad16(const cosy_head_layer_t* layer, int stride, const void* g
     COSY_REQUIRE_PTR("cosy_trunk_wgrad16", dw);
     COSY_REQUIRE(((uintptr_t)dw & 3) == 0 && ((uintptr_t)db & 3) == 0 && ((uintptr_t)scale & 3) == 0 && ((uintptr_t)workspace & 3) == 0,
                  "cosy_trunk_wgrad16: scale, dw, db and workspace must be 4-byte aligned");
-    const int T = a.ksize == 3 ? 9 : 1;
-    COSY_REQUIRE((long)a.c_out * T * a.c_in <= (1L << 36), "cosy_trunk_wgrad16: c_out=%d x c_in=%d weights exceed 2^36", a.c_out, a.c_in);
-    if (M == 0) {
-        COSY_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)a.c_out * T * a.c_in * sizeof(float), s));
-        if (db != nullptr) COSY_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)a.c_out * sizeof(float), s));
-        return COSY_OK;
-    }
-    COSY_REQUIRE(a.x != nullptr, "cosy_trunk_wgrad16: null layer->x");
-    COSY_REQUIRE_PTR("cosy_trunk_wgrad16", g);
-    COSY_REQUIRE_PTR("cosy_trunk_wgrad16", workspace);
-    COSY_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)g & 15) == 0, "cosy_trunk_wgrad16: the rows x and g must be 16-byte aligned");
-    const int slab = wgrad_slab_rows_of((int)M), nslab = cdiv(M, slab);
-    const long slab_floats = wgrad_slab_floats_of(a.ksize, a.c_in, a.c_out);
-    const size_t need = (size_t)nslab * (size_t)slab_floats * sizeof(float);
-    COSY_REQUIRE(workspace_bytes >= need, "cosy_trunk_wgrad16: workspace_bytes=%zu is less than the %zu bytes that %ld cells of c_in=%d, c_out=%d need "
-                 "(cosy_head_wgrad_workspace_bytes)", workspace_bytes, need, M, a.c_in, a.c_out);
-    const int o_tiles = cdiv(a.c_out, 16), c_groups = cdiv(a.c_in, a.ksize == 1 ? 64 : 16);
-    const long n_waves = (long)o_tiles * c_groups;
-    COSY_REQUIRE(n_waves <= 0x7fffffffL, "cosy_trunk_wgrad16: c_out=%d x c_in=%d need more than 2^31 - 1 waves", a.c_out, a.c_in);
-    const dim3 grid((unsigned)cdiv(n_waves, HEAD_THREADS / 64), (unsigned)nslab), block(HEAD_THREADS);
-    float* partial = (float*)workspace;
-    const int want_db = db != nullptr;
-#define COSY_WGRAD16_LAUNCH(MODE, STRIDE) \
-    hipLaunchKernelGGL((wgrad16_kernel<MODE, STRIDE>), grid, block, 0, s, a, (const bf16_t*)g, (int)M, slab, (int)n_waves, c_groups, want_db, partial, slab_floats)
-    if (a.ksize == 1 && stride == 1) COSY_WGRAD16_LAUNCH(0, 1);
-    else if (a.ksize == 1) COSY_WGRAD16_LAUNCH(0, 2);
-    else if (stride == 1) COSY_WGRAD16_LAUNCH(1, 1);
-    else COSY_WGRAD16_LAUNCH(1, 2);
-#undef COSY_WGRAD16_LAUNCH
-    COSY_CHECK_HIP(hipGetLastError());
-    return wgrad_combine(partial, nslab, slab_floats, a.ksize, a.c_in, a.c_out, scale, dw, db, s);
+    COSY_REQUIRE((long)a.c_out * (a.ksize == 3 ? 9 : 1) * a.c_in <= (1L << 36), "cosy_trunk_wgrad16: c_out=%d x c_in=%d weights exceed 2^36", a.c_out, a.c_in);
+    return run_wgrad16("cosy_trunk_wgrad16", a, stride, M, a.c_out, (const bf16_t*)g, scale, a.c_out, dw, db, nullptr, nullptr, workspace, workspace_bytes, s);
 }
 
 }  // extern "C"

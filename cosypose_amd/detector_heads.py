@@ -1,7 +1,8 @@
 """The detector's heads on the matrix pipe: Mask R-CNN's RPN head, box head + predictor and mask head + predictor (torchvision 0.4.2), the
 convolutions and linears between the FPN and detector.detections_from_heads.  By default inference only (HIP: csrc/kernels_dethead.hip, cosy_head_pack and
 cosy_head_conv).  DetectorHeads(..., trainable=True) are float32 heads with parameters and a backward on the same matrix pipe, behind autograd
-(HIP: csrc/kernels_detbwd.hip, which the trunk's backward, detector_trunk_backward.py (section 29), runs too).
+(HIP: csrc/kernels_detbwd.hip, which the trunk's backward, detector_trunk_backward.py (section 29), runs too); with
+train_dtype=torch.bfloat16 their rows and packed weights are bfloat16 under the float32 parameters (section 32; csrc/kernels_detbwd16.hip).
 
 Every layer is one implicit GEMM over ROWS: a row is one cell (level, image, y, x) with its channels contiguous in the storage type (float32,
 float16 or bfloat16; a linear layer's row is its input vector).  The heads' inputs arrive as contiguous NCHW float32 (what the FPN and
@@ -152,16 +153,20 @@ class PackedOnDevice:
 
 
 class TrainableLayer(PackedOnDevice):
-    """A layer of trainable heads, float32: its parameters are torch.nn.Parameters on the device in torchvision's layout
+    """A layer of trainable heads: its parameters are float32 torch.nn.Parameters on the device in torchvision's layout
     (one (weight, bias) pair, or the two siblings of one GEMM); w / bias (what cosy_head_conv reads) and w_t (the transposed, tap-flipped
     packing the data gradient reads) are written by cosy_head_weight_pack on the device, when a parameter has moved since the last pack.
     kind, ksize, relu, c_in, c_out, n_out as HeadLayer; grad_ksize: 3, 1, or 2 for the deconvolution; n_grad: the outputs o of the gradient
-    rows (deconv: C_o, else c_out)."""
+    rows (deconv: C_o, else c_out).  dtype: the type of the rows and of w / w_t (the parameters are float32 whatever it is); torch.bfloat16
+    (section 32) packs through cosy_head_weight_pack16: w holds the bytes of the host packing of the weight rounded to bfloat16."""
     dtype, owner = torch.float32, 'heads'
 
-    def __init__(self, kind, pairs, relu, device, counter=None):
+    def __init__(self, kind, pairs, relu, device, counter=None, dtype=torch.float32):
         if device is None or torch.device(device).type != 'cuda':
             raise ValueError(f'trainable heads live on the ROCm device: give device=, got {device}')
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'the rows of trainable heads are float32 or bfloat16, got {dtype}')
+        self.dtype = dtype
         self.kind, self.relu, self.device = kind, bool(relu), torch.device(device)
         self.counter = counter if counter is not None else [0]
         self.pairs = []
@@ -201,9 +206,10 @@ class TrainableLayer(PackedOnDevice):
         C, O = self.c_in, self.n_grad
         taps, gtaps = (9 if self.ksize == 3 else 1), {1: 1, 3: 9, 2: 4}[self.grad_ksize]
         NP = -(-self.c_out // 64) * 64
-        self.w = torch.empty(NP * taps * (-(-C // 16) * 16), dtype=torch.float32, device=self.device)
+        KB = 16 if dtype == torch.float32 else 32
+        self.w = torch.empty(NP * taps * (-(-C // KB) * KB), dtype=dtype, device=self.device)
         self.bias = torch.empty(NP, dtype=torch.float32, device=self.device)
-        self.w_t = torch.empty((-(-C // 64) * 64) * gtaps * (-(-O // 16) * 16), dtype=torch.float32, device=self.device)
+        self.w_t = torch.empty((-(-C // 64) * 64) * gtaps * (-(-O // KB) * KB), dtype=dtype, device=self.device)
         self.versions = None
 
     def parameters(self):
@@ -212,24 +218,25 @@ class TrainableLayer(PackedOnDevice):
     def _pack(self):
         (w0, b0), (w1, b1) = self.pairs[0], (self.pairs[1] if len(self.pairs) == 2 else (None, None))
         n0 = int(w0.shape[1] if self.kind == 'deconv' else w0.shape[0])
-        _lib.check(_lib.lib().cosy_head_weight_pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0,
-                                                    _lib.ptr(self.w), _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
+        pack = _lib.lib().cosy_head_weight_pack if self.dtype == torch.float32 else _lib.lib().cosy_head_weight_pack16
+        _lib.check(pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0, _lib.ptr(self.w),
+                        _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
 
     @classmethod
-    def conv(cls, weight, bias=None, relu=False, device=None, counter=None):
-        return cls('conv', [(weight, bias)], relu, device, counter)
+    def conv(cls, weight, bias=None, relu=False, device=None, counter=None, dtype=torch.float32):
+        return cls('conv', [(weight, bias)], relu, device, counter, dtype)
 
     @classmethod
-    def linear(cls, weight, bias=None, relu=False, device=None, counter=None):
-        return cls('linear', [(weight, bias)], relu, device, counter)
+    def linear(cls, weight, bias=None, relu=False, device=None, counter=None, dtype=torch.float32):
+        return cls('linear', [(weight, bias)], relu, device, counter, dtype)
 
     @classmethod
-    def deconv(cls, weight, bias=None, relu=False, device=None, counter=None):
-        return cls('deconv', [(weight, bias)], relu, device, counter)
+    def deconv(cls, weight, bias=None, relu=False, device=None, counter=None, dtype=torch.float32):
+        return cls('deconv', [(weight, bias)], relu, device, counter, dtype)
 
     @classmethod
-    def siblings(cls, first, second, kind, device=None, counter=None):
-        return cls(kind, [tuple(first), tuple(second)], False, device, counter)
+    def siblings(cls, first, second, kind, device=None, counter=None, dtype=torch.float32):
+        return cls(kind, [tuple(first), tuple(second)], False, device, counter, dtype)
 
 
 # ---- launches ------------------------------------------------------------------------------------------------------------------------
@@ -330,31 +337,35 @@ def conv_layer(x, layer):
     return _gemm(layer, rows, [(B, H, W)], _lib.HEAD_STORE_NCHW, torch.empty((B, layer.c_out, H, W), dtype=torch.float32, device=dev))
 
 
-# ---- backward: float32 rows, the gradient g of a layer is taken at its PRE-activation output ---------------------
+# ---- backward (DESIGN.md sections 28 and 32): rows of the layer's dtype, the gradient g of a layer is taken at its PRE-activation output -----
 def wgrad_slab_rows(M):
     """cells of one slab of the weight gradient of M cells (the library's; tests sit on its edges)"""
     return int(_lib.lib().cosy_head_wgrad_slab_rows(int(M)))
 
 
 def _grad_pack(g0, g1, rows, B, n0, n1, HW):
-    """NCHW float32 gradients of a sibling pair (or of one tensor, n1 = 0; None: zeros) -> rows (B HW, pad8(n0 + n1)), one launch"""
+    """NCHW float32 gradients of a sibling pair (or of one tensor, n1 = 0; None: zeros) -> rows (B HW, pad8(n0 + n1)) of rows' own type
+    (float32, or bfloat16: rounded to nearest even), one launch"""
     for g, n in ((g0, n0), (g1, n1)):
         if g is not None and (g.dtype != torch.float32 or g.numel() != B * n * HW or not g.is_cuda):
             raise ValueError(f'a gradient of {B} x {n} x {HW} float32 values on the device was expected, got {tuple(g.shape)} {g.dtype} on {g.device}')
     if B:
-        _lib.check(_lib.lib().cosy_head_grad_pack(_lib.ptr(None if g0 is None else g0.contiguous()), _lib.ptr(None if g1 is None else g1.contiguous()),
-                                                  _lib.ptr(rows), B, n0, n1, HW, _lib.stream()))
+        pack = _lib.lib().cosy_head_grad_pack if rows.dtype == torch.float32 else _lib.lib().cosy_head_grad_pack16
+        _lib.check(pack(_lib.ptr(None if g0 is None else g0.contiguous()), _lib.ptr(None if g1 is None else g1.contiguous()), _lib.ptr(rows), B, n0, n1, HW,
+                        _lib.stream()))
     return rows
 
 
 def _dgrad(layer, g_rows, maps, store, out, y=None):
-    """the data gradient of layer from its gradient rows; maps: those of g_rows.  y: the stored rows of the layer below (the ReLU mask)"""
+    """the data gradient of layer from its gradient rows; maps: those of g_rows.  y: the stored rows of the layer below (the ReLU mask).
+    A row store writes rows of the layer's dtype, an NCHW store float32 whatever it is"""
     d = _lib.HeadLayer()
     d.x, d.w, d.out = _lib.ptr(g_rows), _lib.ptr(layer.w_t), _lib.ptr(out)
-    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[torch.float32], layer.grad_ksize, int(g_rows.shape[1]), layer.c_in, 0, store
+    d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[layer.dtype], layer.grad_ksize, int(g_rows.shape[1]), layer.c_in, 0, store
     d.n_split = layer.c_in
     if _describe(d, maps):
-        _lib.check(_lib.lib().cosy_head_dgrad(ctypes.byref(d), _lib.ptr(y), _lib.stream()))
+        dgrad = _lib.lib().cosy_head_dgrad if layer.dtype == torch.float32 else _lib.lib().cosy_head_dgrad16
+        _lib.check(dgrad(ctypes.byref(d), _lib.ptr(y), _lib.stream()))
     return out
 
 
@@ -370,10 +381,11 @@ def _wgrad(layer, x_rows, g_rows, maps):
     """-> [dW, db] per parameter pair of layer, float32 in the parameters' own layout; maps: those of x_rows"""
     d = _lib.HeadLayer()
     d.x = _lib.ptr(x_rows)
-    d.dtype, d.ksize, d.c_in, d.c_out = _DTYPES[torch.float32], layer.grad_ksize, layer.c_in, layer.n_grad
+    d.dtype, d.ksize, d.c_in, d.c_out = _DTYPES[layer.dtype], layer.grad_ksize, layer.c_in, layer.n_grad
     d.n_split = getattr(layer, 'n_split', layer.n_grad)
     out, ws, need = _wgrad_buffers(layer, _describe(d, maps), layer.grad_ksize, layer.n_grad)
-    _lib.check(_lib.lib().cosy_head_wgrad(ctypes.byref(d), _lib.ptr(g_rows), *[_lib.ptr(t) for t in (out + [None, None])[:4]], _lib.ptr(ws), need, _lib.stream()))
+    wgrad = _lib.lib().cosy_head_wgrad if layer.dtype == torch.float32 else _lib.lib().cosy_head_wgrad16
+    _lib.check(wgrad(ctypes.byref(d), _lib.ptr(g_rows), *[_lib.ptr(t) for t in (out + [None, None])[:4]], _lib.ptr(ws), need, _lib.stream()))
     return out
 
 
@@ -392,10 +404,11 @@ def layer_backward(layer, x, grad, need_dx=True):
     want = (B, layer.n_out) if linear else (B, layer.n_out, up * H, up * W)
     if not torch.is_tensor(grad) or tuple(grad.shape) != want or grad.dtype != torch.float32 or not grad.is_cuda:
         raise ValueError(f'grad must be a float32 tensor of shape {want} on the device')
-    rows = x if linear else torch.empty((B * H * W, C), dtype=torch.float32, device=dev)
-    if not linear:
-        _pack(x, rows, B, C, H * W, torch.float32)
-    g = _grad_pack(grad.detach(), None, torch.empty((B * up * H * up * W, _pad8(layer.n_out)), dtype=torch.float32, device=dev), B, layer.n_out, 0, up * H * up * W)
+    rows = x
+    if not linear or layer.dtype != torch.float32:
+        rows = _rows(B * H * W, C, layer, dev)
+        _pack(x, rows, B, C, H * W, layer.dtype)
+    g = _grad_pack(grad.detach(), None, _rows(B * up * H * up * W, _pad8(layer.n_out), layer, dev), B, layer.n_out, 0, up * H * up * W)
     grads = _wgrad(layer, rows, g, [(B, H, W)])
     dx = None
     if need_dx:
@@ -417,6 +430,12 @@ def _g(t):
     return None if t is None else t.contiguous()
 
 
+def _note(head, keep, **rows):
+    """head.keep_rows (the tests): the rows the forward kept and every gradient row buffer of this backward, under the names of its launches"""
+    if getattr(head, 'keep_rows', False):
+        head.last_rows = dict(keep, **rows)
+
+
 class _RpnFn(torch.autograd.Function):
     """rpn_head as one node: forward = RpnHead._forward's launches; backward = per level one gradient pack, then for the sibling 1x1 GEMM and
     the 3x3 conv the weight gradient and the data gradient (the first masked by the stored hidden rows, the second stored NCHW per level)"""
@@ -434,17 +453,18 @@ class _RpnFn(torch.autograd.Function):
         head, k, L = ctx.head, ctx.keep, ctx.L
         maps, starts, A = k['maps'], k['starts'], head.A
         M, dev = starts[-1], k['x'].device
-        g = torch.empty((M, _pad8(5 * A)), dtype=torch.float32, device=dev)
+        g = _rows(M, _pad8(5 * A), head.conv, dev)
         for l, (B, H, W) in enumerate(maps):
             _grad_pack(_g(grads[l]), _g(grads[L + l]), g[starts[l]:starts[l + 1]], B, A, 4 * A, H * W)
         d_pred = _wgrad(head.pred, k['hidden'], g, maps)
-        gh = _dgrad(head.pred, g, maps, _lib.HEAD_STORE_ROWS, torch.empty((M, head.conv.c_out), dtype=torch.float32, device=dev), y=k['hidden'])
+        gh = _dgrad(head.pred, g, maps, _lib.HEAD_STORE_ROWS, _rows(M, head.conv.c_out, head.conv, dev), y=k['hidden'])
         d_conv = _wgrad(head.conv, k['x'], gh, maps)
         dfeat = [None] * L
         if any(ctx.needs_input_grad[2:2 + L]):
             C = head.conv.c_in
             flat = _dgrad(head.conv, gh, maps, _lib.HEAD_STORE_NCHW, torch.empty(C * M, dtype=torch.float32, device=dev))
             dfeat = [flat[C * starts[l]:C * starts[l + 1]].view(B, C, H, W) if ctx.needs_input_grad[2 + l] else None for l, (B, H, W) in enumerate(maps)]
+        _note(head, k, g=g, gh=gh)
         return (None, None) + tuple(dfeat) + tuple(d_conv) + tuple(d_pred)
 
 
@@ -464,14 +484,17 @@ class _BoxFn(torch.autograd.Function):
         head, k = ctx.head, ctx.keep
         maps, K, x = k['maps'], head.K, k['x']
         R, dev = int(x.shape[0]), x.device
-        new = lambda n: torch.empty((R, n), dtype=torch.float32, device=dev)
+        new = lambda n: _rows(R, n, head.fc6, dev)
         g = _grad_pack(_g(g_logits), _g(g_boxes), new(_pad8(5 * K)), R, K, 4 * K, 1)
         d_pred = _wgrad(head.pred, k['h7'], g, maps)
         g7 = _dgrad(head.pred, g, maps, _lib.HEAD_STORE_ROWS, new(head.fc7.c_out), y=k['h7'])
         d_fc7 = _wgrad(head.fc7, k['h6'], g7, maps)
         g6 = _dgrad(head.fc7, g7, maps, _lib.HEAD_STORE_ROWS, new(head.fc6.c_out), y=k['h6'])
         d_fc6 = _wgrad(head.fc6, x, g6, maps)
-        dx = _dgrad(head.fc6, g6, maps, _lib.HEAD_STORE_NCHW, new(head.fc6.c_in)) if ctx.needs_input_grad[1] else None
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = _dgrad(head.fc6, g6, maps, _lib.HEAD_STORE_NCHW, torch.empty((R, head.fc6.c_in), dtype=torch.float32, device=dev))
+        _note(head, k, g=g, g7=g7, g6=g6)
         return (None, dx) + tuple(d_fc6) + tuple(d_fc7) + tuple(d_pred)
 
 
@@ -492,20 +515,22 @@ class _MaskFn(torch.autograd.Function):
         (D, H, W), = k['maps']
         maps, maps2, rows, up, dev = k['maps'], [(D, 2 * H, 2 * W)], k['rows'], k['up'], k['up'].device
         M, K = D * H * W, head.logits.c_out
-        new = lambda m, n: torch.empty((m, n), dtype=torch.float32, device=dev)
+        new = lambda m, n: _rows(m, n, head.deconv, dev)
         g = _grad_pack(_g(g_out), None, new(4 * M, _pad8(K)), D, K, 0, 4 * H * W)
         d_logits = _wgrad(head.logits, up, g, maps2)
         g_up = _dgrad(head.logits, g, maps2, _lib.HEAD_STORE_ROWS, new(4 * M, head.deconv.n_out), y=up)
         d_deconv = _wgrad(head.deconv, rows[-1], g_up, maps)
         g_cur = _dgrad(head.deconv, g_up, maps2, _lib.HEAD_STORE_ROWS, new(M, head.deconv.c_in), y=rows[-1])
-        d_convs, dx = [], None
+        d_convs, dx, g_convs = [], None, [g_cur]
         for i in range(len(head.convs) - 1, -1, -1):
             layer = head.convs[i]
             d_convs = _wgrad(layer, rows[i], g_cur, maps) + d_convs
             if i:
                 g_cur = _dgrad(layer, g_cur, maps, _lib.HEAD_STORE_ROWS, new(M, layer.c_in), y=rows[i])
+                g_convs.insert(0, g_cur)
             elif ctx.needs_input_grad[1]:
                 dx = _dgrad(layer, g_cur, maps, _lib.HEAD_STORE_NCHW, torch.empty(ctx.shape, dtype=torch.float32, device=dev))
+        _note(head, k, g=g, g_up=g_up, g_convs=g_convs)
         return (None, dx) + tuple(d_convs) + tuple(d_deconv) + tuple(d_logits)
 
 
@@ -652,14 +677,17 @@ class DetectorHeads:
     """The three heads as callables with the signatures detector_rpn.detections_from_features documents: .rpn_head, .box_head, .mask_head
     (None without a mask branch).  Weights are packed once, here."""
 
-    def __init__(self, params, dtype=torch.float32, device=None, trainable=False):
+    def __init__(self, params, dtype=torch.float32, device=None, trainable=False, train_dtype=None):
         """params: {key: (weight, bias)} under the names of a torchvision 0.4.2 Mask R-CNN state_dict, without the '.weight' / '.bias'.
-        trainable: the parameters become torch.nn.Parameters on the device and the three heads autograd nodes (float32 only; see _init_trainable)"""
+        trainable: the parameters become float32 torch.nn.Parameters on the device and the three heads autograd nodes (see _init_trainable);
+        train_dtype: the type of their rows and packed weights, None / torch.float32 (section 28) or torch.bfloat16 (section 32)"""
+        from .detector_trunk_backward import check_train_dtype
         dtype = _dtype(dtype)
         kw = dict(dtype=dtype, device=device)
         p = params
         self.dtype = dtype
         self.trainable = bool(trainable)
+        self.train_dtype = check_train_dtype(self.trainable, train_dtype, 'heads')
         if self.trainable:
             return self._init_trainable(p, dtype, device)
         self.rpn_head = RpnHead(HeadLayer.conv(*p[RPN_KEYS[0]], relu=True, **kw), HeadLayer.siblings(p[RPN_KEYS[1]], p[RPN_KEYS[2]], 'conv', **kw))
@@ -675,14 +703,15 @@ class DetectorHeads:
         named_parameters(), state_dict(), load_state_dict(): a checkpoint's head keys go in and out as they are; torch.optim works on them).
         Forward and backward read packings made on the device (cosy_head_weight_pack) when a parameter's _version has moved; pack_count counts
         those launches.  rpn_head / box_head / mask_head are one autograd node each when grad is enabled and an input or a parameter requires
-        grad, and exactly the inference path otherwise."""
+        grad, and exactly the inference path otherwise.  With train_dtype=torch.bfloat16 (section 32) the rows a node keeps, the gradient rows
+        and both packings are bfloat16 under the float32 parameters, the master weights; the forward is that of bfloat16 inference heads."""
         if dtype != torch.float32:
             raise ValueError(f'trainable heads are float32 only (16-bit training and master weights are not built), got dtype={dtype}')
         if device is None:
             w = p[RPN_KEYS[0]][0]
             device = w.device if torch.is_tensor(w) and w.is_cuda else None
         self._counter = [0]
-        kw = dict(device=device, counter=self._counter)
+        kw = dict(device=device, counter=self._counter, dtype=self.train_dtype)
         T = TrainableLayer
         self.rpn_head = RpnHead(T.conv(*p[RPN_KEYS[0]], relu=True, **kw), T.siblings(p[RPN_KEYS[1]], p[RPN_KEYS[2]], 'conv', **kw))
         self.box_head = BoxHead(T.linear(*p[BOX_KEYS[0]], relu=True, **kw), T.linear(*p[BOX_KEYS[1]], relu=True, **kw),
@@ -745,8 +774,9 @@ class DetectorHeads:
         return out
 
     @classmethod
-    def from_state_dict(cls, sd, dtype=torch.float32, device=None, trainable=False):
-        """a Mask R-CNN state_dict as it is: the trunk's and the FPN's keys are ignored, a missing head key is a KeyError naming it"""
+    def from_state_dict(cls, sd, dtype=torch.float32, device=None, trainable=False, train_dtype=None):
+        """a Mask R-CNN state_dict as it is: the trunk's and the FPN's keys are ignored, a missing head key is a KeyError naming it.
+        dtype stays the type of the parameters; train_dtype names the rows of trainable heads (see __init__)"""
         if trainable and dtype != torch.float32:
             raise ValueError(f'trainable heads are float32 only (16-bit training and master weights are not built), got dtype={dtype}')
         params = {}
@@ -755,10 +785,11 @@ class DetectorHeads:
                 if f'{k}.{part}' not in sd:
                     raise KeyError(f'{k}.{part}')
             params[k] = (sd[f'{k}.weight'], sd[f'{k}.bias'])
-        return cls(params, dtype, device, trainable)
+        return cls(params, dtype, device, trainable, train_dtype)
 
     @classmethod
-    def from_modules(cls, rpn_head, box_head, box_predictor, mask_head=None, mask_predictor=None, dtype=torch.float32, device=None, trainable=False):
+    def from_modules(cls, rpn_head, box_head, box_predictor, mask_head=None, mask_predictor=None, dtype=torch.float32, device=None, trainable=False,
+                     train_dtype=None):
         """the same from modules, duck-typed on torchvision's attribute names (conv, cls_logits, bbox_pred; fc6, fc7; cls_score, bbox_pred;
         mask_fcn1..4; conv5_mask, mask_fcn_logits)"""
         if (mask_head is None) != (mask_predictor is None):
@@ -778,4 +809,4 @@ class DetectorHeads:
             device = device if device.type != 'cpu' else None
         if trainable:           # parameters of the heads' own: a copy, never the modules' tensors
             params = {k: tuple(None if t is None else t.detach().clone() for t in pair) for k, pair in params.items()}
-        return cls(params, dtype, device, trainable)
+        return cls(params, dtype, device, trainable, train_dtype)

@@ -495,18 +495,21 @@ class Detector:
 
     @classmethod
     def from_state_dict(cls, sd, label_to_category_id, input_resize=(480, 640), dtype=torch.float32, device='cuda', trainable=False, train_from_stage=2,
-                        train_dtype=None):
+                        train_dtype=None, heads_train_dtype=None):
         """a reference detector checkpoint's state_dict as it is (backbone.*, rpn.head.*, roi_heads.*).  trainable: the trainable trunk
          and the trainable heads (section 28), float32 parameters.  train_dtype=torch.bfloat16: the trunk runs section
-        30's bfloat16 rows; its maps are float32 NCHW, so the float32 trainable heads follow it unchanged"""
+        30's bfloat16 rows; its maps are float32 NCHW, so the float32 trainable heads follow it unchanged.  heads_train_dtype=torch.bfloat16:
+        the heads run section 32's bfloat16 rows (None: float32 rows); both together are the fully 16-bit training step"""
         from .detector_heads import DetectorHeads
         from .detector_trunk_backward import check_train_dtype
         check_train_dtype(trainable, train_dtype)
+        check_train_dtype(trainable, heads_train_dtype, 'heads')
         if trainable and dtype != torch.float32:
             raise ValueError(f'a trainable detector is float32 only (dtype is the type of the parameters; bfloat16 rows in the trunk are '
                              f'train_dtype=torch.bfloat16), got dtype={dtype}')
         trunk = DetectorTrunk.from_state_dict(sd, dtype, device, trainable=trainable, train_from_stage=train_from_stage, train_dtype=train_dtype)
-        return cls(trunk, DetectorHeads.from_state_dict(sd, dtype, device, trainable=trainable), label_to_category_id, input_resize)
+        heads = DetectorHeads.from_state_dict(sd, dtype, device, trainable=trainable, train_dtype=heads_train_dtype)
+        return cls(trunk, heads, label_to_category_id, input_resize)
 
     # ---- training (trainable=True): the reference's train_detector.py loop on this library's kernels ----
     @property

@@ -25,12 +25,12 @@ def _out(n, stride):
     return (n - 1) // stride + 1
 
 
-def check_train_dtype(trainable, train_dtype):
-    """the train_dtype= keyword of the trainable trunk and detector -> the type of the rows and of the packed weights (None: not trainable)"""
+def check_train_dtype(trainable, train_dtype, owner='trunk'):
+    """the train_dtype= keyword of the trainable trunk, heads and detector -> the type of the rows and of the packed weights (None: not trainable)"""
     if train_dtype is None:
         return F32 if trainable else None
     if not trainable:
-        raise ValueError(f'train_dtype={train_dtype} names the rows of a trainable trunk: give trainable=True with it')
+        raise ValueError(f'train_dtype={train_dtype} names the rows of a trainable {owner}: give trainable=True with it')
     if train_dtype == torch.float16:
         raise ValueError('train_dtype=torch.float16: float16 training needs a loss scaler, which is not built; use torch.bfloat16 or torch.float32')
     if train_dtype not in (F32, BF16):

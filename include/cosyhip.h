@@ -1161,6 +1161,30 @@ int cosy_trunk_dgrad16(const cosy_head_layer_t* layer, int stride, const void* a
 int cosy_trunk_wgrad16(const cosy_head_layer_t* layer, int stride, const void* g, const float* scale, float* dw, float* db, void* workspace,
                        size_t workspace_bytes, cosy_stream_t stream);
 
+/* ---- the backward of the detector's heads on bfloat16 rows, float32 master weights ----  DESIGN.md section 32 holds the contract.
+ * The parameters, their gradients and every accumulation are float32; the rows (x, g, y, dX between two layers) and both packed weights are
+ * bfloat16, every conversion rounds to nearest even.  Layers, maps, ksize (1, 3, or 2 for ConvTranspose2d(2, 2)), siblings and limits are those of
+ * cosy_head_grad_pack .. cosy_head_wgrad above; dtype is COSY_BF16 (COSY_F32: the entries above; COSY_F16 is refused: no loss scaler is built).
+ * cosy_head_weight_pack16: as cosy_head_weight_pack -> fwd, the bytes of the host packing of the weight rounded to bfloat16 in the 16-bit
+ *   fragment order cosy_head_conv reads at COSY_BF16 (siblings: w0 then w1; ksize 2: the 4 C_o outputs (o, dy, dx)), c_out rounded up to 64 x
+ *   taps x c_in rounded up to 32 elements; fwd_bias float32 as cosy_head_weight_pack's; bwd: bf16(w), rows c rounded up to 64, reduction o in
+ *   blocks of 32 rounded up with zeros, taps in reverse order (ksize 3) or (dy, dx) ascending (ksize 2).  One launch.
+ * cosy_head_grad_pack16: cosy_head_grad_pack with bfloat16 rows (B HW, GP): the columns of g0, then of g1, then +0.0; NULL is zeros.
+ * cosy_head_dgrad16: cosy_head_dgrad on bfloat16 rows g, y and bwd: accumulator +0.0 float32, blocks of 32 o ascending, the taps in the
+ *   packing's order inside a block, one v_mfma_f32_16x16x32_bf16 per (block, tap).  COSY_HEAD_STORE_ROWS: out bfloat16, t = y <= 0 ? +0.0 : acc
+ *   (y NULL: acc), then ONE conversion.  COSY_HEAD_STORE_NCHW (ksize 1 / 3, y NULL, n_split == c_out): out float32 NCHW per level, the
+ *   accumulator unrounded.
+ * cosy_head_wgrad16: cosy_head_wgrad with layer->x and g bfloat16 rows (g: GP columns); dw, db and the workspace float32.  The cells are the k
+ *   dimension of v_mfma_f32_16x16x32_bf16, 32 per instruction; ksize 2: the k dimension is the cells of x, the four taps read g at
+ *   (2y + dy, 2x + dx), db is the sum over the four.  Slabs, workspace and the ascending second pass are cosy_head_wgrad's.
+ * All: checked on the host before any launch (COSY_EINVAL, the message starts with the function's name).  No atomics: equal inputs give equal bits. */
+int cosy_head_weight_pack16(const float* w0, const float* b0, const float* w1, const float* b1, int ksize, int c_in, int n0, int n1, void* fwd,
+                            float* fwd_bias, void* bwd, cosy_stream_t stream);
+int cosy_head_grad_pack16(const float* g0, const float* g1, void* rows, int B, int n0, int n1, int HW, cosy_stream_t stream);
+int cosy_head_dgrad16(const cosy_head_layer_t* layer, const void* y, cosy_stream_t stream);
+int cosy_head_wgrad16(const cosy_head_layer_t* layer, const void* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace,
+                      size_t workspace_bytes, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
