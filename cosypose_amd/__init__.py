@@ -92,6 +92,12 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ('TrainableTrunkLayer', 'trunk_dgrad', 'trunk_wgrad', 'layer_dgrad', 'layer_wgrad'):
         from . import detector_trunk_backward
         return getattr(detector_trunk_backward, name)
+    if name in ('FlatSGD', 'PackTable'):
+        from . import detector_optim
+        return getattr(detector_optim, name)
+    if name in ('h_maskrcnn', 'train_detector_loop'):
+        from . import detector_training
+        return getattr(detector_training, name)
     if name in ('gt_info', 'annotate_gt'):
         from . import gt_annotations
         return getattr(gt_annotations, name)

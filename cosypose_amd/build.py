@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libcosyhip.so')
 HEADER = os.path.normpath(os.path.join(HERE, '..', 'include', 'cosyhip.h'))     # the C ABI's one declaration (_lib.py binds from it)
-SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_dethead.hip', 'kernels_dettrunk.hip', 'kernels_detbwd.hip', 'kernels_detbwd16.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
+SOURCES = ['kernels_geom.hip', 'kernels_dist.hip', 'kernels_eval.hip', 'kernels_bop.hip', 'kernels_gt.hip', 'kernels_models.hip', 'kernels_ba.hip', 'kernels_ransac.hip', 'kernels_raster.hip', 'kernels_scene.hip', 'kernels_aug.hip', 'kernels_resize.hip', 'kernels_frames.hip', 'kernels_detin.hip', 'kernels_det.hip', 'kernels_detpost.hip', 'kernels_detpre.hip', 'kernels_dettrain.hip', 'kernels_dethead.hip', 'kernels_dettrunk.hip', 'kernels_detbwd.hip', 'kernels_detbwd16.hip', 'kernels_detopt.hip', 'kernels_train.hip', 'kernels_net.hip', 'kernels_small.hip',
            'kernels_dw.hip', 'kernels_wave.hip', 'kernels_stem.hip', 'kernels_smx.hip', 'effnet.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # No packed-fp32 arithmetic (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) anywhere in the library.  Round 4: a wave's packed-fp32 results were WRONG while
@@ -36,11 +36,13 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-u
 # kernels_detpost.hip: the same for the decode, the IoU of NMS (csrc/det_device.h is compiled by both) and the mask paste: DESIGN section 21 counts roundings.
 # kernels_detpre.hip: the same for the RPN's decode and for the taps and sums of the multi-scale RoIAlign, which hold the CPU twin's bits: DESIGN section 22.
 # kernels_dettrain.hip: the same for the matcher's IoU, the encode, the loss terms and the mask targets, which hold the CPU twin's bits: DESIGN section 23.
+# kernels_detopt.hip: the same for the SGD step, whose every product and sum is rounded on its own: DESIGN section 33 (the pack table's one product is
+# a single operation under either setting).
 # kernels_resize.hip: the same for its HOST routine, which computes Pillow's resampling coefficients in double (its kernels are integer only).
 # kernels_frames.hip: its kernel writes the fused operations of DESIGN section 18 as fmaf and must round every other product on its own.
 # kernels_detin.hip: the same for the fused operations of DESIGN section 25 and the one product of a box coordinate (csrc/image_device.h,
 # which states those operations once, is compiled by both).
-FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['-ffp-contract=off'], 'kernels_frames.hip': ['-ffp-contract=off'], 'kernels_detin.hip': ['-ffp-contract=off'], 'kernels_bop.hip': ['-ffp-contract=off'], 'kernels_gt.hip': ['-ffp-contract=off'], 'kernels_models.hip': ['-ffp-contract=off'], 'kernels_det.hip': ['-ffp-contract=off'], 'kernels_detpost.hip': ['-ffp-contract=off'], 'kernels_detpre.hip': ['-ffp-contract=off'], 'kernels_dettrain.hip': ['-ffp-contract=off'], 'kernels_wave.hip': ['-fno-slp-vectorize'], 'kernels_dw.hip': ['-fno-slp-vectorize'], 'kernels_stem.hip': ['-fno-slp-vectorize'], 'kernels_smx.hip': ['-fno-slp-vectorize']}   # kernels_dw.hip: see its header
+FILE_FLAGS = {'kernels_aug.hip': ['-ffp-contract=off'], 'kernels_resize.hip': ['-ffp-contract=off'], 'kernels_frames.hip': ['-ffp-contract=off'], 'kernels_detin.hip': ['-ffp-contract=off'], 'kernels_bop.hip': ['-ffp-contract=off'], 'kernels_gt.hip': ['-ffp-contract=off'], 'kernels_models.hip': ['-ffp-contract=off'], 'kernels_det.hip': ['-ffp-contract=off'], 'kernels_detpost.hip': ['-ffp-contract=off'], 'kernels_detpre.hip': ['-ffp-contract=off'], 'kernels_dettrain.hip': ['-ffp-contract=off'], 'kernels_detopt.hip': ['-ffp-contract=off'], 'kernels_wave.hip': ['-fno-slp-vectorize'], 'kernels_dw.hip': ['-fno-slp-vectorize'], 'kernels_stem.hip': ['-fno-slp-vectorize'], 'kernels_smx.hip': ['-fno-slp-vectorize']}   # kernels_dw.hip: see its header
 
 
 def _headers():

@@ -32,6 +32,58 @@ __device__ __forceinline__ float weight_at(const float* __restrict__ w0, const f
     return o < n0 ? w0[((long)o * C + c) * T + tap] : w1[((long)(o - n0) * C + c) * T + tap];
 }
 
+// The packing rules, stated once: cosy_head_weight_pack / cosy_trunk_weight_pack (T = float), their 16-bit forms (T = bf16_t) and the pack
+// table's one launch (kernels_detopt.hip) all run this function, one thread per element i of [fwd | bwd | fwd_bias].
+// Fragment order of cosy_head_conv, E = 16 / sizeof(T) elements per lane and KB = 4 E per block of the reduction: element [nt][tap][kb][lane][e]
+// holds W[16 nt + (lane & 15)][tap][KB kb + E (lane >> 4) + e].
+// forward: W = the layer's (rows o; ksize 2: rows (o, dy, dx), one tap), the host packing's bytes, and the bias or shift padded like it;
+// backward: W = ws = w scale[o] rounded once to float32 (scale null: w), rows c, reduction o, taps flipped (ksize 3) or (dy, dx) (ksize 2).
+// Siblings: w0 then w1; the trunk's layers are the case n1 = 0, b0 = shift.  The store converts ONCE to T (round to nearest even; float: none).
+template <typename T> struct pack_frag { static constexpr int E_LOG2 = sizeof(T) == 4 ? 2 : 3, E = 1 << E_LOG2, KB = 4 * E; };
+
+template <typename T>
+__device__ __forceinline__ void weight_pack_element(const long i, const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
+                                                    const float* __restrict__ b1, const float* __restrict__ scale, const int ksize, const int C, const int n0,
+                                                    const int n1, T* __restrict__ fwd, float* __restrict__ fwd_bias, T* __restrict__ bwd, const long n_fwd,
+                                                    const long n_bwd, const int n_bias) {
+    constexpr int E_LOG2 = pack_frag<T>::E_LOG2, E = pack_frag<T>::E, KB = pack_frag<T>::KB;
+    const int O = n0 + n1;
+    if (i < n_fwd + n_bwd) {
+        const bool back = i >= n_fwd;
+        const long k = back ? i - n_fwd : i;
+        const int taps = back ? (ksize == 3 ? 9 : ksize == 2 ? 4 : 1) : (ksize == 3 ? 9 : 1);
+        const int N = back ? C : (ksize == 2 ? 4 * O : O), K = back ? O : C;           // rows and reduction length of this packing
+        const int KBn = (K + KB - 1) / KB;
+        const int e = (int)(k & (E - 1)), lane = (int)((k >> E_LOG2) & 63);
+        const long s = k >> (E_LOG2 + 6);
+        const int kb = (int)(s % KBn), tap = (int)((s / KBn) % taps), nt = (int)(s / ((long)KBn * taps));
+        const int n = 16 * nt + (lane & 15), r = KB * kb + E * (lane >> 4) + e;
+        float v = 0.f;
+        if (n < N && r < K) {
+            if (!back) v = ksize == 2 ? weight_at(w0, w1, 2, C, n0, n1, n >> 2, n & 3, r) : weight_at(w0, w1, ksize, C, n0, n1, n, tap, r);
+            else {
+                v = weight_at(w0, w1, ksize, C, n0, n1, r, ksize == 3 ? 8 - tap : tap, n);
+                if (scale != nullptr) v = v * scale[r];
+            }
+        }
+        (back ? bwd : fwd)[k] = (T)v;
+    } else if (i < n_fwd + n_bwd + n_bias) {
+        const int n = (int)(i - n_fwd - n_bwd);
+        const int o = ksize == 2 ? n >> 2 : n;
+        float v = 0.f;
+        if (o < O) v = o < n0 ? b0[o] : b1[o - n0];
+        fwd_bias[n] = v;
+    }
+}
+
+// the elements of one layer's packings for a block of KB of the reduction (16: float32, 32: 16-bit): fwd, bwd, and the floats of fwd_bias
+struct pack_sizes_t { long n_fwd, n_bwd, n_bias; };
+inline pack_sizes_t pack_sizes(int ksize, int c_in, int n0, int n1, int KB) {
+    const long O = (long)n0 + n1, Nf = ksize == 2 ? 4 * O : O, Tf = ksize == 3 ? 9 : 1, Tb = ksize == 3 ? 9 : ksize == 2 ? 4 : 1;
+    const long NPf = (Nf + 63) / 64 * 64, NPb = ((long)c_in + 63) / 64 * 64;
+    return pack_sizes_t{NPf * Tf * (((long)c_in + KB - 1) / KB * KB), NPb * Tb * ((O + KB - 1) / KB * KB), NPf};
+}
+
 // ConvTranspose2d(2, 2)'s data gradient on rows of T: dethead_device.h's DeconvGradPolicy (conv_gemm_kernel's four stride-2 taps) with the mask
 // rows y in the rows' type
 template <typename T> struct grad_epi_of { const T* y; };

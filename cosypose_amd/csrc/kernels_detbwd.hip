@@ -51,41 +51,13 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_grad_pack_kernel(const floa
     rows[i] = v;
 }
 
-// fragment order of cosy_head_conv, float32: element [nt][tap][kb][lane][e] holds W[16 nt + (lane & 15)][tap][16 kb + 4 (lane >> 4) + e].
-// forward: W = the layer's (rows o; ksize 2: rows (o, dy, dx), one tap), the host packing's bytes, and the bias or shift padded like it;
-// backward: W = ws = w scale[o] rounded once (scale null: w), rows c, reduction o, taps flipped (ksize 3) or (dy, dx) (ksize 2).
+// cosy_head_weight_pack / cosy_trunk_weight_pack: one thread per element of [fwd | bwd | fwd_bias]; the rules are detbwd_device.h's weight_pack_element
+// (float32: 16 of the reduction per block, four elements per lane)
 __global__ __launch_bounds__(HEAD_THREADS) void weight_pack_kernel(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
                                                                    const float* __restrict__ b1, const float* __restrict__ scale, int ksize, int C, int n0, int n1,
                                                                    float* __restrict__ fwd, float* __restrict__ fwd_bias, float* __restrict__ bwd, long n_fwd,
                                                                    long n_bwd, int n_bias) {
-    const long i = (long)blockIdx.x * HEAD_THREADS + threadIdx.x;
-    const int O = n0 + n1;
-    if (i < n_fwd + n_bwd) {
-        const bool back = i >= n_fwd;
-        const long k = back ? i - n_fwd : i;
-        const int taps = back ? (ksize == 3 ? 9 : ksize == 2 ? 4 : 1) : (ksize == 3 ? 9 : 1);
-        const int N = back ? C : (ksize == 2 ? 4 * O : O), K = back ? O : C;           // rows and reduction length of this packing
-        const int KBn = (K + 15) / 16;
-        const int e = (int)(k & 3), lane = (int)((k >> 2) & 63);
-        const long s = k >> 8;
-        const int kb = (int)(s % KBn), tap = (int)((s / KBn) % taps), nt = (int)(s / ((long)KBn * taps));
-        const int n = 16 * nt + (lane & 15), r = 16 * kb + 4 * (lane >> 4) + e;
-        float v = 0.f;
-        if (n < N && r < K) {
-            if (!back) v = ksize == 2 ? weight_at(w0, w1, 2, C, n0, n1, n >> 2, n & 3, r) : weight_at(w0, w1, ksize, C, n0, n1, n, tap, r);
-            else {
-                v = weight_at(w0, w1, ksize, C, n0, n1, r, ksize == 3 ? 8 - tap : tap, n);
-                if (scale != nullptr) v = v * scale[r];
-            }
-        }
-        (back ? bwd : fwd)[k] = v;
-    } else if (i < n_fwd + n_bwd + n_bias) {
-        const int n = (int)(i - n_fwd - n_bwd);
-        const int o = ksize == 2 ? n >> 2 : n;
-        float v = 0.f;
-        if (o < O) v = o < n0 ? b0[o] : b1[o - n0];
-        fwd_bias[n] = v;
-    }
+    weight_pack_element<float>((long)blockIdx.x * HEAD_THREADS + threadIdx.x, w0, b0, w1, b1, scale, ksize, C, n0, n1, fwd, fwd_bias, bwd, n_fwd, n_bwd, n_bias);
 }
 
 // MODE 0: one tap (1x1 conv, linear); 1: 3x3, pad 1; 2: ConvTranspose2d(2, 2), stride 1 only.  A wave owns 16 outputs o x 16 CT channels c x all
@@ -290,13 +262,11 @@ int run_wgrad(const char* fn, const cosy_head_layer_t& a, int stride, long M, co
 // the one pack launch, after the caller's own argument checks: n0 (+ n1 sibling) outputs of c_in channels
 int run_weight_pack(const char* fn, const float* w0, const float* b0, const float* w1, const float* b1, const float* scale, int ksize, int c_in, int n0, int n1,
                     float* fwd, float* fwd_bias, float* bwd, hipStream_t s) {
-    const long O = n0 + n1, Nf = ksize == 2 ? 4 * O : O, Tf = ksize == 3 ? 9 : 1, Tb = ksize == 3 ? 9 : ksize == 2 ? 4 : 1;
-    const long NPf = (Nf + 63) / 64 * 64, NPb = ((long)c_in + 63) / 64 * 64;
-    const long n_fwd = NPf * Tf * ((c_in + 15) / 16 * 16), n_bwd = NPb * Tb * ((O + 15) / 16 * 16);
-    const long total = n_fwd + n_bwd + NPf;
+    const pack_sizes_t z = pack_sizes(ksize, c_in, n0, n1, pack_frag<float>::KB);
+    const long total = z.n_fwd + z.n_bwd + z.n_bias;
     COSY_REQUIRE(total <= (1L << 36), "%s: %ld packed elements exceed 2^36", fn, total);
     hipLaunchKernelGGL(weight_pack_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, w0, b0, w1, b1, scale, ksize, c_in, n0, n1, fwd, fwd_bias, bwd,
-                       n_fwd, n_bwd, (int)NPf);
+                       z.n_fwd, z.n_bwd, (int)z.n_bias);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }

@@ -51,41 +51,13 @@ __device__ __forceinline__ bf16x8 image_frag(const unsigned char* image, int rd)
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// [nt][tap][kb][lane][e] holds W[16 nt + (lane & 15)][tap][32 kb + 8 (lane >> 4) + e]: the 16-bit fragment order of cosy_head_conv.  The rules are
-// kernels_detbwd.hip's weight_pack_kernel's (siblings w0 then w1; ksize 2: forward rows (o, dy, dx) with one tap, backward taps (dy, dx)); the
-// trunk's layers are the case n1 = 0, b0 = shift.  scale: one float32 product, then ONE rounding to bfloat16
+// cosy_head_weight_pack16 / cosy_trunk_weight_pack16: the same launch with bfloat16 packings (32 of the reduction per block, eight elements per lane);
+// scale: one float32 product, then ONE rounding to bfloat16 (detbwd_device.h's weight_pack_element)
 __global__ __launch_bounds__(HEAD_THREADS) void weight_pack16_kernel(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
                                                                      const float* __restrict__ b1, const float* __restrict__ scale, int ksize, int C, int n0, int n1,
                                                                      bf16_t* __restrict__ fwd, float* __restrict__ fwd_bias, bf16_t* __restrict__ bwd, long n_fwd,
                                                                      long n_bwd, int n_bias) {
-    const long i = (long)blockIdx.x * HEAD_THREADS + threadIdx.x;
-    const int O = n0 + n1;
-    if (i < n_fwd + n_bwd) {
-        const bool back = i >= n_fwd;
-        const long k = back ? i - n_fwd : i;
-        const int taps = back ? (ksize == 3 ? 9 : ksize == 2 ? 4 : 1) : (ksize == 3 ? 9 : 1);
-        const int N = back ? C : (ksize == 2 ? 4 * O : O), K = back ? O : C;           // rows and reduction length of this packing
-        const int KBn = (K + 31) / 32;
-        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63);
-        const long s = k >> 9;
-        const int kb = (int)(s % KBn), tap = (int)((s / KBn) % taps), nt = (int)(s / ((long)KBn * taps));
-        const int n = 16 * nt + (lane & 15), r = 32 * kb + 8 * (lane >> 4) + e;
-        float v = 0.f;
-        if (n < N && r < K) {
-            if (!back) v = ksize == 2 ? weight_at(w0, w1, 2, C, n0, n1, n >> 2, n & 3, r) : weight_at(w0, w1, ksize, C, n0, n1, n, tap, r);
-            else {
-                v = weight_at(w0, w1, ksize, C, n0, n1, r, ksize == 3 ? 8 - tap : tap, n);
-                if (scale != nullptr) v = v * scale[r];
-            }
-        }
-        (back ? bwd : fwd)[k] = (bf16_t)v;
-    } else if (i < n_fwd + n_bwd + n_bias) {
-        const int n = (int)(i - n_fwd - n_bwd);
-        const int o = ksize == 2 ? n >> 2 : n;
-        float v = 0.f;
-        if (o < O) v = o < n0 ? b0[o] : b1[o - n0];
-        fwd_bias[n] = v;
-    }
+    weight_pack_element<bf16_t>((long)blockIdx.x * HEAD_THREADS + threadIdx.x, w0, b0, w1, b1, scale, ksize, C, n0, n1, fwd, fwd_bias, bwd, n_fwd, n_bwd, n_bias);
 }
 
 // NCHW float32 (B, n0, HW) and (B, n1, HW) -> bfloat16 rows (B HW, GP): the columns of the first, then of the second, then +0.0; a null tensor is
@@ -320,13 +292,11 @@ int run_weight_pack16(const char* fn, const float* w0, const float* b0, const fl
     COSY_REQUIRE(((uintptr_t)w0 & 3) == 0 && ((uintptr_t)b0 & 3) == 0 && ((uintptr_t)w1 & 3) == 0 && ((uintptr_t)b1 & 3) == 0 && ((uintptr_t)scale & 3) == 0 &&
                  ((uintptr_t)fwd & 15) == 0 && ((uintptr_t)bwd & 15) == 0 && ((uintptr_t)fwd_bias & 3) == 0,
                  "%s: the parameters, scale and fwd_bias must be 4-byte, fwd and bwd 16-byte aligned", fn);
-    const long O = (long)n0 + n1, Nf = ksize == 2 ? 4 * O : O, Tf = ksize == 3 ? 9 : 1, Tb = ksize == 3 ? 9 : ksize == 2 ? 4 : 1;
-    const long NPf = (Nf + 63) / 64 * 64, NPb = ((long)c_in + 63) / 64 * 64;
-    const long n_fwd = NPf * Tf * ((c_in + 31) / 32 * 32), n_bwd = NPb * Tb * ((O + 31) / 32 * 32);
-    const long total = n_fwd + n_bwd + NPf;
+    const pack_sizes_t z = pack_sizes(ksize, c_in, n0, n1, pack_frag<bf16_t>::KB);
+    const long total = z.n_fwd + z.n_bwd + z.n_bias;
     COSY_REQUIRE(total <= (1L << 36), "%s: %ld packed elements exceed 2^36", fn, total);
     hipLaunchKernelGGL(weight_pack16_kernel, dim3(cdiv(total, HEAD_THREADS)), dim3(HEAD_THREADS), 0, s, w0, b0, w1, b1, scale, ksize, c_in, n0, n1, (bf16_t*)fwd,
-                       fwd_bias, (bf16_t*)bwd, n_fwd, n_bwd, (int)NPf);
+                       fwd_bias, (bf16_t*)bwd, z.n_fwd, z.n_bwd, (int)z.n_bias);
     COSY_CHECK_HIP(hipGetLastError());
     return COSY_OK;
 }

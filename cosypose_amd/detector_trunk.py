@@ -540,6 +540,14 @@ class Detector:
         for t in self.parameters():
             t.grad = None
 
+    def optimizer(self, **kw):
+        """detector_optim.FlatSGD over this detector's parameters (lr=, momentum=, weight_decay=): its step keeps the packings of every trainable
+        layer of the trunk and the heads current with one launch"""
+        from .detector_heads import PackedOnDevice
+        from .detector_optim import FlatSGD
+        self._need_trainable('optimizer')
+        return FlatSGD(self, layers=[l for l in self.trunk.layers() + self.heads.layers() if isinstance(l, PackedOnDevice)], **kw)
+
     def state_dict(self):
         self._need_trainable('state_dict')
         return {**self.trunk.state_dict(), **self.heads.state_dict()}

@@ -709,8 +709,8 @@ class FlatAdam:
 
 def allreduce_gradients(flat_grad, force=False):
     """DDP's gradient averaging as ONE all-reduce of the flat gradient buffer (42.8 MB fp32 for this network).
-    `flat_grad`: the buffer, or a FlatAdam (gradients that were detached from its buffer are collected first, so that
-    what is reduced is what the step will use).  force=True runs the collective in a 1-rank group too (RCCL smoke test)."""
+    `flat_grad`: the buffer, or a FlatAdam or the detector's detector_optim.FlatSGD (gradients that were detached from its
+    buffer are collected first, so that what is reduced is what the step will use).  force=True runs the collective in a 1-rank group too (RCCL smoke test)."""
     import torch.distributed as dist
     if isinstance(flat_grad, FlatAdam):
         if flat_grad.reduced and not force:       # EVERY backward since zero_grad launched its own bucketed all-reduce (FlatAdam.overlap_allreduce): already averaged
@@ -719,6 +719,12 @@ def allreduce_gradients(flat_grad, force=False):
             raise RuntimeError(f'allreduce_gradients: {flat_grad.n_reduced} of the {flat_grad.n_backward} backwards accumulated since zero_grad averaged their own '
                                'gradients (overlap_allreduce) and the others did not: the buffer mixes averaged and local gradients')
         flat_grad._collect_stray_gradients()
+        flat_grad = flat_grad.grad
+    elif not torch.is_tensor(flat_grad):
+        from .detector_optim import FlatSGD
+        if not isinstance(flat_grad, FlatSGD):
+            raise TypeError(f'allreduce_gradients takes the flat gradient buffer, a FlatAdam or a FlatSGD, got {type(flat_grad).__name__}')
+        flat_grad._collect_stray_gradients()      # the detector's optimiser: the same rule, no bucketed path of its own
         flat_grad = flat_grad.grad
     if dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or force):
         dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM)

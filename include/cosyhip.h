@@ -1185,6 +1185,36 @@ int cosy_head_dgrad16(const cosy_head_layer_t* layer, const void* y, cosy_stream
 int cosy_head_wgrad16(const cosy_head_layer_t* layer, const void* g, float* dw0, float* db0, float* dw1, float* db1, void* workspace,
                       size_t workspace_bytes, cosy_stream_t stream);
 
+/* ---- the detector's optimiser step on flat buffers, and the repack of all its layers in one launch ----  DESIGN.md section 33 holds the contract.
+ * cosy_sgd_step: torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov, on flat float32 buffers of n elements.  lr, momentum and
+ *   weight_decay are float32 (the caller rounds them); every product and every sum below is ONE rounded float32 operation, nothing is fused:
+ *     d  = g + weight_decay w            (weight_decay == 0: d = g, no product is formed)
+ *     m' = d when first_step != 0, else momentum m + d      (momentum == 0: m' = d and momentum_buf is neither read nor written; it may be NULL)
+ *     w' = w - lr m'
+ *   NaN and Inf propagate as these operations propagate them.  A streaming kernel: 16-byte loads and stores on the body (the three buffers must
+ *   be 16-byte aligned), a scalar tail for n % 4, a grid of cosy_sgd_step_pass_elements() / 1024 workgroups (a function of the device's
+ *   compute-unit count) that strides, 64-bit offsets, no atomics.  n = 0 launches nothing.
+ * cosy_sgd_step_pass_elements: the elements one pass of that grid covers on the current device (tests size a buffer past it).
+ * cosy_pack_table_build: the layers of a pack table, one row of 13 long long words each:
+ *     [0] w0  [1] b0  [2] w1  [3] b1  [4] scale  [5] fwd  [6] fwd_bias  [7] bwd       device addresses (w1, b1, scale: 0 for none)
+ *     [8] ksize  [9] c_in  [10] n0  [11] n1  [12] dtype (COSY_F32 or COSY_BF16: the type of fwd and bwd)
+ *   A row means what cosy_head_weight_pack (COSY_F32) / cosy_head_weight_pack16 (COSY_BF16) mean by the same arguments, with one addition: scale
+ *   (n0 floats, n1 = 0), the trunk's FrozenBatchNorm scale as cosy_trunk_weight_pack takes it (b0 is then the shift).  Every row is checked as those
+ *   entries check their arguments, and fwd / bwd 16-byte, every other pointer 4-byte aligned (COSY_EINVAL, the message starts with
+ *   "cosy_pack_table_build: layer <i>:"), before anything touches the device.  Then the table is written to `table` (device memory of
+ *   cosy_pack_table_bytes(n_layers) bytes, 16-byte aligned, owned by the caller) and the call returns once it is there; *n_workgroups receives
+ *   the grid of the run.  Layers start on workgroup boundaries: the table holds every layer's first workgroup.  1 <= n_layers <= 4096.
+ * cosy_pack_table_run: ONE launch that writes fwd, fwd_bias and bwd of every layer of a built table from the parameters as they are now: the
+ *   bytes the per-layer entries write (the packing rules exist once, csrc/detbwd_device.h).  A workgroup finds its layer by a search of the
+ *   first-workgroup column, the same for all its threads.  It only launches: no validation of the table's contents, no copy.  table,
+ *   n_layers and n_workgroups are those of the build. */
+int cosy_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum, float weight_decay, int first_step,
+                  cosy_stream_t stream);
+long long cosy_sgd_step_pass_elements(void);
+size_t cosy_pack_table_bytes(int n_layers);
+int cosy_pack_table_build(const long long* rows, int n_layers, void* table, size_t table_bytes, long long* n_workgroups, cosy_stream_t stream);
+int cosy_pack_table_run(const void* table, int n_layers, long long n_workgroups, cosy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
