@@ -152,6 +152,13 @@ def lib():
     return _lib
 
 
+def rows_entry(name, dtype):
+    """the detector backward's entry point `name` for rows of dtype: the float32 symbol, or its `16` twin for bfloat16 rows"""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise CosyHipError(f'{name}: the rows of the backward are float32 or bfloat16, got {dtype}')
+    return getattr(lib(), name if dtype == torch.float32 else name + '16')
+
+
 def check(rc):
     if rc != 0:
         raise CosyHipError(f'libcosyhip error {rc}: {lib().cosy_last_error().decode()}')

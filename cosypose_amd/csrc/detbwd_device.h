@@ -1,8 +1,9 @@
 // The trunk's data gradient as a template over the type of its rows (DESIGN.md sections 29 and 30): the forward GEMM's chain over the rows g
 // with the transposed, tap-flipped weight, the parity classes of a stride-2 layer, and the store that adds up to two operands (SAME, EVEN,
 // NEAREST_T), applies the ReLU mask of the layer below and converts ONCE to the rows' type.  kernels_detbwd.hip instantiates it for float32 rows
-// (cosy_head_dgrad, cosy_trunk_dgrad: the instruction streams hipcc gave that file's own text of the kernel, kernel for kernel),
-// kernels_detbwd16.hip for bfloat16 rows (cosy_trunk_dgrad16, and cosy_head_dgrad16, whose NCHW store writes the accumulator as float32).
+// (cosy_head_dgrad, cosy_trunk_dgrad) and for bfloat16 rows (cosy_trunk_dgrad16, and cosy_head_dgrad16, whose NCHW store writes the accumulator
+// as float32).  Beside it, the host code both row types share wherever it launches no kernel of one file alone: the packing rules and their
+// validator (kernels_detopt.hip's pack table runs both too), the gradient packs' validator, the level check and the data gradients' contracts.
 //   float32 rows: every term of a block is one fmaf, four v_mfma_f32_16x16x4_f32 per (block of 16 o, live tap).
 //   16-bit rows: one v_mfma_f32_16x16x32 per (block of 32 o, live tap); the products are exact in float32, the accumulation is float32.
 // Store, per element: t = acc; t = t + (float)operand, in the order given, every + one rounded float32 add; t = y <= 0 ? +0.0 : t (a NaN y
@@ -15,14 +16,19 @@ namespace detbwd {
 
 using namespace headgemm;
 
-// kernels_detbwd.hip: the weight gradient's slab rule (cosy_head_wgrad_slab_rows, cosy_head_wgrad_workspace_bytes) and its second pass, which
-// adds the slabs' float32 partial tiles in ascending order, multiplies by scale[o] once and writes torchvision's layout
-int wgrad_slab_rows_of(int M);
-long wgrad_slab_floats_of(int ksize, int c_in, int c_out);
-int wgrad_combine(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, const float* scale, float* dw, float* db, hipStream_t s);
-// the heads' form: outputs [0, n_split) to dw0 / db0 (db0 null: no bias gradient), the rest to dw1 / db1; ksize 2: (C, O, 2, 2)
-int wgrad_combine_split(const float* partial, int nslab, long slab_floats, int ksize, int c_in, int c_out, int n_split, const float* scale, float* dw0, float* db0,
-                        float* dw1, float* db1, hipStream_t s);
+inline int pad8(int n) { return (n + 7) / 8 * 8; }
+inline bool aligned(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+
+// The first pass of a weight gradient as kernels_detbwd.hip's run_wgrad<T> planned it: the grid is (waves / 4, nslab).  The float32 rows' kernel
+// lives in kernels_detbwd.hip, the bfloat16 rows' in kernels_detbwd16.hip; a wave takes 16 outputs x wgrad_group_channels<T>(ksize) channels.
+struct wgrad_plan_t {
+    int GP, M, slab, nslab, n_waves, c_groups, want_db;
+    float* partial;
+    long slab_floats;
+};
+template <typename T> constexpr int wgrad_group_channels(int ksize) { return ksize == 1 || (sizeof(T) == 2 && ksize == 2) ? 64 : 16; }
+void launch_wgrad(const cosy_head_layer_t& a, int stride, const float* g, const wgrad_plan_t& p, hipStream_t s);
+void launch_wgrad(const cosy_head_layer_t& a, int stride, const bf16_t* g, const wgrad_plan_t& p, hipStream_t s);
 
 // the element (o, tap, c) of a layer's weight in torchvision's layout; o runs over the first tensor's outputs, then the second's.
 // ksize 1 / 3: (O, C, k, k) or (O, C); ksize 2: ConvTranspose2d's (C, O, 2, 2)
@@ -84,14 +90,67 @@ inline pack_sizes_t pack_sizes(int ksize, int c_in, int n0, int n1, int KB) {
     return pack_sizes_t{NPf * Tf * (((long)c_in + KB - 1) / KB * KB), NPb * Tb * ((O + KB - 1) / KB * KB), NPf};
 }
 
-// ConvTranspose2d(2, 2)'s data gradient on rows of T: dethead_device.h's DeconvGradPolicy (conv_gemm_kernel's four stride-2 taps) with the mask
-// rows y in the rows' type
-template <typename T> struct grad_epi_of { const T* y; };
+// What every weight pack asks of its arguments, whoever packs: the four entry points (`at`: the entry's name) and every row of the pack table
+// (`at`: "cosy_pack_table_build: layer l").  The trunk's layers are the case n1 = 0, b0 = shift.  KB: pack_frag<T>::KB of the packings' type.
+// -> COSY_OK and the sizes of the packings, or COSY_EINVAL after set_error
+inline int check_weight_pack(const char* at, const void* w0, const void* b0, const void* w1, const void* b1, const void* scale, const void* fwd, const void* fwd_bias,
+                             const void* bwd, long long ksize, long long c_in, long long n0, long long n1, int KB, pack_sizes_t* sizes) {
+    COSY_REQUIRE(ksize == 1 || ksize == 2 || ksize == 3, "%s: ksize=%lld must be 1, 3 or 2 (ConvTranspose2d(2, 2))", at, ksize);
+    COSY_REQUIRE(c_in >= 8 && c_in % 8 == 0 && c_in <= (1 << 24), "%s: the reduction length c_in=%lld must be a positive multiple of 8", at, c_in);
+    COSY_REQUIRE(n0 >= 1 && n1 >= 0 && n0 <= (1 << 22) && n1 <= (1 << 22) && n0 + n1 <= (1 << 22), "%s: n0=%lld must be >= 1 and n1=%lld >= 0", at, n0, n1);
+    COSY_REQUIRE(ksize != 2 || (n1 == 0 && n0 % 8 == 0), "%s: a deconvolution has no sibling and n0=%lld a multiple of 8", at, n0);
+    COSY_REQUIRE(scale == nullptr || (n1 == 0 && ksize != 2 && n0 % 8 == 0), "%s: a layer with a scale is one 1x1 or 3x3 convolution of a multiple of 8 outputs, got "
+                 "ksize=%lld n0=%lld n1=%lld", at, ksize, n0, n1);
+    COSY_REQUIRE(w0 != nullptr, "%s: null w0", at); COSY_REQUIRE(b0 != nullptr, "%s: null b0 (the bias, or the trunk's shift)", at);
+    COSY_REQUIRE(fwd != nullptr, "%s: null fwd", at); COSY_REQUIRE(fwd_bias != nullptr, "%s: null fwd_bias", at); COSY_REQUIRE(bwd != nullptr, "%s: null bwd", at);
+    COSY_REQUIRE(n1 == 0 || (w1 != nullptr && b1 != nullptr), "%s: null w1 or b1 with n1=%lld", at, n1);
+    COSY_REQUIRE(aligned(w0, 4) && aligned(b0, 4) && aligned(w1, 4) && aligned(b1, 4) && aligned(scale, 4) && aligned(fwd_bias, 4) && aligned(fwd, 16) && aligned(bwd, 16),
+                 "%s: the parameters, scale and fwd_bias must be 4-byte, fwd and bwd 16-byte aligned", at);
+    *sizes = pack_sizes((int)ksize, (int)c_in, (int)n0, (int)n1, KB);
+    const long total = sizes->n_fwd + sizes->n_bwd + sizes->n_bias;
+    COSY_REQUIRE(total <= (1L << 36), "%s: %ld packed elements exceed 2^36", at, total);
+    return COSY_OK;
+}
+
+// What both gradient packs (float32 rows: one thread per element; bfloat16 rows: eight columns per thread) ask of their arguments
+// -> the elements of the rows (B HW GP; 0: nothing to do), or -1 after set_error
+inline long check_grad_pack(const char* fn, const float* g0, const float* g1, const void* rows, int B, int n0, int n1, int HW) {
+    if (!(B >= 0 && HW >= 1)) { set_error("%s: B=%d must be >= 0 and HW=%d >= 1", fn, B, HW); return -1; }
+    if (!(n0 >= 0 && n1 >= 0 && n0 + n1 >= 1 && n0 + n1 <= (1 << 20))) { set_error("%s: n0=%d and n1=%d must be >= 0 and hold 1 to 2^20 columns", fn, n0, n1); return -1; }
+    if ((long)B * HW > HEAD_MAX_ROWS) { set_error("%s: B HW = %ld rows exceed 2^30", fn, (long)B * HW); return -1; }
+    if (B == 0) return 0;
+    if (rows == nullptr) { set_error("%s: null rows", fn); return -1; }
+    if (!(aligned(rows, 16) && aligned(g0, 4) && aligned(g1, 4))) { set_error("%s: rows must be 16-byte, g 4-byte aligned", fn); return -1; }
+    const long total = (long)B * HW * pad8(n0 + n1);
+    if (total > (1L << 38)) { set_error("%s: %ld elements exceed 2^38", fn, total); return -1; }
+    return total;
+}
+
+// ConvTranspose2d(2, 2)'s data gradient on rows of T is dethead_device.h's conv_gemm_kernel over the transposed weight:
+// the rows are the upstream gradient, no bias is added, and a row store may apply the ReLU mask of the layer below: y <= 0 ? +0.0 : v with y that
+// layer's stored rows, in the rows' type (torch's threshold_backward: a NaN y passes v).  TAPS2: the four taps (dy, dx) = (0..1, 0..1) at stride 2,
+// pad 0; the rows of the launch are the cells of the (H / 2, W / 2) map and no tap ever leaves the (H, W) map.
+template <typename T> struct grad_epi_of { const T* y; };      // rows (M, c_out), or null
 template <typename T> struct DeconvGradPolicyOf {
     static constexpr int STRIDE = 2;
     static constexpr bool TRUNK = false, GRAD = true, TAPS2 = true;
     typedef grad_epi_of<T> epi_t;
 };
+
+// M rows of the (H / 2, W / 2) maps, the four taps of the forward GEMM.  fn: the entry point the caller called; its name opens every message
+template <typename T> int launch_deconv_dgrad(const char* fn, const cosy_head_layer_t& a, int M, const T* y, hipStream_t s) {
+    typedef DeconvGradPolicyOf<T> P;
+    const conv_grid_t c = conv_grid<T>(a, M);
+    COSY_REQUIRE(c.blocks <= 0x7fffffffL, "%s: %d rows x c_out=%d need more than 2^31 - 1 workgroups", fn, M, a.c_out);
+    const dim3 grid((unsigned)c.blocks), block(HEAD_THREADS);
+    const grad_epi_of<T> e{y};
+    if (c.big_m && c.big_n) hipLaunchKernelGGL((conv_gemm_kernel<T, TILE_MT_BIG, TILE_NT_BIG, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_m) hipLaunchKernelGGL((conv_gemm_kernel<T, TILE_MT_BIG, 1, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else if (c.big_n) hipLaunchKernelGGL((conv_gemm_kernel<T, 1, TILE_NT_BIG, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    else hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 1, P>), grid, block, 0, s, a, M, c.KBn, c.n_tiles, c.n_groups, e);
+    COSY_CHECK_HIP(hipGetLastError());
+    return COSY_OK;
+}
 
 enum { ADD_NONE = 0, ADD_SAME = COSY_TRUNK_ADD_SAME, ADD_EVEN = COSY_TRUNK_ADD_EVEN, ADD_NEAREST_T = COSY_TRUNK_ADD_NEAREST_T };
 
@@ -341,6 +400,31 @@ template <typename T> int run_trunk_dgrad(const char* fn, const cosy_head_layer_
         if (rc != COSY_OK) return rc;
     }
     return COSY_OK;
+}
+
+// cosy_head_dgrad's contract (cosyhip.h) on rows of T, after the caller's check of the layer pointer and of dtype.  An NCHW store writes the
+// accumulator as float32 whatever T is
+template <typename T> int run_head_dgrad(const char* fn, const cosy_head_layer_t& a, const T* y, hipStream_t s) {
+    COSY_REQUIRE(a.ksize == 1 || a.ksize == 2 || a.ksize == 3, "%s: ksize=%d must be 1, 3 or 2 (ConvTranspose2d(2, 2))", fn, a.ksize);
+    COSY_REQUIRE(a.c_in >= 8 && a.c_in % 8 == 0, "%s: the reduction length c_in=%d must be a positive multiple of 8", fn, a.c_in);
+    COSY_REQUIRE(a.c_out >= 8 && a.c_out % 8 == 0, "%s: c_out=%d (the layer's input channels) must be a positive multiple of 8", fn, a.c_out);
+    COSY_REQUIRE(a.store == COSY_HEAD_STORE_ROWS || a.store == COSY_HEAD_STORE_NCHW, "%s: store=%d is not COSY_HEAD_STORE_ROWS or COSY_HEAD_STORE_NCHW", fn, a.store);
+    COSY_REQUIRE(a.relu == 0, "%s: relu=%d must be 0 (the mask is given by y)", fn, a.relu);
+    COSY_REQUIRE(a.store != COSY_HEAD_STORE_NCHW || (a.n_split == a.c_out && y == nullptr), "%s: an NCHW store takes n_split == c_out=%d and no y", fn, a.c_out);
+    const long rows_in = check_levels(fn, a);
+    if (rows_in < 0) return COSY_EINVAL;
+    long M = rows_in;
+    if (a.ksize == 2) {
+        COSY_REQUIRE(a.n_levels == 1 && a.H[0] % 2 == 0 && a.W[0] % 2 == 0, "%s: ksize 2 takes one level of even maps, got %d levels of %d x %d", fn, a.n_levels, a.H[0],
+                     a.W[0]);
+        M = rows_in / 4;
+    }
+    if (M == 0) return COSY_OK;
+    COSY_REQUIRE(a.x != nullptr && a.w != nullptr && a.out != nullptr, "%s: null layer->x, w or out", fn);
+    COSY_REQUIRE(aligned(a.x, 16) && aligned(a.w, 16) && aligned(a.out, 16) && aligned(y, 16), "%s: x, w, out and y must be 16-byte aligned", fn);
+    if (a.ksize == 2) return launch_deconv_dgrad<T>(fn, a, (int)M, y, s);
+    const tadd_t<T> none{nullptr, ADD_NONE, 1, 1, 1.f, 1.f};
+    return launch_dgrad_rows<T, 1>(fn, a, (int)M, tgrad_epi_t<T>{y, {none, none}, 0, 0}, s);
 }
 
 }  // namespace detbwd

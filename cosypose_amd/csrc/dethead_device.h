@@ -48,16 +48,7 @@ template <int STRIDE_, bool TRUNK_> struct ConvPolicy {
 };
 typedef ConvPolicy<1, false> HeadPolicy;
 
-// The data gradient of ConvTranspose2d(2, 2) is the same GEMM over the transposed weight: the rows are the upstream
-// gradient, no bias is added, and a row store may apply the ReLU mask of the layer below: y <= 0 ? +0.0 : v with y that layer's stored rows
-// (torch's threshold_backward: a NaN y passes v).  TAPS2: the four taps (dy, dx) = (0..1, 0..1) at stride 2, pad 0; the rows of the launch are
-// the cells of the (H / 2, W / 2) map and no tap ever leaves the (H, W) map.  (Every other data gradient is detbwd_device.h's dgrad_rows_kernel.)
-struct grad_epi_t { const float* y; };       // rows (M, c_out) float32, or null
-struct DeconvGradPolicy {
-    static constexpr int STRIDE = 2;
-    static constexpr bool TRUNK = false, GRAD = true, TAPS2 = true;
-    typedef grad_epi_t epi_t;
-};
+// (A third policy, with GRAD and TAPS2 set, is detbwd_device.h's DeconvGradPolicyOf<T>: the data gradient of ConvTranspose2d(2, 2).)
 
 template <typename T> __device__ __forceinline__ typename DT<T>::raw_t zero_frag() {
     typename DT<T>::raw_t z;

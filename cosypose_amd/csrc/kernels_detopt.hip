@@ -5,10 +5,11 @@
 //     both are template parameters, so a NaN or an Inf goes exactly where these operations carry it.  Streaming: a thread moves 16 bytes per
 //     buffer and iteration, the grid (GRID_PER_CU workgroups per compute unit) strides over the body, the n % 4 last elements are the scalar
 //     tail of the first threads.  64-bit offsets, no atomics, no LDS.
-//   * pack_table_kernel: the per-layer packs of kernels_detbwd.hip / kernels_detbwd16.hip, all layers in one grid.  The table (device memory,
+//   * pack_table_kernel: the per-layer packs of kernels_detbwd.hip, all layers in one grid.  The table (device memory,
 //     built once) holds the first workgroup of every layer, then one pack_layer_t per layer; a workgroup finds its layer by a binary search of
 //     the first column -- blockIdx.x alone decides, so every thread of the workgroup takes the same layer -- and runs detbwd_device.h's
-//     weight_pack_element on its element: the packing rules exist once.
+//     weight_pack_element on its element: the packing rules exist once, and so do the checks of a row (check_weight_pack).
+#include <cstdio>
 #include <vector>
 #include "detbwd_device.h"
 
@@ -163,30 +164,22 @@ int cosy_pack_table_build(const long long* rows, int n_layers, void* table, size
     long wgs = 0;
     for (int l = 0; l < n_layers; ++l) {
         const long long* r = rows + (size_t)l * PACK_ROW_WORDS;
-        const uintptr_t w0 = (uintptr_t)r[0], b0 = (uintptr_t)r[1], w1 = (uintptr_t)r[2], b1 = (uintptr_t)r[3], scale = (uintptr_t)r[4], fwd = (uintptr_t)r[5],
-                        fwd_bias = (uintptr_t)r[6], bwd = (uintptr_t)r[7];
+        void* ptrs[8];                                    // w0, b0, w1, b1, scale, fwd, fwd_bias, bwd
+        for (int k = 0; k < 8; ++k) ptrs[k] = (void*)(uintptr_t)r[k];
         const long long ksize = r[8], c_in = r[9], n0 = r[10], n1 = r[11], dtype = r[12];
-#define COSY_ROW "cosy_pack_table_build: layer %d: "
-        COSY_REQUIRE(dtype == COSY_F32 || dtype == COSY_BF16, COSY_ROW "dtype=%lld is not COSY_F32 or COSY_BF16 (float16 training needs a loss scaler, which is not built)", l, dtype);
-        COSY_REQUIRE(ksize == 1 || ksize == 2 || ksize == 3, COSY_ROW "ksize=%lld must be 1, 3 or 2 (ConvTranspose2d(2, 2))", l, ksize);
-        COSY_REQUIRE(c_in >= 8 && c_in % 8 == 0 && c_in <= (1 << 24), COSY_ROW "the reduction length c_in=%lld must be a positive multiple of 8", l, c_in);
-        COSY_REQUIRE(n0 >= 1 && n1 >= 0 && n0 <= (1 << 22) && n1 <= (1 << 22) && n0 + n1 <= (1 << 22), COSY_ROW "n0=%lld must be >= 1 and n1=%lld >= 0", l, n0, n1);
-        COSY_REQUIRE(ksize != 2 || (n1 == 0 && n0 % 8 == 0), COSY_ROW "a deconvolution has no sibling and n0=%lld a multiple of 8", l, n0);
-        COSY_REQUIRE(scale == 0 || (n1 == 0 && ksize != 2 && n0 % 8 == 0), COSY_ROW "a layer with a scale is one 1x1 or 3x3 convolution of a multiple of 8 outputs, got ksize=%lld n0=%lld n1=%lld",
-                     l, ksize, n0, n1);
-        COSY_REQUIRE(w0 != 0, COSY_ROW "null w0", l); COSY_REQUIRE(b0 != 0, COSY_ROW "null b0", l);
-        COSY_REQUIRE(fwd != 0, COSY_ROW "null fwd", l); COSY_REQUIRE(fwd_bias != 0, COSY_ROW "null fwd_bias", l); COSY_REQUIRE(bwd != 0, COSY_ROW "null bwd", l);
-        COSY_REQUIRE(n1 == 0 || (w1 != 0 && b1 != 0), COSY_ROW "null w1 or b1 with n1=%lld", l, n1);
-        COSY_REQUIRE((w0 & 3) == 0 && (b0 & 3) == 0 && (w1 & 3) == 0 && (b1 & 3) == 0 && (scale & 3) == 0 && (fwd & 15) == 0 && (bwd & 15) == 0 && (fwd_bias & 3) == 0,
-                     COSY_ROW "the parameters, scale and fwd_bias must be 4-byte, fwd and bwd 16-byte aligned", l);
-        const pack_sizes_t z = pack_sizes((int)ksize, (int)c_in, (int)n0, (int)n1, dtype == COSY_F32 ? pack_frag<float>::KB : pack_frag<bf16_t>::KB);
-        const long total = z.n_fwd + z.n_bwd + z.n_bias;
-        COSY_REQUIRE(total <= (1L << 36), COSY_ROW "%ld packed elements exceed 2^36", l, total);
-#undef COSY_ROW
+        char at[48];                                      // opens every message of this row
+        snprintf(at, sizeof at, "cosy_pack_table_build: layer %d", l);
+        COSY_REQUIRE(dtype == COSY_F32 || dtype == COSY_BF16, "%s: dtype=%lld is not COSY_F32 or COSY_BF16 (float16 training needs a loss scaler, which is not built)", at,
+                     dtype);
+        pack_sizes_t z;                                   // the rest is what the per-layer packs check (detbwd_device.h)
+        if (const int rc = check_weight_pack(at, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7], ksize, c_in, n0, n1,
+                                             dtype == COSY_F32 ? pack_frag<float>::KB : pack_frag<bf16_t>::KB, &z))
+            return rc;
         first[l] = wgs;
-        wgs += (total + HEAD_THREADS - 1) / HEAD_THREADS;
-        layers[l] = pack_layer_t{(const float*)w0, (const float*)b0, n1 ? (const float*)w1 : nullptr, n1 ? (const float*)b1 : nullptr, (const float*)scale, (void*)fwd,
-                                 (float*)fwd_bias, (void*)bwd, z.n_fwd, z.n_bwd, (int)ksize, (int)c_in, (int)n0, (int)n1, (int)dtype, (int)z.n_bias};
+        wgs += (z.n_fwd + z.n_bwd + z.n_bias + HEAD_THREADS - 1) / HEAD_THREADS;
+        layers[l] = pack_layer_t{(const float*)ptrs[0], (const float*)ptrs[1], n1 ? (const float*)ptrs[2] : nullptr, n1 ? (const float*)ptrs[3] : nullptr,
+                                 (const float*)ptrs[4], ptrs[5], (float*)ptrs[6], ptrs[7], z.n_fwd, z.n_bwd, (int)ksize, (int)c_in, (int)n0, (int)n1, (int)dtype,
+                                 (int)z.n_bias};
     }
     first[n_layers] = wgs;
     COSY_REQUIRE(wgs <= 0x7fffffffL, "cosy_pack_table_build: the %d layers need %ld workgroups, more than 2^31 - 1", n_layers, wgs);

@@ -34,10 +34,15 @@ def _dtype(dtype):
     return dtype
 
 
+def k_block(dtype):
+    """channels of one block of a GEMM's reduction (csrc/dethead_device.h: KB): one MFMA step of the rows' type"""
+    return 16 if dtype == torch.float32 else 32
+
+
 def pack_weight(w, dtype):
     """(N, taps, C_in) float32 CPU -> the fragment order cosy_head_conv reads (cosyhip.h): [N_pad / 16][tap][k-block][lane][element], zero padded"""
     N, taps, C = (int(v) for v in w.shape)
-    KB = 16 if dtype == torch.float32 else 32
+    KB = k_block(dtype)
     KBn, NP = -(-C // KB), -(-N // 64) * 64
     wp = torch.zeros((NP, taps, KBn * KB), dtype=torch.float32)
     wp[:N, :, :C] = w
@@ -136,8 +141,28 @@ def transposed_weight(kind, weight):
 
 
 class PackedOnDevice:
-    """What a trainable layer of the heads and one of the trunk share: parameters() on self.device, and w / bias / w_t that _pack() writes from
-    them on the device."""
+    """What a trainable layer of the heads and one of the trunk share: parameters() on self.device, and the packings w / bias / w_t that one
+    launch writes from them on the device.  A subclass states its layer once, as pack_args(), and how its entry point takes it, as _pack()."""
+
+    def pack_args(self):
+        """-> (w0, b0, w1, b1, scale, ksize, c_in, n0, n1): the layer as a weight pack takes it (cosyhip.h: cosy_head_weight_pack; a trunk
+        layer is the case n1 = 0, b0 = shift); tensors or None, ksize 2 for ConvTranspose2d(2, 2)"""
+        raise NotImplementedError
+
+    @staticmethod
+    def packed_sizes(ksize, c_in, n0, n1, dtype):
+        """-> the elements of (w, bias, w_t) that a pack writes: csrc/detbwd_device.h's pack_sizes"""
+        KB, O = k_block(dtype), n0 + n1
+        rows_f, taps_f, taps_b = (4 * O if ksize == 2 else O), (9 if ksize == 3 else 1), {1: 1, 2: 4, 3: 9}[ksize]
+        NPf, NPb = -(-rows_f // 64) * 64, -(-c_in // 64) * 64
+        return NPf * taps_f * (-(-c_in // KB) * KB), NPf, NPb * taps_b * (-(-O // KB) * KB)
+
+    def _alloc_packings(self):
+        n_w, n_bias, n_wt = self.packed_sizes(*self.pack_args()[5:], self.dtype)
+        self.w = torch.empty(n_w, dtype=self.dtype, device=self.device)
+        self.bias = torch.empty(n_bias, dtype=torch.float32, device=self.device)
+        self.w_t = torch.empty(n_wt, dtype=self.dtype, device=self.device)
+        self.versions = None
 
     def refresh(self, dev=None):
         """pack on the device when a parameter's _version (or its storage) has moved since the last pack, and not otherwise"""
@@ -203,24 +228,20 @@ class TrainableLayer(PackedOnDevice):
             raise ValueError(f'{kind} layer: the reduction length {self.c_in} must be a positive multiple of 8 (it is not padded silently)')
         if len(self.pairs) == 2:
             self.n_split = int(w0.shape[0])
-        C, O = self.c_in, self.n_grad
-        taps, gtaps = (9 if self.ksize == 3 else 1), {1: 1, 3: 9, 2: 4}[self.grad_ksize]
-        NP = -(-self.c_out // 64) * 64
-        KB = 16 if dtype == torch.float32 else 32
-        self.w = torch.empty(NP * taps * (-(-C // KB) * KB), dtype=dtype, device=self.device)
-        self.bias = torch.empty(NP, dtype=torch.float32, device=self.device)
-        self.w_t = torch.empty((-(-C // 64) * 64) * gtaps * (-(-O // KB) * KB), dtype=dtype, device=self.device)
-        self.versions = None
+        self._alloc_packings()
 
     def parameters(self):
         return [p for pair in self.pairs for p in pair]
 
-    def _pack(self):
+    def pack_args(self):
         (w0, b0), (w1, b1) = self.pairs[0], (self.pairs[1] if len(self.pairs) == 2 else (None, None))
         n0 = int(w0.shape[1] if self.kind == 'deconv' else w0.shape[0])
-        pack = _lib.lib().cosy_head_weight_pack if self.dtype == torch.float32 else _lib.lib().cosy_head_weight_pack16
-        _lib.check(pack(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), self.grad_ksize, self.c_in, n0, self.n_grad - n0, _lib.ptr(self.w),
-                        _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
+        return w0, b0, w1, b1, None, self.grad_ksize, self.c_in, n0, self.n_grad - n0
+
+    def _pack(self):
+        w0, b0, w1, b1, _, ksize, c_in, n0, n1 = self.pack_args()
+        _lib.check(_lib.rows_entry('cosy_head_weight_pack', self.dtype)(_lib.ptr(w0), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), ksize, c_in, n0, n1, _lib.ptr(self.w),
+                                                                      _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
 
     @classmethod
     def conv(cls, weight, bias=None, relu=False, device=None, counter=None, dtype=torch.float32):
@@ -350,7 +371,7 @@ def _grad_pack(g0, g1, rows, B, n0, n1, HW):
         if g is not None and (g.dtype != torch.float32 or g.numel() != B * n * HW or not g.is_cuda):
             raise ValueError(f'a gradient of {B} x {n} x {HW} float32 values on the device was expected, got {tuple(g.shape)} {g.dtype} on {g.device}')
     if B:
-        pack = _lib.lib().cosy_head_grad_pack if rows.dtype == torch.float32 else _lib.lib().cosy_head_grad_pack16
+        pack = _lib.rows_entry('cosy_head_grad_pack', rows.dtype)
         _lib.check(pack(_lib.ptr(None if g0 is None else g0.contiguous()), _lib.ptr(None if g1 is None else g1.contiguous()), _lib.ptr(rows), B, n0, n1, HW,
                         _lib.stream()))
     return rows
@@ -364,8 +385,7 @@ def _dgrad(layer, g_rows, maps, store, out, y=None):
     d.dtype, d.ksize, d.c_in, d.c_out, d.relu, d.store = _DTYPES[layer.dtype], layer.grad_ksize, int(g_rows.shape[1]), layer.c_in, 0, store
     d.n_split = layer.c_in
     if _describe(d, maps):
-        dgrad = _lib.lib().cosy_head_dgrad if layer.dtype == torch.float32 else _lib.lib().cosy_head_dgrad16
-        _lib.check(dgrad(ctypes.byref(d), _lib.ptr(y), _lib.stream()))
+        _lib.check(_lib.rows_entry('cosy_head_dgrad', layer.dtype)(ctypes.byref(d), _lib.ptr(y), _lib.stream()))
     return out
 
 
@@ -384,7 +404,7 @@ def _wgrad(layer, x_rows, g_rows, maps):
     d.dtype, d.ksize, d.c_in, d.c_out = _DTYPES[layer.dtype], layer.grad_ksize, layer.c_in, layer.n_grad
     d.n_split = getattr(layer, 'n_split', layer.n_grad)
     out, ws, need = _wgrad_buffers(layer, _describe(d, maps), layer.grad_ksize, layer.n_grad)
-    wgrad = _lib.lib().cosy_head_wgrad if layer.dtype == torch.float32 else _lib.lib().cosy_head_wgrad16
+    wgrad = _lib.rows_entry('cosy_head_wgrad', layer.dtype)
     _lib.check(wgrad(ctypes.byref(d), _lib.ptr(g_rows), *[_lib.ptr(t) for t in (out + [None, None])[:4]], _lib.ptr(ws), need, _lib.stream()))
     return out
 

@@ -34,26 +34,14 @@ def _params_of(params_or_detector):
 
 
 def table_row(layer):
-    """a PackedOnDevice layer -> the 13 words of its row: a heads' layer (one pair, or the two siblings of one GEMM) as cosy_head_weight_pack
-    takes it, a trunk's layer (weight, FrozenBatchNorm scale and shift, or the FPN's bias) as cosy_trunk_weight_pack does"""
-    if hasattr(layer, 'pairs'):
-        (w0, b0), (w1, b1) = layer.pairs[0], (layer.pairs[1] if len(layer.pairs) == 2 else (None, None))
-        n0 = int(w0.shape[1] if layer.kind == 'deconv' else w0.shape[0])
-        scale, ksize, n1 = None, layer.grad_ksize, layer.n_grad - n0
-    else:
-        w0, b0, w1, b1 = layer.weight, (layer.shift if layer.bias_param is None else layer.bias_param), None, None
-        scale, ksize, n0, n1 = layer.scale, layer.ksize, layer.c_out, 0
-    # the buffers the launch writes must hold what it writes: the sizes of the per-layer packs (csrc/detbwd_device.h: pack_sizes)
-    KB = 16 if layer.dtype == torch.float32 else 32
-    O, rows_f = n0 + n1, (4 * (n0 + n1) if ksize == 2 else n0 + n1)
-    taps_f, taps_b = (9 if ksize == 3 else 1), {1: 1, 2: 4, 3: 9}[ksize]
-    NPf, NPb = -(-rows_f // 64) * 64, -(-layer.c_in // 64) * 64
-    want = (NPf * taps_f * (-(-layer.c_in // KB) * KB), NPf, NPb * taps_b * (-(-O // KB) * KB))
+    """a PackedOnDevice layer -> the 13 words of its row: its pack_args(), its three packings and the type of its rows"""
+    w0, b0, w1, b1, scale, ksize, c_in, n0, n1 = layer.pack_args()
+    want = layer.packed_sizes(ksize, c_in, n0, n1, layer.dtype)          # the buffers the launch writes must hold what it writes
     have = (layer.w.numel(), layer.bias.numel(), layer.w_t.numel())
     if have != want or layer.w.dtype != layer.dtype or layer.w_t.dtype != layer.dtype or layer.bias.dtype != torch.float32:
         raise ValueError(f'FlatSGD: a layer\'s packings hold {have} elements of {layer.w.dtype}, its pack writes {want} of {layer.dtype}')
     ptr = lambda t: 0 if t is None else t.data_ptr()
-    return [ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(scale), ptr(layer.w), ptr(layer.bias), ptr(layer.w_t), ksize, layer.c_in, n0, n1, _lib.DTYPES[layer.dtype]]
+    return [ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(scale), ptr(layer.w), ptr(layer.bias), ptr(layer.w_t), ksize, c_in, n0, n1, _lib.DTYPES[layer.dtype]]
 
 
 class PackTable:

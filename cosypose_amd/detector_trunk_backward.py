@@ -1,8 +1,8 @@
 """The backward of the detector's trunk on the matrix pipe: the data and weight gradients of the ResNet
 bottlenecks and the FPN as GEMMs (HIP: csrc/kernels_detbwd.hip, the heads' gradient kernels -- cosy_trunk_weight_pack, cosy_trunk_dgrad, cosy_trunk_wgrad), the
 trainable layer that holds a trunk parameter, and the autograd node behind DetectorTrunk(trainable=True).  float32, or with
-train_dtype=torch.bfloat16 (section 30; csrc/kernels_detbwd16.hip -- cosy_trunk_weight_pack16, cosy_trunk_grad_pack16, cosy_trunk_dgrad16,
-cosy_trunk_wgrad16) bfloat16 rows and packed weights under float32 parameters, the master weights, and float32 gradients.
+train_dtype=torch.bfloat16 (section 30; the same entry points with `16` appended, picked by _lib.rows_entry, and cosy_trunk_grad_pack16)
+bfloat16 rows and packed weights under float32 parameters, the master weights, and float32 gradients.
 
 A trunk layer is v = fmaf(conv_stride(x, W), scale, shift) [+ r], y = relu(v).  Its gradient rows g are the gradient at v, float32 rows on
 the layer's OUTPUT grid.  No scaled copy of g is stored: the data gradient reads ws = w scale[o] (packed once per weight version), the weight
@@ -82,21 +82,18 @@ class TrainableTrunkLayer(PackedOnDevice):
             if b.dim() != 1 or b.shape[0] != O:
                 raise ValueError(f'{name}.bias must be ({O}), got {tuple(b.shape)}')
             self.bias_param = torch.nn.Parameter(b.detach().to(device=dev, dtype=F32).contiguous().clone())
-        taps = k * k
-        KB = 16 if dtype == F32 else 32
-        self.w = torch.empty(NP * taps * (-(-C // KB) * KB), dtype=dtype, device=dev)
-        self.bias = torch.empty(NP, dtype=F32, device=dev)
-        self.w_t = torch.empty((-(-C // 64) * 64) * taps * (-(-O // KB) * KB), dtype=dtype, device=dev)
-        self.versions = None
+        self._alloc_packings()
 
     def parameters(self):
         return [self.weight] + ([self.bias_param] if self.bias_param is not None else [])
 
+    def pack_args(self):
+        return self.weight, (self.shift if self.bias_param is None else self.bias_param), None, None, self.scale, self.ksize, self.c_in, self.c_out, 0
+
     def _pack(self):
-        shift = self.shift if self.bias_param is None else self.bias_param
-        pack = _lib.lib().cosy_trunk_weight_pack if self.dtype == F32 else _lib.lib().cosy_trunk_weight_pack16
-        _lib.check(pack(_lib.ptr(self.weight), _lib.ptr(self.scale), _lib.ptr(shift), self.ksize, self.c_in, self.c_out, _lib.ptr(self.w), _lib.ptr(self.bias),
-                        _lib.ptr(self.w_t), _lib.stream()))
+        w, shift, _, _, scale, ksize, c_in, c_out, _ = self.pack_args()
+        _lib.check(_lib.rows_entry('cosy_trunk_weight_pack', self.dtype)(_lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), ksize, c_in, c_out, _lib.ptr(self.w),
+                                                                       _lib.ptr(self.bias), _lib.ptr(self.w_t), _lib.stream()))
 
     ready = PackedOnDevice.refresh
 
@@ -118,7 +115,7 @@ def trunk_dgrad(layer, g_rows, B, H, W, out, adds=(), y=None, store=_lib.HEAD_ST
     flat = []
     for rule, rows, aH, aW in adds + [(_lib.TRUNK_ADD_NONE, None, 0, 0)] * (2 - len(adds)):
         flat += [_lib.ptr(rows), rule, aH, aW]
-    dgrad = _lib.lib().cosy_trunk_dgrad if layer.dtype == F32 else _lib.lib().cosy_trunk_dgrad16
+    dgrad = _lib.rows_entry('cosy_trunk_dgrad', layer.dtype)
     _lib.check(dgrad(ctypes.byref(d), layer.stride if stride is None else stride, *flat, _lib.ptr(y), _lib.stream()))
     return out
 
@@ -131,7 +128,7 @@ def trunk_wgrad(layer, x_rows, g_rows, B, H, W):
     _describe(d, [(B, H, W)])
     Ho, Wo = layer.out_size(H, W)
     out, ws, need = _wgrad_buffers(layer, B * Ho * Wo, layer.ksize, layer.c_out)
-    wgrad = _lib.lib().cosy_trunk_wgrad if layer.dtype == F32 else _lib.lib().cosy_trunk_wgrad16
+    wgrad = _lib.rows_entry('cosy_trunk_wgrad', layer.dtype)
     _lib.check(wgrad(ctypes.byref(d), layer.stride, _lib.ptr(g_rows), _lib.ptr(layer.scale), _lib.ptr(out[0]), _lib.ptr(out[1]) if len(out) > 1 else None,
                      _lib.ptr(ws), need, _lib.stream()))
     return out
@@ -144,7 +141,7 @@ def trunk_grad_pack(g, rows, B, C, HW):
     if g is not None and (g.dtype != F32 or g.numel() != B * C * HW or not g.is_cuda):
         raise ValueError(f'a gradient of {B} x {C} x {HW} float32 values on the device was expected, got {tuple(g.shape)} {g.dtype} on {g.device}')
     if B:
-        _lib.check(_lib.lib().cosy_trunk_grad_pack16(_lib.ptr(None if g is None else g.contiguous()), _lib.ptr(rows), B, C, HW, _lib.stream()))
+        _lib.check(_lib.rows_entry('cosy_trunk_grad_pack', rows.dtype)(_lib.ptr(None if g is None else g.contiguous()), _lib.ptr(rows), B, C, HW, _lib.stream()))
     return rows
 
 
