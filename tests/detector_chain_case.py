@@ -1,8 +1,10 @@
 """The cases that tests/test_detector_chain_host.py (CPU) and tests/test_detector_chain.py (GPU) share: seeded frames, targets and sampler keys
 for one training step of the narrow detector of dettrunk_case.detector_weights(), and the inputs of detector_chain_ref.Chain taken from the
 twins' chain on the CPU (the GPU test takes them from the device run instead).  The seeds were chosen on the CPU so that the float64 graph and
-its float32 replica take the same side at every kink (test_detector_chain_host.py keeps that check)."""
+its float32 replica take the same side at every kink (test_detector_chain_host.py keeps that check), and so that each case reaches what it is
+there for (check_reach, run by the CPU test on the twins' decisions and by every GPU test on the device's own)."""
 import functools
+import math
 
 import numpy as np
 import torch
@@ -17,7 +19,9 @@ SIZES, RATIOS = ((32,), (64,), (128,), (256,), (512,)), (0.5, 1.0, 2.0)        #
 RPN_BATCH, ROI_BATCH, ROI_POSITIVES, TOP_N = 256, 512, 128, 2000               # torchvision's training values, as detector_losses has them
 N_STAGES = len(tc.BLOCKS)
 
-# name -> frame sizes (h, w), input_resize, seeds of the frames / the masks / the keys, ground truths per frame (x1, y1, x2, y2, label)
+# name -> frame sizes (h, w), input_resize, seeds of the frames / the masks / the keys, ground truths per frame (x1, y1, x2, y2, label[, mask
+# fill]): the share of the box's pixels that its mask holds, MASK_FILL unless given; 0.0 is an all-zero mask, 1.0 the whole box
+MASK_FILL = 0.8
 CASES = {
     # tests/test_detector_trunk_backward.py's end-to-end frames and targets: 64 x 64 after padding, every RoI on level 0
     'small': dict(frames=tc.E2E_FRAMES, resize=(48, 64), seeds=(31, 41, 5),
@@ -26,6 +30,18 @@ CASES = {
     # leaves level 0 (sqrt(area) >= 112)
     'two-levels': dict(frames=[(120, 168), (150, 200)], resize=(160, 224), seeds=(32, 42, 6),
                        gt=[[(0, 0, 118, 103, 1)], [(0, 24, 127, 150, 2)]]),
+    # ONE frame that the resize leaves as it is: 448 px is the smallest side at which the level mapper reaches level 3 (sqrt(area) >= 448), so
+    # 480 x 640 with a ground truth over nearly the whole frame is the smallest case whose RoIs read and write all four maps.  The other three
+    # ground truths sit on levels 1, 0 and 0
+    'four-levels': dict(frames=[(480, 640)], resize=(480, 640), seeds=(33, 43, 7),
+                        gt=[[(10, 5, 630, 475, 1), (20, 30, 320, 290, 2), (400, 100, 540, 230, 1), (50, 300, 110, 350, 2)]]),
+    # three frames (an odd batch) of three shapes, so three network sizes on one 64 x 64 canvas, with 1, 3 and 5 ground truths (G differs from
+    # G_max on two images, the offsets are 0, 1, 4): a box over the whole frame on two images, two near-duplicates with different labels, a box of
+    # 6 x 5 px (about 4 x 3.4 px in the network: narrower than one cell of map 0, mask-target grid 1), an all-one and an all-zero mask
+    'mixed': dict(frames=[(90, 60), (60, 90), (70, 70)], resize=(48, 64), seeds=(34, 44, 8),
+                  gt=[[(0, 0, 60, 90, 1)],
+                      [(10, 10, 50, 40, 1), (12, 9, 52, 42, 2), (60, 30, 88, 58, 1, 1.0)],
+                      [(0, 0, 70, 70, 2), (40, 20, 46, 25, 1), (5, 5, 35, 30, 1, 0.0), (30, 35, 65, 66, 2), (3, 40, 28, 68, 1)]]),
 }
 
 
@@ -35,15 +51,15 @@ def frames(case):
 
 
 def targets(case):
-    """boxes (G,4) float32, labels (G) int64, masks (G,h,w) uint8: the box filled to 80 %"""
+    """boxes (G,4) float32, labels (G) int64, masks (G,h,w) uint8: the box filled to the ground truth's share (MASK_FILL: 80 %)"""
     c = CASES[case]
     rng = np.random.RandomState(c['seeds'][1])
     out = []
     for (h, w), gts in zip(c['frames'], c['gt']):
         boxes = np.array([g[:4] for g in gts], np.float32)
         masks = np.zeros((len(gts), h, w), np.uint8)
-        for m, (x1, y1, x2, y2) in zip(masks, boxes.astype(int)):
-            m[y1:y2, x1:x2] = rng.uniform(0, 1, (y2 - y1, x2 - x1)) < 0.8
+        for m, (x1, y1, x2, y2), g in zip(masks, boxes.astype(int), gts):
+            m[y1:y2, x1:x2] = rng.uniform(0, 1, (y2 - y1, x2 - x1)) < (g[5] if len(g) > 5 else MASK_FILL)     # uniform < 1 always, < 0 never
         out.append(dict(boxes=boxes, labels=np.array([g[4] for g in gts], np.int64), masks=masks))
     return out
 
@@ -79,6 +95,54 @@ def padded(parts, per_image, fill, dtype):
     for b, p in enumerate(parts):
         out[b * per_image:b * per_image + len(p)] = p
     return torch.from_numpy(out)
+
+
+def real_rows(inp, key, counts):
+    """the padded rows of inp[key] -> per image its real rows"""
+    per = int(inp[key].shape[0]) // len(inp['net_sizes'])
+    return [inp[key][b * per:b * per + int(c)] for b, c in enumerate(inp[counts])]
+
+
+def check_reach(case, inp, kinks):
+    """What each case was chosen to reach, asserted on detector_chain_ref.Chain's inputs (the twins' on the CPU, the device's own on the GPU) and on
+    the kinks of a float64 step over them; prints a summary first."""
+    B = len(inp['net_sizes'])
+    positives, backgrounds = [int(c) for c in inp['pos_counts']], [int((l == 0).sum()) for l in real_rows(inp, 'roi_labels', 'roi_counts')]
+    box_levels, mask_levels = ([sorted(set(r.tolist())) for r in real_rows(inp, k, c)] for k, c in (('roi_levels', 'roi_counts'), ('pos_levels', 'pos_counts')))
+    matched = [r.tolist() for r in real_rows(inp, 'pos_matched', 'pos_counts')]
+    print(f'{case}: images {tuple(inp["images"].shape)}, network sizes {inp["net_sizes"]}, ground truths {[len(g) for g in inp["gt_boxes"]]}, sampled RoIs '
+          f'{[int(c) for c in inp["roi_counts"]]}, positives {positives}, background rows {backgrounds}, levels of the box path {box_levels}, of the mask path '
+          f'{mask_levels} with {torch.bincount(torch.cat(real_rows(inp, "pos_levels", "pos_counts")).long(), minlength=4).tolist()} RoIs')
+    assert B == len(CASES[case]['frames']) and tuple(inp['padded_size']) == tuple(padded_size(case))
+    assert min(positives) >= 2 and min(backgrounds) >= 1
+    across = lambda levels: set().union(*levels)
+    if case == 'small':
+        assert across(box_levels) == across(mask_levels) == {0}
+    if case == 'two-levels':
+        assert len(across(box_levels)) >= 2 and len(across(mask_levels)) >= 2 and tuple(inp['padded_size']) == (160, 224)
+        assert all(len(g) == 1 and float(min(g[0, 2] - g[0, 0], g[0, 3] - g[0, 1])) > 130 for g in inp['gt_boxes'])
+    if case == 'four-levels':
+        assert B == 1 and tuple(inp['padded_size']) == (480, 640) == tuple(inp['net_sizes'][0])
+        assert across(box_levels) == across(mask_levels) == {0, 1, 2, 3}
+    if case == 'mixed':
+        assert len(set(inp['net_sizes'])) == B == 3 and [len(g) for g in inp['gt_boxes']] == [1, 3, 5] == [len(g) for g in inp['gt_masks']]
+        gts = CASES[case]['gt']
+        tiny = [(b, i) for b in range(B) for i, g in enumerate(gts[b]) if min(g[2] - g[0], g[3] - g[1]) < 8]
+        filled = {fill: [(b, i) for b in range(B) for i, g in enumerate(gts[b]) if len(g) > 5 and g[5] == fill] for fill in (0.0, 1.0)}
+        assert len(tiny) == len(filled[0.0]) == len(filled[1.0]) == 1
+        (tb, ti), (zb, zi), (ob, oi) = tiny[0], filled[0.0][0], filled[1.0][0]
+        assert ti in matched[tb] and zi in matched[zb] and oi in matched[ob]       # each of them is the match of a sampled positive
+        box = inp['gt_boxes'][tb][ti]
+        assert float(box[2] - box[0]) * 0.25 < 1.25 and float(box[3] - box[1]) * 0.25 < 1.25       # on map 0 about one cell: RoIAlign's max(extent, 1)
+        assert not inp['gt_masks'][zb][zi].any()
+        x1, y1, x2, y2 = (float(v) for v in inp['gt_boxes'][ob][oi])
+        assert inp['gt_masks'][ob][oi][math.ceil(y1) + 1:math.floor(y2) - 1, math.ceil(x1) + 1:math.floor(x2) - 1].all()
+        grids = dict(kinks)['mask target grid']                                    # (2, the real positives), image after image
+        first = sum(positives[:tb])
+        of_tiny = [first + r for r, m in enumerate(matched[tb]) if m == ti]
+        assert int(grids.min()) == 1 and bool((grids[:, of_tiny] == 1).all())
+        full = [bool(((g[:, 2] - g[:, 0] >= w - 1) & (g[:, 3] - g[:, 1] >= h - 1)).any()) for g, (h, w) in zip(inp['gt_boxes'], inp['net_sizes'])]
+        assert sum(full) >= 2                                                      # a ground truth over the whole frame on two images
 
 
 @functools.lru_cache(maxsize=None)

@@ -28,7 +28,9 @@ LOSS_KEYS = ('loss_objectness', 'loss_rpn_box_reg', 'loss_classifier', 'loss_box
 RPN_WEIGHTS, ROI_WEIGHTS = (1.0, 1.0, 1.0, 1.0), (10.0, 10.0, 5.0, 5.0)
 XFORM_CLIP = math.log(1000.0 / 16)
 BOUNDARY = 1e-4                      # cells; float32's rounding of a sample position here is below 1e-5
-MUTATIONS = ('mask_over_padded_rows', 'pool_detached', 'proposals_differentiable', 'sampling_ratio_1', 'level1_reads_map0', 'rpn_box_over_positives')
+MUTATIONS = ('mask_over_padded_rows', 'pool_detached', 'proposals_differentiable', 'sampling_ratio_1', 'level1_reads_map0', 'rpn_box_over_positives',
+             'level2_reads_map1', 'level3_reads_map2', 'gt_rows_at_gmax_stride')
+LEVEL_MUTATIONS = {f'level{l}_reads_map{l - 1}': l for l in (1, 2, 3)}             # the rows of level l read the map below with level l's scale
 HEAD_PREFIXES = ('rpn.head', 'roi_heads.box_head', 'roi_heads.box_predictor', 'roi_heads.mask_head', 'roi_heads.mask_predictor')
 # the head modules whose input is a ReLU's output
 AFTER_RELU = ('rpn.head.cls_logits', 'roi_heads.box_head.fc7', 'roi_heads.box_predictor.cls_score', 'roi_heads.mask_head.mask_fcn2',
@@ -120,13 +122,13 @@ def infer_scales(maps, net_sizes):
     return [2.0 ** round(math.log2(float(m.shape[2]) / top)) for m in maps]
 
 
-def multiscale_roi_align(maps, scales, boxes, im, levels, P, g, kinks=None, level1_reads_map0=False, name='roi_align'):
-    """the row's level selects the map and the scale -> (n,C,P,P)"""
+def multiscale_roi_align(maps, scales, boxes, im, levels, P, g, kinks=None, wrong_level=None, name='roi_align'):
+    """the row's level selects the map and the scale -> (n,C,P,P) (wrong_level: the mutation whose rows of that level read the map below)"""
     out = maps[0].new_zeros((int(boxes.shape[0]), int(maps[0].shape[1]), P, P))
     for l in range(len(maps)):
         rows = torch.nonzero(levels == l).reshape(-1)
         if rows.numel():
-            feat = maps[0] if (l == 1 and level1_reads_map0) else maps[l]
+            feat = maps[l - 1] if l == wrong_level else maps[l]
             out[rows] = roi_align(feat, im[rows], boxes[rows], scales[l], P, g, g, kinks, f'{name} level {l}')
     return out
 
@@ -270,6 +272,11 @@ class Chain:
         deltas = torch.cat([d.reshape(B, A, 4, *d.shape[2:]).permute(0, 3, 4, 1, 2).reshape(B, -1, 4) for d in deltas], 1)
         anchors = inp['anchors'].to(dt)
         gt = [g.to(dt) for g in inp['gt_boxes']]
+        if self.mutate == 'gt_rows_at_gmax_stride':
+            # the planted mistake: the ground truths lie one after another, image b's from offset[b] on; row b G_max + m is read instead of
+            # offset[b] + m (modulo the table's length, to stay inside it).  Nothing moves when every image holds G_max ground truths
+            table, G_max = torch.cat(gt), max(int(g.shape[0]) for g in gt)
+            gt = [table[(b * G_max + torch.arange(G_max)) % int(table.shape[0])] for b in range(B)]
 
         loss_objectness, loss_rpn_box_reg = rpn_losses(logits, deltas, anchors, gt, long('rpn_matched'), long('rpn_samp_idx'), long('rpn_samp_count'), kinks,
                                                        self.mutate == 'rpn_box_over_positives')
@@ -277,7 +284,7 @@ class Chain:
         # the box branch over the real rows
         roi_maps, g = maps[:4], 1 if self.mutate == 'sampling_ratio_1' else 2
         scales = infer_scales(roi_maps, inp['net_sizes'])
-        wrong_map = self.mutate == 'level1_reads_map0'
+        wrong_map = LEVEL_MUTATIONS.get(self.mutate)
         rows, im = self._real_rows(long('roi_counts'), int(inp['roi_boxes'].shape[0]) // B)
         boxes, labels = inp['roi_boxes'][rows].to(dt), long('roi_labels')[rows]
         if self.mutate == 'proposals_differentiable':

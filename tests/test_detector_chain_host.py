@@ -1,7 +1,8 @@
 """CPU tests that guard tests/detector_chain_ref.py, the plain-torch float64 statement of the detector's training forward that
 tests/test_detector_chain.py holds the device to: gradcheck of its RoIAlign, agreement with the twins as a third opinion,
-its teeth (six planted mistakes, each far above the device test's tolerance), and the stability of the two chosen cases: the float64 graph and
-its float32 replica take the same side at every kink."""
+its teeth (nine planted mistakes, each far above the device test's tolerance; the three that only the cases `four-levels` and `mixed` can see move
+not one bit on the two earlier cases), what each chosen case reaches, and the cases' stability: the float64 graph and its float32 replica take the
+same side at every kink."""
 import functools
 
 import numpy as np
@@ -177,9 +178,17 @@ def test_the_layerwise_trunk_is_the_modules_forward_and_the_storage_rounding_goe
 
 
 # ---- teeth: each planted mistake moves a gradient by far more than the device test allows ----------------------------------------------------------
+SEEN_ON = dict(level1_reads_map0='two-levels', level2_reads_map1='four-levels', level3_reads_map2='four-levels', gt_rows_at_gmax_stride='mixed')
+
+
 @pytest.mark.parametrize('mutation', cr.MUTATIONS)
 def test_a_planted_mistake_is_seen(mutation):
-    case = 'two-levels' if mutation == 'level1_reads_map0' else 'small'
+    case = SEEN_ON.get(mutation, 'small')
+    if case in ('four-levels', 'mixed'):                                           # the two earlier cases are blind to it: not one bit moves
+        for blind in ('small', 'two-levels'):
+            same = step(blind, mutate=mutation)[1], step(blind)[1]
+            assert set(same[0]) == set(same[1]) and all(torch.equal(same[0][k], same[1][k]) for k in same[1]), (mutation, blind)
+            assert all(torch.equal(a, b) for a, b in zip(step(blind, mutate=mutation)[2], step(blind)[2]))
     tol = tolerance(case)
     moved = ratios(step(case, mutate=mutation)[1], step(case)[1])
     worst = max(moved, key=moved.get)
@@ -203,6 +212,13 @@ def test_the_float64_graph_and_its_float32_replica_take_the_same_side_at_every_k
     on_a_border = sum(int((v % 1 == 0.5).sum()) for k, v in kinks64 if k.endswith('floor'))
     print(f'{case}: {len(kinks64)} kink tensors, {decisions} decisions, {on_a_border} RoIAlign samples on a cell border, disagreements: {differ}')
     assert not differ
+
+
+@pytest.mark.parametrize('case', list(cc.CASES))
+def test_a_case_reaches_what_it_was_chosen_for(case):
+    """on the twins' decisions: one frame with RoIs on all four levels of both paths; three frames of three network sizes with 1, 3 and 5 ground
+    truths, among them a tiny one, an all-zero and an all-one mask, each the match of a sampled positive (detector_chain_case.check_reach)"""
+    cc.check_reach(case, cc.cpu_inputs(case), step(case)[3])
 
 
 def test_the_second_case_leaves_level_zero_on_both_paths():
